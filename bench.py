@@ -1,15 +1,19 @@
 #!/usr/bin/env python3
 """Headline benchmark: training images/sec (fwd + bwd + AdamW step), HRFormer-small + fusion head, 256x192, bf16.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME] [--dump-outputs DIR] [--full]
 
 `--gpus N` without a torchrun environment starts N fresh ranks itself (one child process per GPU); under
 `python -m torch.distributed.run --nproc-per-node N` it reads RANK / LOCAL_RANK / WORLD_SIZE.  Rank 0 prints ONE JSON line
-(contract in the task statement).  Synthetic device-resident batches (seed 1234+rank), weak scaling (fixed per-GPU batch),
-DropPath on, BN in train mode, every parameter updated.  Extra objects on the line:
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = milliseconds per timed step, ...).  Synthetic device-resident
+batches (seed 1234+rank), weak scaling (fixed per-GPU batch), DropPath on, BN in train mode, every parameter updated.
+A plain run sets up, warms up, times the K steps and prints the line.  `--dump-outputs DIR` writes what the last timed step returned
+(and, for training, the updated parameters) as float32 DIR/<name>.npy files; same arguments -> same inputs, run after run.
+`--full` adds, after the timed steps, the measurements the headline figure does not need, as extra objects on the line:
   `roofline`      the dominant hand-written kernel of the step AND a `table` with the top aggregate kernels of the rocprof trace
-                  (profiles/), each on its dominant shape, each timed live with HIP events on the launch stream;
-  `cpu_baseline`  the CPU oracle (parity-pinned port of the reference) timed on this host's cores (rank 0, N=1 only).
+                  (profiles/), each on its dominant shape, each timed live with HIP events on the launch stream (`--no-roofline`: off);
+  `cpu_baseline`  the CPU oracle (parity-pinned port of the reference) timed on this host's cores (rank 0, N=1 only; `--no-cpu-baseline`: off).
+Without `--full` both are null.
 Other BASELINE.json configs (not the headline metric): --config hrnet_w32_384 (cfg 4: HRNet-W32 heatmap head, 384x288, training) and
 --config hrformer_base_infer (cfg 5: HRFormer-base + fusion head, K=13, 384x288, flip-test inference, hipGraph replay).
 """
@@ -409,6 +413,29 @@ def roofline_other(cfg_name, model, B, c):
     return rows
 
 
+DUMP_MAX_ELEMS = 1 << 21       # per array; at most ~14 arrays are dumped, so the files stay well under 64 MB in all
+
+
+def dump_outputs(path, arrays):
+    """Write each tensor of `arrays` as float32 `path/<name>.npy`.  One larger than DUMP_MAX_ELEMS is written flattened as a sample of
+    DUMP_MAX_ELEMS elements whose indices depend on its size alone (fixed seed), so two builds are compared element for element."""
+    import numpy as np
+    out = {}
+    for name, t in arrays.items():
+        t = t.detach().float()
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_MAX_ELEMS, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        out[name] = t.cpu().numpy()
+    total = sum(a.nbytes for a in out.values())
+    if total > 64 << 20:
+        raise SystemExit(f"bench.py --dump-outputs: {total} bytes of outputs, over the 64 MB limit")
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, f"{name}.npy"), a)
+    log(f"dumped {len(out)} arrays ({total / 2 ** 20:.1f} MB) to {path}")
+
+
 class InferRunner:
     """Flip-test inference as one replayed hipGraph (static input buffer); falls back to eager launches when capture is refused."""
 
@@ -455,8 +482,10 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="hrformer_small", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also run the roofline probes and the CPU baseline after the timed steps")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: leave out the roofline probes")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as float32 DIR/<name>.npy")
     ap.add_argument("--eager", action="store_true",
                     help="launch every kernel from the host each step instead of replaying the captured hipGraph")
     ap.add_argument("--single-stream", action="store_true", help="do not run the resolution branches on concurrent HIP streams")
@@ -574,8 +603,20 @@ def main():
 
     if rank == 0:
         log(f"timed region: {dt:.3f} s for {args.steps} steps -> {B * world * args.steps / dt:.1f} img/s")
+        if args.dump_outputs:
+            if c["mode"] == "train":
+                # the step's returned dict (losses, head outputs) and its effect: the fp32 parameters after the AdamW update
+                arrays = {"params": trainer.opt.flat}
+                for k, v in out.items():
+                    if isinstance(v, dict):
+                        arrays.update({f"{k}.{n}": t for n, t in v.items()})
+                    else:
+                        arrays[k] = v
+            else:
+                arrays = {"keypoints": out[0], "scores": out[1]}
+            dump_outputs(args.dump_outputs, arrays)
         roof = None
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             try:
                 if world > 1:
                     time.sleep(0.5)          # one watchdog polling period: the timed region's collectives are retired
@@ -589,7 +630,7 @@ def main():
                 log(f"roofline: {e['kernel'][:48]:48s} {e['us_per_launch']:8.1f} us isolated ({e.get('us_in_step_avg', '-')} in step)  "
                     f"{e['achieved']:8.1f} {e['unit']} = {e['frac'] * 100:5.1f} % of {e['bound']} peak")
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(args.config, c, cfg)
             log(f"cpu baseline: {cpu}")
         line = {

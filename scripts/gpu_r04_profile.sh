@@ -11,6 +11,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 rm -rf gpurun_out/prof4
 timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof4 -- python3 bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-roofline > gpurun_out/prof4.log 2>&1 || { tail -5 gpurun_out/prof4.log; exit 1; }
 st=$(find gpurun_out/prof4 -name "*kernel_stats.csv" | head -1); tr=$(find gpurun_out/prof4 -name "*kernel_trace.csv" | head -1)
+out=${st%%/*}      # the output directory of this run
 cp "$st" gpurun_out/r04_bench_kernel_stats.csv
 python scripts/trace_summary.py "$tr" 3 gpurun_out/r04_kernel_union.json > gpurun_out/r04_trace_summary.txt 2>&1 || true
 python scripts/profile_meta.py write gpurun_out/r04_profile_meta.json "rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-roofline" > /dev/null
@@ -39,9 +40,9 @@ sed "s/r03_pmc_sq_counters/r04_pmc_sq_counters/g" scripts/gpu_pmc_sq.sh > gpurun
 sed "s/r03_pmc_traffic_wide/r04_pmc_traffic_wide/g" scripts/gpu_pmc_traffic_wide.sh > gpurun_out/_wide.sh; bash gpurun_out/_wide.sh > gpurun_out/r04_wide.log 2>&1 || tail -3 gpurun_out/r04_wide.log
 bash scripts/gpu_sections.sh > gpurun_out/r04_sections.log 2>&1 || tail -3 gpurun_out/r04_sections.log
 # bench lines (the default line last: it is the one the roofline entries read profiles/ for)
-timeout -k 10 300 python bench.py --config hrnet_w32_384 --steps 30 --warmup 8 > gpurun_out/r04_bench_line_hrnet_w32_384.json 2> gpurun_out/r04_bench_w32.err || tail -3 gpurun_out/r04_bench_w32.err
-timeout -k 10 300 python bench.py --config hrformer_base_infer --steps 30 --warmup 5 > gpurun_out/r04_bench_line_hrformer_base_infer.json 2> gpurun_out/r04_bench_base.err || tail -3 gpurun_out/r04_bench_base.err
+timeout -k 10 300 python bench.py --full --config hrnet_w32_384 --steps 30 --warmup 8 > "$out/r04_bench_line_hrnet_w32_384.json" 2> "$out/r04_bench_w32.err" || tail -3 "$out/r04_bench_w32.err"
+timeout -k 10 300 python bench.py --full --config hrformer_base_infer --steps 30 --warmup 5 > "$out/r04_bench_line_hrformer_base_infer.json" 2> "$out/r04_bench_base.err" || tail -3 "$out/r04_bench_base.err"
 cp gpurun_out/r04_bench_kernel_stats.csv gpurun_out/r04_kernel_union.json gpurun_out/r04_profile_meta.json gpurun_out/r04_pmc_traffic_isolated.json gpurun_out/r04_pmc_traffic_step.json gpurun_out/r04_pmc_traffic_wide.json profiles/ 2>/dev/null
-timeout -k 10 400 python bench.py > gpurun_out/r04_bench_line.json 2> gpurun_out/r04_bench.err || tail -3 gpurun_out/r04_bench.err
+timeout -k 10 400 python bench.py --full > "$out/r04_bench_line.json" 2> "$out/r04_bench.err" || tail -3 "$out/r04_bench.err"
 grep "roofline\|cpu baseline\|timed region" gpurun_out/r04_bench.err | cut -c1-220
 for f in gpurun_out/r04_bench_line*.json; do echo $f; cut -c1-330 $f; echo; done

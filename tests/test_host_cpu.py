@@ -346,3 +346,25 @@ def test_bench_profile_fields_carry_their_source_and_go_stale(tmp_path, monkeypa
     assert bench.profile_source()["stale"] is True
     e = bench._entry("k", "shape", "mfma", 1e-4, flops=1e9, trace="k_conv8p(IgemmArgs)", single_shape=True, prof=prof, pmc=({}, {}))
     assert e["frac_in_step_union"] > e["frac_in_step"] > 0
+
+
+def test_bench_dump_outputs_writes_float32_and_samples_large_arrays_alike(tmp_path):
+    """bench.py --dump-outputs: every array as float32 <name>.npy; one above DUMP_MAX_ELEMS as a sample whose indices depend on its
+    size alone, so dumps of two builds line up element for element."""
+    sys.path.insert(0, ROOT)
+    import bench
+    n = bench.DUMP_MAX_ELEMS + 1000
+    big = torch.arange(n, dtype=torch.float64)
+    arrays = {"loss": torch.tensor(2.5, requires_grad=True), "heatmaps": torch.randn(2, 3, 4, 5).to(torch.bfloat16), "params": big}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    for name in arrays:
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, b)
+    assert np.load(tmp_path / "a" / "loss.npy") == 2.5
+    assert np.array_equal(np.load(tmp_path / "a" / "heatmaps.npy"), arrays["heatmaps"].float().numpy())
+    s = np.load(tmp_path / "a" / "params.npy")
+    assert s.shape == (bench.DUMP_MAX_ELEMS,) and np.all(np.diff(s) > 0) and s[-1] < n      # sorted distinct elements of the array
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "c"), {f"x{i}": big for i in range(9)})             # 9 x 8 MB: over the 64 MB limit
+    assert not (tmp_path / "c").exists()
