@@ -77,6 +77,29 @@ int pk_affine_coords(const float* coords, const float* center, const float* scal
 int pk_pose_records(const float* keypoints, const float* scores, float* records, float* instance_score, int B, int K,
                     void* stream);
 
+/* ---- f1: COCO keypoint AP/AR (COCOeval iouType='keypoints', one category, one maxDets; utils/coco_eval.py holds the host side) --------
+ * Everything fp64.  Images are the evaluated image ids in ascending order; ground truths and detections are grouped by image in CSR form
+ * (gt_off, dt_off: n_img + 1 offsets; file / record order inside an image).  gt_kpt (G,K,3) with the visibility, gt_bbox (G,4) x y w h,
+ * gt_area (G); dt_kpt (N,K,3) (only x, y read), dt_score (N); vars = (2 sigma)^2 (K).  cap_off[i] = sum of min(n_j, max_dets) over j < i,
+ * oks_off[i] = sum of min(n_j, max_dets) * G_j.
+ * pk_coco_kpt_oks (computeOks): per image, stable-ranks the detections by descending score (NaN last, ties in record order), keeps the
+ *   first max_dets (cap_idx[cap_off[i] + r] = detection index of rank r) and writes the OKS block oks[oks_off[i] + r * G_i + g].
+ *   K <= 64, max_dets <= 64.
+ * pk_coco_kpt_eval (evaluateImg + accumulate): gt_flags bit 0 = ignore (iscrowd or num_keypoints == 0), bit 1 = iscrowd; dt_area (N);
+ *   area_rng (A,2) inclusive; iou_thrs (T); rec_thrs (R); A * T <= 64.  Writes dt_match / dt_ignore (A*T, n_cap): matched ground truth
+ *   (index inside its image, file order) or -1, and the ignore flag of each capped slot per curve a * T + t; npig (n_img, A): non-ignored
+ *   ground truths; order (n_cap): capped slots by descending score, stable; precision (T,R,A) and recall (T,A) in COCOeval's
+ *   eval['precision'][:, :, 0, :, 0] / eval['recall'][:, 0, :, 0] layout (-1 where an area has no non-ignored ground truth).
+ *   ws: pk_coco_kpt_eval_ws_floats(n_gt, n_cap, A, T) floats.                                                                        */
+int pk_coco_kpt_oks(const double* gt_kpt, const double* gt_bbox, const double* gt_area, const int32_t* gt_off, const double* dt_kpt,
+                    const double* dt_score, const int32_t* dt_off, const double* vars, const int32_t* cap_off, const int64_t* oks_off,
+                    int32_t* cap_idx, double* oks, int n_img, int K, int max_dets, void* stream);
+int pk_coco_kpt_eval_ws_floats(int n_gt, int n_cap, int A, int T);
+int pk_coco_kpt_eval(const double* oks, const int64_t* oks_off, const int32_t* gt_off, const double* gt_area, const int32_t* gt_flags,
+                     const int32_t* cap_off, const int32_t* cap_idx, const double* dt_score, const double* dt_area, const double* area_rng,
+                     const double* iou_thrs, const double* rec_thrs, int32_t* dt_match, uint8_t* dt_ignore, int32_t* npig, int32_t* order,
+                     void* ws, double* precision, double* recall, int n_img, int n_gt, int n_cap, int A, int T, int R, void* stream);
+
 /* ---- f2: input pipeline (datasets/transforms.py:42-47,128-131,212-217; datasets/coco_dataset.py:156-163; inference.py:83-110):
  * affine crop (OpenCV 8-bit warpAffine INTER_LINEAR / BORDER_CONSTANT 0 integer algorithm, see oracle/warp.py; parity unpinned vs cv2
  * itself) + optional column mirror + optional BGR->RGB + ((v/255) - mean)/std, whole batch, one launch.  src_u8: device buffer holding the

@@ -133,6 +133,43 @@ def pose_records(keypoints, scores):
     return rec, inst
 
 
+F64, I64 = torch.float64, torch.int64
+
+
+def coco_kpt_oks(gt_kpt, gt_bbox, gt_area, gt_off, dt_kpt, dt_score, dt_off, vars_, cap_off, oks_off, max_dets):
+    """computeOks of every image (pk_coco_kpt_oks).  gt_kpt (G,K,3), dt_kpt (N,K,3) fp64; *_off int32 CSR offsets over the images, oks_off
+    int64; vars_ = (2 sigma)^2.  -> cap_idx (n_cap,) int32 = detection of each capped slot (per image by descending score), oks (flat
+    fp64, one D_i x G_i block per image at oks_off[i])."""
+    gk, dk = _chk(gt_kpt, F64, "gt_kpt"), _chk(dt_kpt, F64, "dt_kpt")
+    go, do, co, oo = _chk(gt_off, I32, "gt_off"), _chk(dt_off, I32, "dt_off"), _chk(cap_off, I32, "cap_off"), _chk(oks_off, I64, "oks_off")
+    n_img, K = go.numel() - 1, dk.shape[1]
+    n_cap, n_oks = int(co[-1]), int(oo[-1])
+    cap_idx = torch.empty(max(n_cap, 1), dtype=I32, device=dk.device)
+    oks = torch.empty(max(n_oks, 1), dtype=F64, device=dk.device)
+    _call_if(n_img * n_cap, "pk_coco_kpt_oks", gk, _chk(gt_bbox, F64, "gt_bbox"), _chk(gt_area, F64, "gt_area"), go, dk,
+             _chk(dt_score, F64, "dt_score"), do, _chk(vars_, F64, "vars"), co, oo, cap_idx, oks, n_img, K, int(max_dets), stream_ptr())
+    return cap_idx[:n_cap], oks[:n_oks]
+
+
+def coco_kpt_eval(oks, oks_off, gt_off, gt_area, gt_flags, cap_off, cap_idx, dt_score, dt_area, area_rng, iou_thrs, rec_thrs):
+    """evaluateImg + accumulate (pk_coco_kpt_eval) over the blocks of `coco_kpt_oks`.  area_rng (A,2), iou_thrs (T,), rec_thrs (R,) fp64.
+    -> dict: precision (T,R,A), recall (T,A), dt_match / dt_ignore (A,T,n_cap), npig (n_img,A), order (n_cap,)."""
+    go, co = _chk(gt_off, I32, "gt_off"), _chk(cap_off, I32, "cap_off")
+    ar, it, rt = _chk(area_rng, F64, "area_rng"), _chk(iou_thrs, F64, "iou_thrs"), _chk(rec_thrs, F64, "rec_thrs")
+    dev = ar.device
+    n_img, n_gt, n_cap = go.numel() - 1, int(go[-1]), cap_idx.numel()
+    A, T, R = ar.shape[0], it.numel(), rt.numel()
+    out = {"precision": torch.empty(T, R, A, dtype=F64, device=dev), "recall": torch.empty(T, A, dtype=F64, device=dev),
+           "dt_match": torch.empty(A, T, n_cap, dtype=I32, device=dev), "dt_ignore": torch.empty(A, T, n_cap, dtype=torch.uint8, device=dev),
+           "npig": torch.empty(n_img, A, dtype=I32, device=dev), "order": torch.empty(n_cap, dtype=I32, device=dev)}
+    ws = torch.empty(max(int(_lib.lib.pk_coco_kpt_eval_ws_floats(n_gt, n_cap, A, T)), 1), dtype=F32, device=dev)
+    _call_if(n_img * n_gt * n_cap, "pk_coco_kpt_eval", _chk(oks, F64, "oks") if oks.numel() else ws, _chk(oks_off, I64, "oks_off"), go,
+             _chk(gt_area, F64, "gt_area"), _chk(gt_flags, I32, "gt_flags"), co, _chk(cap_idx, I32, "cap_idx"), _chk(dt_score, F64, "dt_score"),
+             _chk(dt_area, F64, "dt_area"), ar, it, rt, out["dt_match"], out["dt_ignore"], out["npig"], out["order"], ws, out["precision"],
+             out["recall"], n_img, n_gt, n_cap, A, T, R, stream_ptr())
+    return out
+
+
 def flip_merge(hm, hm_from_flipped, partner):
     a, b = _chk(hm), _chk(hm_from_flipped)
     B, K, H, W = a.shape

@@ -2,9 +2,9 @@
 
 `COCOEvaluator.update` takes what `validate()` has at hand.  When the predictions are device tensors the (B,K,3) records and the
 per-instance scores come from one kernel (pk_pose_records) and ONE device->host copy per batch; numpy inputs (the reference's
-calling convention) are accepted as they are -- the evaluator itself is host bookkeeping (a list of dicts for pycocotools).
-COCO AP through pycocotools is third-party code outside the path: `evaluate()` hands it the records when an
-annotation file is given, and otherwise reports the precision of greedy OKS matching against `gt_annotations=` (array form)."""
+calling convention) are accepted as they are -- the evaluator itself is host bookkeeping (a list of record dicts).
+With an annotation file `evaluate()` reports COCO keypoint AP / AR (utils/coco_eval.py: COCOeval's arithmetic on the device, no
+pycocotools); without one, the precision of greedy OKS matching against `gt_annotations=` (array form)."""
 from collections import defaultdict
 from typing import Dict, List, Optional
 
@@ -59,26 +59,18 @@ class COCOEvaluator:
         return oks_precision(self.predictions, gt_annotations, self.oks_sigmas, self.oks_thresholds)
 
     def evaluate(self, gt_annotations: Optional[List[Dict]] = None) -> Dict[str, float]:
-        """AP numbers for the collected records.  With an annotation file the arithmetic is pycocotools' (third-party, outside the
-        path: SURVEY §2 row 12 -- this only hands it the records); without one, `gt_annotations` (dicts with image_id / keypoints /
-        area) are matched by OKS (`oks_precision`), the stand-in train.py uses to pick best.pth on loaders that carry no file."""
+        """AP numbers for the collected records.  With an annotation file: the ten COCO keypoint numbers (AP, AP50, AP75, AP_M, AP_L,
+        AR, AR50, AR75, AR_M, AR_L) of COCOKeypointEval with this evaluator's OKS sigmas; without one, `gt_annotations` (dicts with
+        image_id / keypoints / area) are matched by OKS (`oks_precision`), the stand-in train.py uses to pick best.pth on loaders that
+        carry no file."""
         if not self.predictions:
             return {'AP': 0.0, 'AP50': 0.0, 'AP75': 0.0}
         if self.ann_file is not None:
-            return _pycocotools_keypoint_stats(self.ann_file, self.predictions)
+            from .coco_eval import COCOKeypointEval
+            return COCOKeypointEval(self.ann_file, self.oks_sigmas).evaluate(self.predictions)
         if gt_annotations is None:
             raise ValueError("Either ann_file or gt_annotations must be provided")
         return oks_precision(self.predictions, gt_annotations, self.oks_sigmas, self.oks_thresholds)
-
-
-def _pycocotools_keypoint_stats(ann_file, records):
-    from pycocotools.coco import COCO              # ImportError here means "install pycocotools", as in the reference
-    from pycocotools.cocoeval import COCOeval
-    gt = COCO(ann_file)
-    ev = COCOeval(gt, gt.loadRes(list(records)), 'keypoints')       # loadRes takes the list itself: no temporary json file
-    for stage in (ev.evaluate, ev.accumulate, ev.summarize):
-        stage()
-    return dict(zip(('AP', 'AP50', 'AP75', 'AP_M', 'AP_L', 'AR', 'AR50', 'AR75', 'AR_M', 'AR_L'), ev.stats))
 
 
 def oks_precision(records, gts, sigmas, thresholds):

@@ -3,9 +3,9 @@
 
 Flip-test inference + decode run entirely on the GPU (`PoseEstimator.inference`: two forwards, one flip-merge kernel, one
 decode kernel); the heat-px -> image transform of validate.py:100-117 is one kernel (`heatmap_to_image_coords`) instead of a
-Python B x K loop; `COCOEvaluator.update` receives device tensors.  COCO AP needs pycocotools + annotation files on the machine
-(third-party, outside the hot path): when they are missing, AP is the reference's own OKS matching (utils/metrics.py:206-270) against the
-loader's ground truth.
+Python B x K loop; `COCOEvaluator.update` receives device tensors.  A loader whose dataset carries an annotation file (the COCO loader)
+gets the ten COCO keypoint AP / AR numbers (utils/coco_eval.py, on the device, no pycocotools); a loader without one (SyntheticLoader) gets
+the reference's own OKS matching (utils/metrics.py:206-270) against the loader's ground truth.
 """
 import argparse
 import logging
@@ -23,25 +23,16 @@ from infantposeestimation_gaussianbias_amd.utils import AverageMeter  # noqa: E4
 from infantposeestimation_gaussianbias_amd.utils.postprocess import heatmap_to_image_coords  # noqa: E402
 
 
-def _coco_available(cfg):
-    ann = os.path.join(cfg.data.data_root, cfg.data.val_ann)
-    try:
-        import pycocotools  # noqa: F401
-    except ImportError:
-        return None
-    return ann if os.path.isfile(ann) else None
-
-
 @torch.no_grad()
 def validate(model, loader, device, cfg, logger, flip_test=True):
     """train.py:231-325 == validate.py:39-140 of the reference: loss + decode + image-space transform + COCOEvaluator.update per batch,
     then AP.  Decode, flip merge, the heat-px -> image transform and the evaluator's record arrays are kernels (no B x K Python loops, one
-    device->host copy per batch).  AP comes from pycocotools when it and the annotation file exist; otherwise from the reference's own
-    OKS matching against the batch's ground truth mapped to image space (synthetic loaders carry no annotation file)."""
+    device->host copy per batch).  AP / AR come from COCOKeypointEval when the loader's dataset has an annotation file; otherwise AP is the
+    reference's own OKS matching against the batch's ground truth mapped to image space (synthetic loaders carry no annotation file)."""
     from infantposeestimation_gaussianbias_amd.utils import COCOEvaluator
     model.eval()
     loss_meter = AverageMeter("Loss", ":.4f")
-    ann = _coco_available(cfg)
+    ann = getattr(getattr(loader, "dataset", None), "ann_file", None)
     evaluator = COCOEvaluator(ann_file=ann, num_keypoints=cfg.data.num_keypoints)
     flip_pairs = cfg.data.flip_pairs if flip_test else None
     gts = []
@@ -66,8 +57,8 @@ def validate(model, loader, device, cfg, logger, flip_test=True):
             logger.info(f"  [{i}/{len(loader)}] Loss: {loss_meter.avg:.4f}")
     metrics = dict(evaluator.evaluate(gt_annotations=None if ann else gts))
     metrics["loss"] = loss_meter.avg
-    logger.info(f"Validation Loss: {loss_meter.avg:.4f}  AP: {metrics['AP']:.4f}  AP50: {metrics['AP50']:.4f}  AP75: {metrics['AP75']:.4f}"
-                + ("" if ann else "  (reference OKS matching against the loader's ground truth: no pycocotools / annotation file)"))
+    logger.info(f"Validation Loss: {loss_meter.avg:.4f}  " + "  ".join(f"{k}: {v:.4f}" for k, v in metrics.items() if k != "loss")
+                + ("" if ann else "  (reference OKS matching against the loader's ground truth: the loader has no annotation file)"))
     return metrics, evaluator.predictions
 
 
