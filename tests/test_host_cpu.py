@@ -89,6 +89,29 @@ def test_ops_refuse_cpu_tensors():
         hipops.argmax_decode(torch.zeros(1, 1, 4, 4))
 
 
+_NORM_ROWS = sorted({1, 2, 7, 31, 32, 33, 127, 128, 129, 240, 3077, 32767, 32768, 32769, 40000, 65536, 196608, 221184, 1 << 20,
+                     (1 << 30) - 1} | set(range(1, 70000, 97)))
+
+
+def test_norm_block_count_rules():
+    """Partial-block counts of the normalisation backward kernels, which size the partial buffers the GPU tests allocate: the small-tensor
+    BatchNorm path re-reduces at most 64 partial rows per workgroup, the grouped one at most 256 above 32 768 rows, and every launch has
+    1 .. 1024 blocks.  Host-side queries: the library loads and answers them without a GPU."""
+    from infantposeestimation_gaussianbias_amd import _lib
+    L = _lib.lib
+    for rows in _NORM_ROWS:
+        nb, nbg, nl = L.pk_bn_bwd_blocks(rows), L.pk_bn_bwd_group_blocks(rows), L.pk_ln_bwd_blocks(rows)
+        assert 1 <= nb <= 1024 and 1 <= nl <= 1024 and 1 <= nbg, rows
+        assert nb <= rows and nl <= rows and nbg <= rows, rows               # no block without rows
+        if rows <= 32768:
+            assert nb <= 64 and nbg == nb, rows                              # the grouped member takes the single entry's rule there
+        else:
+            assert nbg <= 256, rows
+        assert nl == min(1024, -(-rows // 32)), rows
+    assert L.pk_bn_bwd_blocks(32768) == 64 and L.pk_bn_bwd_blocks(32769) == 1024     # the two BatchNorm paths on either side of the limit
+    assert L.pk_ln_bwd_blocks(196608) == 1024 and L.pk_ln_bwd_blocks(3 * 1024 + 5) == 97
+
+
 def test_config_surface_matches_reference_defaults(golden):
     from infantposeestimation_gaussianbias_amd.configs import get_config
     ref = golden("meta.json")["schedule"]["default_config"]
