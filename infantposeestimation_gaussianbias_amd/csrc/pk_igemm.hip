@@ -896,8 +896,10 @@ __global__ void __launch_bounds__(512, 2) k_conv8p(IgemmArgs p) {
         c8_barrier();
     }
 
-    // ---- BatchNorm statistics: a wave's 128 pixels are exactly one statistics tile (STAT_ROWS = 128) of its 64 channels
-    if (p.stats) {
+    // ---- BatchNorm statistics: a wave's 128 pixels are exactly one statistics tile (STAT_ROWS = 128) of its 64 channels.  A wave group
+    // whose 128 pixels all lie beyond M writes no row: the buffer has pk_conv_stats_tiles(M) = ceil(M / 128) rows, and the second half of
+    // a last tile with M % 256 in (0, 128] would be row ceil(M / 128), past its end.
+    if (p.stats && m0 + grp * 128 < p.M) {
         float* dst = p.stats + (size_t)(mt * 2 + grp) * 2 * p.N + n0 + wn * 64;
 #pragma unroll
         for (int a = 0; a < 4; ++a)

@@ -112,6 +112,44 @@ def test_norm_block_count_rules():
     assert L.pk_ln_bwd_blocks(196608) == 1024 and L.pk_ln_bwd_blocks(3 * 1024 + 5) == 97
 
 
+def test_block_kernel_cases_reach_their_loop_regimes():
+    """The cases of tests/test_gpu_block_kernels_at_scale.py claim loop regimes of the persistent block kernels (several items per wave,
+    ragged walks, several windows per workgroup) and chunk launches with at most one item per wave.  The release build fixes the grid
+    caps at compile time, so the claims follow from the library's size queries: a retuned cap fails here instead of letting the GPU
+    cases fall back to one item per wave unnoticed."""
+    from infantposeestimation_gaussianbias_amd import _lib
+    L = _lib.lib
+    # fused attention half: 4 waves per workgroup, one window per wave and iteration
+    waves = lambda nw: 4 * L.pk_attn_block_blocks(nw)                                  # noqa: E731
+    assert 4480 / waves(4480) > 4                                                     # C = 32, B = 64, 64 x 48
+    assert 1050 - waves(1050) == 26                                                   # B = 15: 26 waves take a second window
+    assert waves(1280) < 1280 < 2 * waves(1280) and 1280 % waves(1280) != 0          # C = 64, B = 64, 32 x 24: ragged
+    assert 70 <= waves(70) and 20 <= waves(20)                                        # the per-sample chunks: one window per wave
+    # fused MLP half: 32-row groups, 4 waves per workgroup
+    for M, C, dw_min in ((196608, 32, 6), (49152, 64, 12), (62403, 64, 15)):
+        groups = -(-M // 32)
+        assert groups // (4 * L.pk_ln_mlp_dw_blocks(M, C)) >= dw_min, (M, C)
+    assert 6144 == 3 * 4 * L.pk_ln_mlp_dx_blocks(196608, 32)                           # fwd / dx at C = 32: 3 groups per wave
+    assert L.pk_ln_mlp_dw_blocks(49152, 64) == 32 and L.pk_ln_mlp_hidden_slice(64) == 32    # 32 workgroups x 8 slices
+    assert 62403 % 32 != 0
+    for rows, C in ((3072, 32), (768, 64), (1023, 64)):                                # per-sample chunks: one group per wave
+        assert -(-rows // 32) <= 4 * min(L.pk_ln_mlp_dx_blocks(rows, C), L.pk_ln_mlp_dw_blocks(rows, C)), (rows, C)
+    # unfused window attention backward: windows per workgroup, groups per head (> 256: several passes of k_relbias_reduce)
+    for nw, heads, per_group in ((1280, 2, 2), (4480, 1, 3), (4480, 2, 5)):
+        per_head = L.pk_window_attn_bwd_groups(nw, heads) // heads
+        assert -(-nw // per_head) == per_group and per_head > 256, (nw, heads)
+        assert L.pk_window_attn_bwd_groups(512, heads) == 512 * heads                 # the 512-window chunks: one window per group
+    assert L.pk_window_attn_bwd_groups(4480, 1) == 1494
+    # wide forward kernels at cfg 5 sizes: the launches the library takes for them (grid 256 x 8 waves for attention; for the MLP one
+    # workgroup per CU over 1 536 tiles of 256 rows with the resident C = 80 weights, one per tile at C = 160)
+    assert L.pk_attn_block_wide_supported(80, 2, 8960) and 8960 > 256 * 8
+    assert L.pk_ln_mlp_wide_supported(80, 320, 393216) and L.pk_ln_mlp_wide_supported(160, 640, 98304)
+    # the weight gradients of the block-level cases run in several slices (flags: 1 = row map of x, 2 = row map of g, 4 = row scale)
+    for M, Nn, Cin, Hs, Ws, flags in ((4480 * 49, 96, 32, 0, 0, 0), (4480 * 49, 32, 32, 64, 48, 6), (1280 * 49, 192, 64, 32, 24, 1),
+                                      (1280 * 49, 64, 64, 32, 24, 6), (12288, 128, 512, 0, 0, 4), (12288, 512, 128, 0, 0, 0)):
+        assert L.pk_wgrad_slices(M, Nn, Cin, 1, 1, Hs, Ws, flags) >= 2, (M, Nn, Cin, flags)
+
+
 def test_config_surface_matches_reference_defaults(golden):
     from infantposeestimation_gaussianbias_amd.configs import get_config
     ref = golden("meta.json")["schedule"]["default_config"]
