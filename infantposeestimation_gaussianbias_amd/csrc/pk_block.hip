@@ -252,9 +252,6 @@ __global__ void __launch_bounds__(256) k_mlp_fwd(MlpArgs p) {
 // loads of x, gamma, beta and of the weight columns are out of range there.  `c_real` < C (padded twins, models/padded.py): the
 // LayerNorm statistics run over the real channels -- the padded ones hold exact zeros, so the sums only need the divisor, and the
 // squared-deviation sum is corrected by (32 NK - c_real) mean^2.
-#ifndef PK_MLP_WIDE_GELU_POLY
-#define PK_MLP_WIDE_GELU_POLY 1
-#endif
 // RESIDENT (C = 80 with hidden 320: 110 KB of fragments): every slice is staged ONCE per workgroup, the workgroups are persistent over
 // 32-token groups and the waves run through the slices on their own -- no barrier after the prologue.
 template <int NK, int NCT, int WAVES, bool RESIDENT>
@@ -406,11 +403,7 @@ __global__ void __launch_bounds__(64 * WAVES) k_mlp_fwd_w(MlpArgs p, int C, int 
             bf16x8 hf[RT];
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt) {
-#if PK_MLP_WIDE_GELU_POLY
                 hf[rt] = pack2(gelu_erf_poly(h[rt][0]), gelu_erf_poly(h[rt][1]));          // packed-fp32 polynomial form (pk_common.h)
-#else
-                hf[rt] = pack2(gelu_erf(h[rt][0]), gelu_erf(h[rt][1]));
-#endif
             }
 #pragma unroll
             for (int ct = 0; ct < NCT; ++ct) {
@@ -1659,7 +1652,7 @@ static inline int attn_blocks(int n_windows) {
     // one 4-wave workgroup per CU, each wave walking ~4 windows (B = 64): 1 024 workgroups (two rounds of two per CU, one window per wave)
     // cost the step 0.13 ms more (15.49-15.56 vs 15.38 ms, three alternating runs; 128 / 192 / 512 / 2 048: 15.37 / 15.41 / 15.37 / 15.49) --
     // a quarter of the weight prologues, and room on every CU for the other branches' workgroups
-    static const int cap = PK_KNOB("PK_ATTN_WGS", 256);
+    constexpr int cap = 256;
     const int need = (n_windows + 3) / 4;
     return need < cap ? (need < 1 ? 1 : need) : cap;
 }
@@ -1711,9 +1704,8 @@ extern "C" int pk_attn_block_fwd(const void* x, const int32_t* rowmap, const flo
 
 // Head_dim-40 twins, forward only.  `n_windows` > 0 also asks whether the launch has enough windows to pay (one wave per window).
 extern "C" int pk_attn_block_wide_supported(int C, int heads, int n_windows) {
-    static const int on = PK_KNOB("PK_ATTN_WIDE", 1);
-    static const int min_win = PK_KNOB("PK_ATTN_WIDE_MIN_WINDOWS", 1024);
-    if (!(on && C == 80 && heads == 2)) return 0;
+    constexpr int min_win = 1024;
+    if (!(C == 80 && heads == 2)) return 0;
     return n_windows <= 0 || n_windows >= min_win;
 }
 template <int NK, int NCT, int HEADS, int WAVES>
@@ -1728,7 +1720,7 @@ static int attn_wide_launch(const AttnArgs& a, int C, int c_real, hipStream_t st
         }
         attr_set = true;
     }
-    static const int cap = PK_KNOB("PK_ATTN_WIDE_WGS", 256);      // one 8-wave workgroup per CU (104 KB of LDS)
+    constexpr int cap = 256;      // one 8-wave workgroup per CU (104 KB of LDS)
     const int need = (a.n_windows + WAVES - 1) / WAVES;
     hipLaunchKernelGGL((k_attn_fwd_w<NK, NCT, HEADS, WAVES>), dim3(need < cap ? need : cap), dim3(64 * WAVES), lds, st, a, C, c_real);
     return pk_launch_status("pk_attn_block_wide_fwd");
@@ -1753,8 +1745,6 @@ extern "C" int pk_attn_block_wide_fwd(const void* x, const int32_t* rowmap, cons
 
 // ================================================================================================ C-ABI
 static inline int mlp_hidden_slice(int C) {          // hidden units per blockIdx.y slice of the weight-gradient kernel
-    static const int env = PK_KNOB("PK_MLP_HS", 0);
-    if (env == 32 || env == 64 || (env == 128 && C == 32)) return env;
     // Measured (B = 64): the 128 accumulator registers of HS * C = 4096 hold the kernel at one wave per SIMD (C = 32: 66 us);
     // half of that (two waves per SIMD) runs the same work in 40 us although every slice recomputes LayerNorm.  (Round 4, with VGPR-form
     // MFMAs the 128-unit slice needs 255 registers, i.e. two waves per SIMD as well: 15.48-15.51 vs 15.43-15.51 ms per step -- no gain.)
@@ -1769,25 +1759,15 @@ extern "C" int pk_ln_mlp_slab_floats(int C) {
 }
 // workgroups (4 waves, one 32-token group per wave and iteration): enough to fill 256 CUs twice, never more than the work
 static inline int mlp_blocks(int M, int target) {
-    static const int env_target = PK_KNOB("PK_MLP_WGS", 0);
-    if (env_target > 0) target = env_target;
     const int need = (mlp_row_groups(M) + 3) / 4;
     return need < target ? (need < 1 ? 1 : need) : target;
 }
-static inline int mlp_dx_target(int C) {
-    static const int t32 = PK_KNOB("PK_MLP_DX32_WGS", 512), t64 = PK_KNOB("PK_MLP_DX64_WGS", 512);
-    return C == 32 ? t32 : t64;
-}
-static inline int mlp_fwd_target(int C) {
-    static const int t32 = PK_KNOB("PK_MLP_FWD32_WGS", 512), t64 = PK_KNOB("PK_MLP_FWD64_WGS", 512);
-    return C == 32 ? t32 : t64;
-}
+constexpr int MLP_FWD_WGS = 512, MLP_DX_WGS = 512;          // forward and data gradient, C = 32 and C = 64 alike
 static inline int mlp_dw_target(int C) {
-    // (C = 64: 32 x 8 slices = one workgroup per CU; 64 x 8 ran 38 us in isolation and the step 0.07 ms slower, see PK_ATTN_WGS)
-    static const int t32 = PK_KNOB("PK_MLP_DW32_WGS", 256), t64 = PK_KNOB("PK_MLP_DW64_WGS", 32);
-    return C == 32 ? t32 : t64;
+    // (C = 64: 32 x 8 slices = one workgroup per CU; 64 x 8 ran 38 us in isolation and the step 0.07 ms slower, see attn_blocks)
+    return C == 32 ? 256 : 32;
 }
-extern "C" int pk_ln_mlp_dx_blocks(int M, int C) { return mlp_blocks(M, mlp_dx_target(C)); }
+extern "C" int pk_ln_mlp_dx_blocks(int M, int C) { return mlp_blocks(M, MLP_DX_WGS); }
 // (fewer, longer-lived workgroups: each one stages its weight slice and ends with a 4-phase slab reduction; 256 x slices
 // workgroups beat 512 and 1024 at every slice width)
 // workgroups beat 512 and 1024 at every slice width; C = 64 with its 8 slices: 64 x 8 = 38 us, 128 x 8 = 46 us, 256 x 8 = 67 us)
@@ -1811,7 +1791,7 @@ extern "C" int pk_ln_mlp_fwd(const void* x, const float* gamma, const float* bet
     int rc = mlp_check("pk_ln_mlp_fwd", a, C);
     if (rc) return rc;
     PK_REQUIRE(w1 && w2 && b2 && y, "pk_ln_mlp_fwd: null pointer");
-    const dim3 grid(mlp_blocks(M, mlp_fwd_target(C))), block(256);
+    const dim3 grid(mlp_blocks(M, MLP_FWD_WGS)), block(256);
     if (C == 32) hipLaunchKernelGGL(k_mlp_fwd<32>, grid, block, 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(k_mlp_fwd<64>, grid, block, 0, (hipStream_t)stream, a);
     return pk_launch_status("pk_ln_mlp_fwd");
@@ -1830,20 +1810,18 @@ static int pk_cu_count_block() {
 // `M` > 0 also asks whether the launch pays: a workgroup walks ALL hidden slices for its 128 / 256 tokens, so a launch with few
 // workgroups is one long serial chain per CU -- measured in cfg 5 (HRFormer-base twin, B = 64 with the flip): C = 320 with 13 824 tokens
 // (108 workgroups) 151 us against ~70 us for the unfused fc1 + fc2 GEMMs (step 29.35 ms with it, 27.45 ms without), while C = 80
-// (864 workgroups) and C = 160 (216) win 2.4 ms per step.  Default: at least PK_MLP_WIDE_MIN_WGS = 160 workgroups.
+// (864 workgroups) and C = 160 (216) win 2.4 ms per step.  Hence at least min_wgs = 160 workgroups.
 extern "C" int pk_ln_mlp_wide_supported(int C, int hidden, int M) {
-    static const int on = PK_KNOB("PK_MLP_WIDE", 1);
-    static const int min_wgs = PK_KNOB("PK_MLP_WIDE_MIN_WGS", 160);
-    if (!(on && (C == 80 || C == 128 || C == 160 || C == 256 || C == 320) && hidden > 0 && hidden % 32 == 0 && hidden <= 2048)) return 0;
+    constexpr int min_wgs = 160;
+    if (!((C == 80 || C == 128 || C == 160 || C == 256 || C == 320) && hidden > 0 && hidden % 32 == 0 && hidden <= 2048)) return 0;
     const int per_wg = C >= 256 ? 128 : 256;
     return M <= 0 || (M + per_wg - 1) / per_wg >= min_wgs;
 }
 template <int NK, int NCT, int WAVES>
 static int mlp_wide_launch(const MlpArgs& a, int C, int c_real, int HD, hipStream_t st) {
     constexpr int NF = 2 * NK + NCT;
-    static const int res_on = PK_KNOB("PK_MLP_WIDE_RESIDENT", 1);
     const int NS = HD / 32, lds_res = NS * NF * 1024 + HD * 4;
-    const bool resident = res_on && lds_res <= 150 * 1024;         // every slice fits: stage once, persistent workgroups, no per-slice barrier
+    const bool resident = lds_res <= 150 * 1024;         // every slice fits: stage once, persistent workgroups, no per-slice barrier
     const int lds = resident ? lds_res : 2 * NF * 1024 + HD * 4;
     static bool attr_set = false;
     if (!attr_set) {
@@ -1917,10 +1895,7 @@ extern "C" int pk_ln_mlp_bwd_dw(const void* dy, const void* x, const float* gamm
     const int hs = mlp_hidden_slice(C);
     const dim3 grid(pk_ln_mlp_dw_blocks(M, C), (4 * C) / hs), block(256);
     hipStream_t st = (hipStream_t)stream;
-    if (C == 32 && hs == 128) hipLaunchKernelGGL((k_mlp_bwd_dw<32, 128>), grid, block, 0, st, a);
-    else if (C == 32 && hs == 64) hipLaunchKernelGGL((k_mlp_bwd_dw<32, 64>), grid, block, 0, st, a);
-    else if (C == 32) hipLaunchKernelGGL((k_mlp_bwd_dw<32, 32>), grid, block, 0, st, a);
-    else if (hs == 64) hipLaunchKernelGGL((k_mlp_bwd_dw<64, 64>), grid, block, 0, st, a);
+    if (C == 32) hipLaunchKernelGGL((k_mlp_bwd_dw<32, 64>), grid, block, 0, st, a);          // <C, mlp_hidden_slice(C)>
     else hipLaunchKernelGGL((k_mlp_bwd_dw<64, 32>), grid, block, 0, st, a);
     return pk_launch_status("pk_ln_mlp_bwd_dw");
 }

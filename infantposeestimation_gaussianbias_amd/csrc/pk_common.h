@@ -6,17 +6,9 @@
 
 #include "../../include/posekernels.h"
 
-// Tuning knobs.  The RELEASE library reads nothing from the environment except the four documented routing switches of the two specialised
-// convolution kernels (PK_CONV8P, PK_CONV8P_MIN_TILES, PK_CONV3H, PK_CONV3H_MIN_TILES: the parity tests lower the thresholds to push small
-// and ragged shapes through them): every other knob of the measurement rounds is the compile-time constant it was left at.  A tuning build
-// (`make TUNING=1`, -DPK_TUNING) turns the knobs back into environment reads for A/B runs on one box.
-#ifdef PK_TUNING
-#include <stdlib.h>
-#define PK_KNOB(name, dflt) (getenv(name) ? atol(getenv(name)) : (long)(dflt))
-#else
-#define PK_KNOB(name, dflt) (dflt)
-#endif
-
+// The library reads nothing from the environment except the four documented routing switches of the two specialised convolution kernels
+// (PK_CONV8P, PK_CONV8P_MIN_TILES, PK_CONV3H, PK_CONV3H_MIN_TILES: the parity tests lower the thresholds to push small and ragged shapes
+// through them).  Every other threshold is a constant next to the routing code that uses it, with the measurement behind it.
 
 #define PK_WAVE 64
 
@@ -102,15 +94,11 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
 //   gelu'(x) = Phi(x) + x exp(-x^2/2) / sqrt(2 pi),   Phi = x >= 0 ? 1 - hw : hw
 // 1 v_rcp + 1 v_exp + 11 (gelu) / 14 (gelu') plain VALU ops.  (libm erff is ~60 instructions with a divergent branch; the first
 // version of this code used __frcp_rn, which hipcc expands to a correctly rounded division: 10 instructions instead of one.)
-// (-DPK_GELU_POLY=1 selects the rcp/exp-free polynomial form further down: measured in the captured training step, same box,
-// alternating runs: 17.30 / 17.25 ms with it, 17.39 / 17.02 ms without -- the fused MLP kernels wait on memory and on MFMA results
-// (profiles/r03_pmc_sq_counters.json: VALU active 25-42 % of the wave cycles), they do not queue on the VALU; and its 4e-5 absolute
-// error is visible to the whole-model golden test.  Kept for reference, off.)
-#ifndef PK_GELU_POLY
-#define PK_GELU_POLY 0
-#endif
+// (The rcp/exp-free polynomial form further down is not used here: put at every call site and measured in the captured training step,
+// same box, alternating runs: 17.30 / 17.25 ms with it, 17.39 / 17.02 ms without -- the fused MLP kernels wait on memory and on MFMA
+// results (profiles/r03_pmc_sq_counters.json: VALU active 25-42 % of the wave cycles), they do not queue on the VALU; and its 4e-5
+// absolute error is visible to the whole-model golden test.)
 typedef __attribute__((ext_vector_type(4))) float pk_f32x4;
-#if !PK_GELU_POLY
 struct GeluTerms { float hw, e; };
 __device__ __forceinline__ GeluTerms gelu_terms(float x) {
     const float ax = fabsf(x);
@@ -149,7 +137,6 @@ __device__ __forceinline__ void gelu_both(pk_f32x4 x, pk_f32x4& val, pk_f32x4& g
         grad[i] = b;
     }
 }
-#endif
 // The rcp and the exp of the form above are quarter-rate instructions (together as expensive as its eleven plain ones), and none of it maps
 // onto the packed fp32 pipe.  erf(x / sqrt 2) = xc P(xc^2), xc = clamp(x, -4.2, 4.2), P of degree 8 (minimax fit, scripts/fit_gelu_poly.py;
 // |error| <= 1.5e-5 inside the interval, 2.7e-5 = 1 - erf(4.2 / sqrt 2) beyond it; gelu: <= 4.4e-5 absolute, gelu': <= 1.1e-5 -- two
@@ -157,7 +144,7 @@ __device__ __forceinline__ void gelu_both(pk_f32x4 x, pk_f32x4& val, pk_f32x4& g
 // 4-wide form (an MFMA accumulator tile) every multiply / FMA is a v_pk_mul_f32 / v_pk_fma_f32 on two values: 7.5 issue slots per value
 // instead of 19.  Used where GELU is the measured bound: the forward-only wide MLP kernel (k_mlp_fwd_w: 70 M hidden elements per launch
 // at C = 80, 38 of its 83 us).  The training kernels keep the A&S form (measured there: no gain in the step, and their hidden is recomputed
-// in backward with the same function either way); -DPK_GELU_POLY=1 switches every call site over (A/B builds).
+// in backward with the same function either way).
 #define PK_GELU_CLAMP 4.2f
 #define PK_GELU_C0 0.79781485f
 #define PK_GELU_C1 -0.13272066f
@@ -204,38 +191,6 @@ __device__ __forceinline__ pk_f32x4 gelu_erf_poly(pk_f32x4 x) {
     const pk_f32x4 h = x * 0.5f;
     return __builtin_elementwise_fma(h, erf_rsqrt2(x), h);
 }
-#if PK_GELU_POLY
-__device__ __forceinline__ float gelu_erf(float x) { return gelu_erf_poly(x); }
-__device__ __forceinline__ pk_f32x4 gelu_erf(pk_f32x4 x) { return gelu_erf_poly(x); }
-// gelu'(x) = Phi(x) + x exp(-x^2 / 2) / sqrt(2 pi)
-__device__ __forceinline__ float gelu_grad(float x) {
-    const float e = __builtin_amdgcn_exp2f((x * x) * (-0.5f * 1.44269504088896340736f));
-    return __fmaf_rn(x * 0.39894228040143267794f, e, __fmaf_rn(0.5f, erf_rsqrt2(x), 0.5f));
-}
-__device__ __forceinline__ pk_f32x4 gelu_grad(pk_f32x4 x) {
-    const pk_f32x4 a = (x * x) * (-0.5f * 1.44269504088896340736f);
-    pk_f32x4 e;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) e[i] = __builtin_amdgcn_exp2f(a[i]);
-    const pk_f32x4 cdf = __builtin_elementwise_fma((pk_f32x4)(0.5f), erf_rsqrt2(x), (pk_f32x4)(0.5f));
-    return __builtin_elementwise_fma(x * 0.39894228040143267794f, e, cdf);
-}
-__device__ __forceinline__ void gelu_both(float x, float& val, float& grad) {
-    const float er = erf_rsqrt2(x), h = 0.5f * x;
-    const float e = __builtin_amdgcn_exp2f((x * x) * (-0.5f * 1.44269504088896340736f));
-    val = __fmaf_rn(h, er, h);
-    grad = __fmaf_rn(x * 0.39894228040143267794f, e, __fmaf_rn(0.5f, er, 0.5f));
-}
-__device__ __forceinline__ void gelu_both(pk_f32x4 x, pk_f32x4& val, pk_f32x4& grad) {
-    const pk_f32x4 er = erf_rsqrt2(x), h = x * 0.5f;
-    const pk_f32x4 a = (x * x) * (-0.5f * 1.44269504088896340736f);
-    pk_f32x4 e;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) e[i] = __builtin_amdgcn_exp2f(a[i]);
-    val = __builtin_elementwise_fma(h, er, h);
-    grad = __builtin_elementwise_fma(x * 0.39894228040143267794f, e, __builtin_elementwise_fma((pk_f32x4)(0.5f), er, (pk_f32x4)(0.5f)));
-}
-#endif
 __device__ __forceinline__ float softplus_(float v) { return v > 20.f ? v : log1pf(__expf(v)); }
 
 // Sum over the 16 lanes of a DPP row (lanes 16 k .. 16 k + 15), result in every lane of the row: two quad permutes and two row

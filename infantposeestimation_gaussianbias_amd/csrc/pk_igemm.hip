@@ -46,7 +46,7 @@ struct IgemmArgs {
     int rows_per_sample;      // rows of one sample (for res_scale): Ho*Wo or tokens per image
     int act;                  // 0 none, 1 GELU(erf), 2 softplus, 3 ReLU applied AFTER the residual add
     int out_mode;             // 0 bf16 row-major, 1 fp32 row-major, 2 fp32 NCHW planes [B][N][Ho*Wo]
-    int xcd_remap;            // set by igemm_launch (PK_IGEMM_XCD=0 disables the XCD-contiguous tile order)
+    int xcd_remap;            // set by igemm_launch: XCD-contiguous tile order
     int vec8;                 // set by igemm_launch: row-major pointers 16-byte aligned and ldo % 8 == 0 -> 16-byte epilogue I/O
     int chunk_major;          // set by igemm_launch: K order = all taps of one channel chunk back to back (N <= 32 tiles of deep 3x3 convs)
     int dil_group;            // set by igemm_launch (stride-2 data gradients): output pixels enumerated parity class by parity class
@@ -178,13 +178,16 @@ __device__ __forceinline__ void igemm_epilogue_row8(const IgemmArgs& p, f32x4 lo
     }
 }
 
-// LEAN = 1: the token GEMMs of the HRFormer blocks only (linear rows with optional gather / scatter maps, bias, residual with a per-sample
-// scale, bf16 output) -- the convolution addressing, the activations, the fp32 / NCHW outputs and the statistics are compiled out.  The
-// full kernel is 27-30 KB of code; a small launch (100-900 workgroups, 1-4 K-steps) spends much of its few microseconds fetching it cold.
+// Every instantiation is one of four specialisations (LEAN = 1 .. 4; there is no kernel with every run-time mode left in):
+//   1: the token GEMMs of the HRFormer blocks only (linear rows with optional gather / scatter maps, bias, residual with a per-sample
+//      scale, bf16 output) -- the convolution addressing, the activations, the fp32 / NCHW outputs and the statistics are compiled out.  The
+//      full kernel is 27-30 KB of code; a small launch (100-900 workgroups, 1-4 K-steps) spends much of its few microseconds fetching it cold.
+//   2: as 1, with the GELU epilogues kept;  3: every epilogue, plain addressing;  4: every epilogue, dilated gather (see the first lines).
 // The kernel body takes its tile coordinates and grid shape as arguments: k_igemm2 passes blockIdx / gridDim, the GROUPED launch
 // k_igemm2g (below) cuts one 1-D grid into the tile grids of several independent problems.
-template <int BM, int BN, int WM, int WN, int BK, int LEAN = 0>
+template <int BM, int BN, int WM, int WN, int BK, int LEAN>
 __device__ __forceinline__ void igemm2_body(const IgemmArgs& p_in, const int bid_x, const int bid_y, const int grid_x, const int grid_y) {
+    static_assert(LEAN >= 1 && LEAN <= 4, "igemm2_body: LEAN is 1, 2, 3 or 4");
     IgemmArgs p = p_in;
     if (LEAN == 3) {
         // every feature of the epilogue, but the PLAIN addressing in the K loop: no dilated gather (stride-2 data gradients), no parity
@@ -194,7 +197,7 @@ __device__ __forceinline__ void igemm2_body(const IgemmArgs& p_in, const int bid
         p.dilated = 0; p.dil_group = 0;       // (chunk-major stays a run-time flag of the 128 x 32 tiles: with the mask form a tap change per step is cheap)
     } else if (LEAN == 4) {          // the stride-2 data gradients (dilated gather, grouped or not): no chunk-major order
         p.dilated = 1; p.chunk_major = 0;
-    } else if (LEAN) {               // LEAN = 2 keeps the GELU epilogues (fc1: GELU + saved pre-activation; fc2 data gradient: x gelu'(z))
+    } else {                         // LEAN = 2 keeps the GELU epilogues (fc1: GELU + saved pre-activation; fc2 data gradient: x gelu'(z))
         p.stats = nullptr;
         p.out_mode = 0; p.T = 1; p.Ho = 0; p.Wo = 0; p.dilated = 0; p.vec8 = 1; p.chunk_major = 0; p.dil_group = 0;
         p.col_scale = nullptr;
@@ -683,7 +686,7 @@ __device__ __forceinline__ void igemm2_body(const IgemmArgs& p_in, const int bid
     }
 }
 
-template <int BM, int BN, int WM, int WN, int BK, int LEAN = 0>
+template <int BM, int BN, int WM, int WN, int BK, int LEAN>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) k_igemm2(IgemmArgs p_in) {
     igemm2_body<BM, BN, WM, WN, BK, LEAN>(p_in, (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.x, (int)gridDim.y);
 }
@@ -1296,73 +1299,40 @@ static inline bool conv8p_takes(const IgemmArgs& a) {
            a.ldo == a.N && (((uintptr_t)a.out) & 15) == 0 && (long)((a.M + 255) / 256) * (a.N / 256) >= min_tiles && a.Hs == a.Ho && a.Ws == a.Wo;
 }
 
-// PK_IGEMM_LOG=1: the launch shapes of a run, counted on the host and printed at exit (profiling aid)
-#include <map>
-#include <string>
-static std::map<std::string, int>& igemm_log() {
-    static std::map<std::string, int>* m = new std::map<std::string, int>();      // leaked on purpose: read by an atexit handler
-    return *m;
-}
-static void igemm_log_dump() {
-    for (auto& kv : igemm_log()) fprintf(stderr, "# igemm %6d x %s\n", kv.second, kv.first.c_str());
-}
-static void igemm_log_add(const IgemmArgs& a) {
-    static const bool on = PK_KNOB("PK_IGEMM_LOG", 0) != 0;
-    if (!on) return;
-    static bool reg = false;
-    if (!reg) {
-        reg = true;
-        atexit(igemm_log_dump);
-    }
-    char buf[200];
-    snprintf(buf, sizeof buf, "M=%-7d N=%-4d Cin=%-4d T=%d s=%d dil=%d conv=%d amap=%d omap=%d res=%d stats=%d act=%d gelu_of=%d out_mode=%d", a.M, a.N, a.Cin, a.T,
-             a.stride, a.dilated, a.Ho > 0, a.a_rowmap != nullptr, a.o_rowmap != nullptr, a.res != nullptr, a.stats != nullptr, a.act,
-             a.gelu_of != nullptr, a.out_mode);
-    igemm_log()[buf]++;
-}
-// plain launches (no dilated gather, no chunk-major order) take the LEAN = 3 instantiation of the same tile: see the kernel's first lines
+// plain launches (no dilated gather) take the LEAN = 3 instantiation of a tile, the stride-2 data gradients LEAN = 4: see the kernel's first lines
 #define IGEMM_GO(BM_, BN_, WM_, WN_, BK_, GRID)                                                                      \
     do {                                                                                                             \
-        if (plain) hipLaunchKernelGGL((k_igemm2<BM_, BN_, WM_, WN_, BK_, 3>), GRID, block, 0, st, a);                \
-        else if (plain_on && a.dilated && !a.chunk_major) hipLaunchKernelGGL((k_igemm2<BM_, BN_, WM_, WN_, BK_, 4>), GRID, block, 0, st, a);       \
-        else hipLaunchKernelGGL((k_igemm2<BM_, BN_, WM_, WN_, BK_>), GRID, block, 0, st, a);                         \
+        if (!a.dilated) hipLaunchKernelGGL((k_igemm2<BM_, BN_, WM_, WN_, BK_, 3>), GRID, block, 0, st, a);           \
+        else hipLaunchKernelGGL((k_igemm2<BM_, BN_, WM_, WN_, BK_, 4>), GRID, block, 0, st, a);                      \
     } while (0)
 static int igemm_launch(const IgemmArgs& a_in, hipStream_t st, const char* who) {
     IgemmArgs a = a_in;
-    igemm_log_add(a);
     a.vec8 = (a.ldo % 8) == 0 &&
              ((((uintptr_t)a.out | (uintptr_t)a.res | (uintptr_t)a.preact | (uintptr_t)a.gelu_of) & 15) == 0);
-    static const int xcd_on = PK_KNOB("PK_IGEMM_XCD", 1);
-    a.xcd_remap = xcd_on;
-    static const int cm_on = PK_KNOB("PK_IGEMM_CHUNK_MAJOR", 1);
-    a.chunk_major = cm_on && a.T == 9 && a.N <= 32 && a.Cin >= 128 && (a.Cin % 64) == 0 && !a.dilated;      // (the dilated walk has its own tap list)
-    static const int dg_on = PK_KNOB("PK_IGEMM_DILGROUP", 1);
-    a.dil_group = dg_on && a.dilated && a.T == 9 && a.out_mode == 0 && !a.stats && !a.o_rowmap && !a.res_scale;
+    a.xcd_remap = 1;
+    a.chunk_major = a.T == 9 && a.N <= 32 && a.Cin >= 128 && (a.Cin % 64) == 0 && !a.dilated;      // (the dilated walk has its own tap list)
+    a.dil_group = a.dilated && a.T == 9 && a.out_mode == 0 && !a.stats && !a.o_rowmap && !a.res_scale;
     if (conv3h_takes(a)) return conv3h_launch(a, st, who);
     if (conv8p_takes(a)) {
         hipLaunchKernelGGL(k_conv8p, dim3((unsigned)(((a.M + 255) / 256) * (a.N / 256))), dim3(512), 0, st, a);
         return pk_launch_status(who);
     }
     const dim3 block(256);
-    static const int plain_on = PK_KNOB("PK_IGEMM_PLAIN", 1);
-    const bool plain = plain_on && !a.dilated;
     const unsigned gm = (unsigned)((a.M + 127) / 128);
     // Deep contractions with wide outputs (the 3x3 convs of the head: K = 2304, N = 128/256): 256 x 128 workgroup tile, 128 x 64
     // per wave -- a third less LDS traffic per MFMA than the 64 x 64 wave tile, which is what bounds those kernels.
-    static const int big_on = PK_KNOB("PK_IGEMM_BIG", 1);
     // (needs >= 1024 workgroups: with 768 -- N = 128 at M = 196 608 -- the second round of workgroups is half empty and the
     // kernel is slower than the 128 x 128 tile.  Measured at N = 256: fwd 361 -> 334 us, dgrad 306 -> 285 us.)
-    if (big_on && (a.N % 128) == 0 && a.T * a.Cin >= 576 && (a.Cin % 32) == 0 && (long)((a.M + 255) / 256) * (a.N / 128) >= 1024) {
+    if ((a.N % 128) == 0 && a.T * a.Cin >= 576 && (a.Cin % 32) == 0 && (long)((a.M + 255) / 256) * (a.N / 128) >= 1024) {
         IGEMM_GO(256, 128, 2, 2, 32, dim3((a.M + 255) / 256, a.N / 128));
         return pk_launch_status(who);
     }
     // deeper K-chunks when the channel count allows full 64-wide tiles -- except for contractions of <= 128 (one or two steps): the BK = 32
     // variants hold half the LDS and run 4-7 waves per SIMD instead of 3, which is what an output-bound launch needs (1x1 64 -> 256 @64x48
     // data gradient 48.5 -> 37 us)
-    static const int shallow32 = PK_KNOB("PK_IGEMM_SHALLOW32", 128);
+    constexpr int shallow32 = 128;
     const bool k64 = (a.Cin % 64) == 0 && !(a.T * a.Cin <= shallow32);
-    static const int lean_on = PK_KNOB("PK_IGEMM_LEAN", 1);
-    const bool lean_any = lean_on && a.T == 1 && a.Ho == 0 && !a.stats && a.act <= 1 && a.out_mode == 0 && a.vec8 && k64 && (a.N % 8) == 0;
+    const bool lean_any = a.T == 1 && a.Ho == 0 && !a.stats && a.act <= 1 && a.out_mode == 0 && a.vec8 && k64 && (a.N % 8) == 0;
     const bool lean = lean_any && !a.preact && !a.gelu_of && a.act == 0, lean_g = lean_any && !lean;
     // Shallow contractions (K = T*Cin <= 256: the token-MLP / qkv GEMMs) are bound by their output traffic, not MFMA:
     // 128x64 tiles need half the accumulators (4 waves/SIMD instead of 2) and hide the epilogue's memory latency better
@@ -1370,8 +1340,7 @@ static int igemm_launch(const IgemmArgs& a_in, hipStream_t st, const char* who) 
     // Few pixel rows (low-resolution branches: 24 .. 96 row tiles): a 128-wide N tile leaves most of the 256 CUs idle, so take
     // the widest N tile that still gives >= 512 workgroups (they are latency-bound, not MFMA-bound, at that size).
     // (128 x 64 tiles for the large convs were measured too: head conv 421 us instead of 361 us.)
-    static const int smallm_on = PK_KNOB("PK_IGEMM_SMALLM", 1);
-    const bool small_m = smallm_on && a.N > 64 && (long)gm * ((a.N + 127) / 128) < 512;
+    const bool small_m = a.N > 64 && (long)gm * ((a.N + 127) / 128) < 512;
     if (small_m && (long)gm * ((a.N + 63) / 64) < 512 && !a.stats) {
         if (lean) hipLaunchKernelGGL((k_igemm2<128, 32, 4, 1, 64, 1>), dim3(gm, (a.N + 31) / 32), block, 0, st, a);
         else if (lean_g) hipLaunchKernelGGL((k_igemm2<128, 32, 4, 1, 64, 2>), dim3(gm, (a.N + 31) / 32), block, 0, st, a);
@@ -1912,8 +1881,7 @@ __global__ void __launch_bounds__(512, 2) k_wgrad3(WgradArgs p) {
         }
 }
 static inline bool wgrad_wide(int N, int Cin, int T) {
-    static const int on = PK_KNOB("PK_WGRAD_WIDE", 1);
-    return on && T == 9 && (N % 256) == 0 && (Cin % 256) == 0;
+    return T == 9 && (N % 256) == 0 && (Cin % 256) == 0;
 }
 
 // ------------------------------------------------------------------------------------------------ streaming weight-gradient kernels
@@ -2491,15 +2459,15 @@ __global__ void __launch_bounds__(256, 2) k_wgrad4_3x3(WgradArgs p) {
 }
 // which weight gradients the streaming kernels take: flags bit 0 = a_rowmap, 1 = g_rowmap, 2 = g_scale
 static inline int wgrad4_kind(int N, int Cin, int ksize, int stride, int Hs, int Ws, int flags) {
-    static const int on = PK_KNOB("PK_WGRAD4", 15);     // bit 0: single tap, 1: nine-tap 3x3, 2: column-form 3x3, 3: window / scaled rows
+    // 1: single tap, 2: nine-tap 3x3, 3: column-form 3x3, 4: window-gathered / scaled rows, 0: not theirs (k_wgrad2 / k_wgrad3)
     if (flags) {       // gathered / scaled rows: linear form; a row map needs the token grid it is the window partition of
         if (ksize != 1 || stride != 1 || ((flags & 3) && (Hs <= 0 || Ws <= 0))) return 0;
-        return (on & 8) ? 4 : 0;
+        return 4;
     }
-    if (ksize == 1 && stride == 1) return (on & 1) ? 1 : 0;
+    if (ksize == 1 && stride == 1) return 1;
     if (ksize == 3 && wgrad_wide(N, Cin, 9)) return 0;
-    if (ksize == 3 && stride == 1 && Ws >= 1 && Ws <= 48) return (on & 2) ? 2 : 0;
-    if (ksize == 3) return (on & 4) ? 3 : 0;
+    if (ksize == 3 && stride == 1 && Ws >= 1 && Ws <= 48) return 2;
+    if (ksize == 3) return 3;
     return 0;
 }
 
@@ -2623,14 +2591,14 @@ static inline void wgrad_tile2(int N, int Cin, int T, int& tn, int& tc) {
 }
 static int wgrad_slices_old(int M, int N, int Cin, int T) {
     // enough workgroups to fill 256 CUs several times over (>= 2048), but no slice shorter than 256 rows
-    static const int target = PK_KNOB("PK_WGRAD_WGS", 2048);
+    constexpr int target = 2048;
     // (shorter slices for the low-resolution branches were measured: 64-row slices cost +1.3 ms per step in slab traffic; longer ones
     // are slower as well -- 512 / 1 024 rows: +0.35 / +1.8 ms per step -- each k_wgrad2 workgroup is bound by its own load latency)
-    static const int min_rows = PK_KNOB("PK_WGRAD_ROWS", 256);
+    constexpr int min_rows = 256;
     if (wgrad_wide(N, Cin, T)) {
         // one 512-thread workgroup per CU (128 KB LDS ring): ~one round of equal-sized workgroups over the 256 CUs, in whole groups of
         // 8 slices (one slice per XCD and group)
-        static const int wide_target = PK_KNOB("PK_WGRAD_WIDE_WGS", 256);
+        constexpr int wide_target = 256;
         const int tiles3 = (N / 256) * (Cin / 256) * T;
         int s3 = wide_target / tiles3 / 8 * 8;
         if (s3 < 8) s3 = 8;
@@ -2658,16 +2626,12 @@ static int wgrad4_slices(int rows, int N, int Cin, int kind) {
     // two workgroups per CU (single tap) / one (3x3: nine accumulator sets), slices of >= 512 rows: against 256 the step is unchanged
     // (17.3 / 17.6 ms on two boxes either way) and the slabs of the low-resolution branches halve (k_reduce_many 653 -> 570 us isolated);
     // 1 024 rows starve the small launches of workgroups (step + 0.6 ms)
-    static const int t1 = PK_KNOB("PK_WGRAD4_WGS", 512);
-    static const int t9 = PK_KNOB("PK_WGRAD4_WGS9", 256);
-    static const int min_rows = PK_KNOB("PK_WGRAD4_ROWS", 512);
+    constexpr int t1 = 512, t9 = 256, min_rows = 512;
     int tn, tc;
     wgrad4_tile(N, Cin, kind, tn, tc);
     const int tiles = ((N + tn - 1) / tn) * (((kind == 3 ? 9 * Cin : Cin) + tc - 1) / tc);
     int s = ((kind == 2 ? t9 : t1) + tiles - 1) / tiles;
-    static const int min_rows_w = PK_KNOB("PK_WGRAD4W_ROWS", min_rows);      // kind 4: window-gathered / row-scaled
-    const int mr = kind == 4 ? min_rows_w : min_rows;
-    const int max_s = (rows + mr - 1) / mr;
+    const int max_s = (rows + min_rows - 1) / min_rows;
     if (s > max_s) s = max_s;
     return s < 1 ? 1 : s;
 }
@@ -2771,9 +2735,8 @@ extern "C" int pk_wgrad_bf16(const void* x, const void* grad_out, float* workspa
         a.m_per_slice = ((rows + S - 1) / S + 31) / 32 * 32;
         const dim3 grid(8 * ((S + 7) / 8) * a.ntiles3);
         if (kind4 == 4) {
-            static const int w4_modes = PK_KNOB("PK_WGRAD4W_MODES", 1);
             const bool gw_ = a.g_rowmap != nullptr, xw_ = a.a_rowmap != nullptr, sc_ = a.g_scale != nullptr;
-            const int mode = !w4_modes ? 0 : (xw_ && !gw_ && !sc_) ? 1 : (gw_ && sc_ && !xw_) ? 2 : (sc_ && !gw_ && !xw_) ? 3 : 0;
+            const int mode = (xw_ && !gw_ && !sc_) ? 1 : (gw_ && sc_ && !xw_) ? 2 : (sc_ && !gw_ && !xw_) ? 3 : 0;
 #define W4W_GO(TN_, TC_)                                                                                     \
     do {                                                                                                     \
         if (mode == 1) hipLaunchKernelGGL((k_wgrad4w<TN_, TC_, 1>), grid, dim3(256), 0, st, a);              \
@@ -2808,8 +2771,7 @@ extern "C" int pk_wgrad_bf16(const void* x, const void* grad_out, float* workspa
         hipLaunchKernelGGL(k_wgrad3, dim3(8 * ((S + 7) / 8) * 9 * a.ntiles3), dim3(512), W3_LDS, st, a);
     } else {
         dim3 grid(((N + tn - 1) / tn) * a.ctiles, a.T, S);
-        static const int xcd9 = PK_KNOB("PK_WGRAD2_XCD", 1);
-        if (a.T == 9 && xcd9) {
+        if (a.T == 9) {
             a.ntiles3 = grid.x;
             a.nslices3 = S;
             grid = dim3(8 * ((S + 7) / 8) * 9 * a.ntiles3);

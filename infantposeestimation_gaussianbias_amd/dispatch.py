@@ -170,7 +170,7 @@ def join_detached():
 # 17.16 vs 17.21 ms over four alternating runs each -- inside the noise, not kept.  Round 4, only the slab launches of the LOW-resolution
 # branches (i >= 2: latency-bound chains, the longest branches of HRNet-W32's regions when run alone), one shared or one auxiliary
 # stream per branch, operands held until the region joins: cfg 4 20.28 -> 24.17 / 23.96 ms, cfg 2 16.15 -> 18.3 ms
-# (scripts/gpu_r04_n.sh) -- every launch moved aside costs two cross-queue event edges in the captured graph, more than it hides.)
+# -- every launch moved aside costs two cross-queue event edges in the captured graph, more than it hides.)
 
 
 def _tensors(obj):

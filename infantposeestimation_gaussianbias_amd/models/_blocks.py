@@ -92,20 +92,6 @@ def transition_branch(tr, i, t, n_prev, training):
     return t
 
 
-def run_transition(tr, ys, n_cur, training):
-    outs = []
-    for i in range(n_cur):
-        key = str(i)
-        if i < len(ys):
-            outs.append(nnops.conv_bn_act(ys[i], tr[key][0], tr[key][1], True, None, training) if key in tr else ys[i])
-        else:
-            t = ys[-1]
-            for cv, bn in tr[key]:
-                t = nnops.conv_bn_act(t, cv, bn, True, None, training)
-            outs.append(t)
-    return outs
-
-
 def init_backbone_weights(module):
     """hrformer.py:709-720 / hrnet.py:386-393: conv kaiming-normal(fan_out, relu); norm 1/0; linear trunc-normal .02."""
     for m in module.modules():

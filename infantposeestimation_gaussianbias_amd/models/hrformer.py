@@ -7,13 +7,11 @@ exchange unit after every module; only output 0 of the last module is returned (
 """
 from typing import Sequence
 
-import os
-
 import torch
 import torch.nn as nn
 
 from .. import dispatch as nnops
-from ._blocks import Residual, conv, init_backbone_weights, make_fuse_layers, make_transition, run_transition, transition_branch
+from ._blocks import Residual, conv, init_backbone_weights, make_fuse_layers, make_transition, transition_branch
 
 
 def drop_path(x: torch.Tensor, drop_prob: float = 0., training: bool = False) -> torch.Tensor:
@@ -120,9 +118,6 @@ class HRFormerBlock(nn.Module):
             return nnops.to_public(nnops.window_block(t, self, self.heads, s1, s2))
 
 
-_CHAIN = os.environ.get("POSE_CHAIN_MODULES", "1") != "0"
-
-
 class HRFormerModule(nn.Module):
     def __init__(self, channels, heads, blocks_per_branch, mlp_ratios, drop_path, with_rpe=True):
         super().__init__()
@@ -223,13 +218,11 @@ class HRFormer(nn.Module):
             scales = nnops.drop_scales(sum(m.n_draws() for m in mods), x.shape[0], self.drop_path_rate, x.device)
         d = 0
         for s in (2, 3, 4):
-            trans = getattr(self, f"transition{s - 1}") if _CHAIN else None
-            if not _CHAIN:
-                ys = run_transition(getattr(self, f"transition{s - 1}"), ys, s, tr)
+            trans = getattr(self, f"transition{s - 1}")
             mods_s, pre = list(getattr(self, f"stage{s}")), None
             for k, m in enumerate(mods_s):
                 n = m.n_draws()
-                chain = _CHAIN and k + 1 < len(mods_s)          # the exchange unit of this module runs inside the next module's tasks
+                chain = k + 1 < len(mods_s)          # the exchange unit of this module runs inside the next module's tasks
                 ys = m(ys, None if scales is None else scales[d:d + n], pre=pre, defer=chain, trans=trans if k == 0 else None,
                        first_only=(s == 4 and k + 1 == len(mods_s)))
                 pre = m.fuse_layers if chain else None

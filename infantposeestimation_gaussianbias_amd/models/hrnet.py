@@ -3,13 +3,12 @@
 Stem -> 4 bottlenecks -> stage2 (1 module) -> stage3 (4 modules) -> stage4 (3 modules), 4 BasicBlocks per branch per
 module, exchange unit after each module (hrnet.py:243-302); returns branch 0 only (hrnet.py:441).
 """
-import os
 
 import torch
 import torch.nn as nn
 
 from .. import dispatch as nnops
-from ._blocks import Residual, conv, init_backbone_weights, make_fuse_layers, make_transition, run_transition, transition_branch
+from ._blocks import Residual, conv, init_backbone_weights, make_fuse_layers, make_transition, transition_branch
 
 
 class HighResolutionModule(nn.Module):
@@ -38,9 +37,6 @@ class HighResolutionModule(nn.Module):
         ys = nnops.parallel([make(b, blocks) for b, blocks in enumerate(self.branches)],
                             [(list(xs) if pre is not None else [xs[min(b, n_prev - 1)]]) for b in range(len(self.branches))])
         return ys if (len(ys) == 1 or defer) else nnops.exchange(ys, self.fuse_layers, self.training, first_only=first_only)
-
-
-_CHAIN = os.environ.get("POSE_CHAIN_MODULES", "1") != "0"
 
 
 class HRNet(nn.Module):
@@ -78,12 +74,10 @@ class HRNet(nn.Module):
             x = blk(x)
         ys = [x]
         for s in (2, 3, 4):
-            trans = getattr(self, f"transition{s - 1}") if _CHAIN else None
-            if not _CHAIN:
-                ys = run_transition(getattr(self, f"transition{s - 1}"), ys, s, tr)
+            trans = getattr(self, f"transition{s - 1}")
             mods_s, pre = list(getattr(self, f"stage{s}")), None
             for k, m in enumerate(mods_s):
-                chain = _CHAIN and k + 1 < len(mods_s)
+                chain = k + 1 < len(mods_s)
                 ys = m(ys, pre=pre, defer=chain, trans=trans if k == 0 else None, first_only=(s == 4 and k + 1 == len(mods_s)))
                 pre = m.fuse_layers if chain else None
             # N > 1: once backward has passed this boundary the later stages' gradients are exchanged while the earlier stages still

@@ -314,19 +314,6 @@ def to_features(x_nchw_f32, cpad=8):
     return y
 
 
-_WGRAD_LOG = None
-if os.environ.get("POSE_LOG_WGRAD") == "1":          # profiling: the weight-gradient launch shapes of a run, printed at exit
-    import atexit
-    import collections
-    _WGRAD_LOG = collections.Counter()
-
-    def _dump_wgrad_log():
-        print("# weight-gradient launches: count x (M, N, Cin, ksize, stride, a_map, g_map, g_scale, n_bias, slices, deferred)")
-        for k, v in sorted(_WGRAD_LOG.items(), key=lambda kv: -kv[1] * kv[0][0] * (kv[0][1] + kv[0][2])):
-            print(f"# {v:4d} x {k}  slab MB {k[9] * k[1] * (k[3] ** 2 * k[2] + 1) * 4 / 1e6:.1f}")
-    atexit.register(_dump_wgrad_log)
-
-
 def _conv_geometry(x, ksize, stride):
     B, Hs, Ws, Cin = x.shape
     pad = ksize // 2
@@ -373,8 +360,6 @@ def _wgrad(x, g, N, Cin, ksize, stride, geom, a_map=None, g_map=None, g_scale=No
     S = _lib.lib.pk_wgrad_slices(M, N, Cin, ksize, stride, Hs, Ws, flags)
     layout = 1 if (geom is not None and oihw) else 0
     n_bias = 0 if dbias is None else dbias.numel()
-    if _WGRAD_LOG is not None:
-        _WGRAD_LOG[(M, N, Cin, ksize, stride, a_map is not None, g_map is not None, g_scale is not None, n_bias, S, bool(deferred))] += 1
     if deferred and out is not None and deferral_enabled():
         # slabs into a persistent workspace, reduction postponed to finalize_deferred()
         ws = _workspace(out, "w", S * N * (T * Cin + 1))
@@ -513,7 +498,7 @@ def conv_bn_act(x, conv, bn, relu=False, residual=None, training=False, skip_out
 def residual_block(x, first, middle, last, training):
     """relu(bn(conv_last(...relu(bn(conv_first(x)))...)) + x) with an IDENTITY skip; first / last = (conv, bn), middle = list of (conv, bn).
     In training the skip gradient bypasses autograd (SkipGrad); otherwise this is the plain chain."""
-    fuse = training and torch.is_grad_enabled() and x.requires_grad and first[0].stride[0] == 1 and os.environ.get("POSE_SKIP_GRAD", "1") != "0"
+    fuse = training and torch.is_grad_enabled() and x.requires_grad and first[0].stride[0] == 1
     hold = SkipGrad() if fuse else None
     y = conv_bn_act(x, first[0], first[1], True, None, training, skip_in=hold)
     for conv, bn in middle:
@@ -865,11 +850,6 @@ class _MlpHalf(torch.autograd.Function):
                 None if s_b2 else db2, None, None)
 
 
-def _fused_widths(var, default):
-    import os
-    return tuple(int(v) for v in os.environ.get(var, default).split(",") if v.strip())
-
-
 class _WindowAttnOnly(torch.autograd.Function):
     """proj(window_attention(qkv(tokens))) on window-ordered tokens (B_*49, C): the reference's WindowAttention.forward by itself
     (hrformer.py:174-200), without the block's LayerNorm / window partition / residual."""
@@ -963,8 +943,8 @@ def mlp_rows(x2d, mlp):
 
 
 def fused_mlp_enabled(C, c_real=0):
-    """POSE_FUSED_MLP = comma-separated channel counts that take the fused MLP half (default: all the kernels are built for)."""
-    return c_real in (0, C) and C in _fused_widths("POSE_FUSED_MLP", "32,64") and bool(_lib.lib.pk_ln_mlp_supported(C))
+    """The channel counts that take the fused MLP half: all the kernels are built for."""
+    return c_real in (0, C) and C in (32, 64) and bool(_lib.lib.pk_ln_mlp_supported(C))
 
 
 class _MlpHalfFused(torch.autograd.Function):
@@ -1030,9 +1010,9 @@ class _MlpHalfFused(torch.autograd.Function):
 
 def wide_mlp_enabled(C, hidden, M=0):
     """Forward-only fused MLP half for the wide branches (C = 80 ... 320, weights streamed through LDS): pk_ln_mlp_wide_fwd.  With the
-    token count M the library also says whether the launch would pay (enough workgroups).  POSE_FUSED_MLP_WIDE=0 switches it off
-    (the unfused LayerNorm / fc1+GELU / fc2 sequence runs instead)."""
-    return os.environ.get("POSE_FUSED_MLP_WIDE", "1") != "0" and bool(_lib.lib.pk_ln_mlp_wide_supported(C, hidden, 0 if _wide_forced() else M))
+    token count M the library also says whether the launch would pay (enough workgroups); where it says no,
+    the unfused LayerNorm / fc1+GELU / fc2 sequence runs instead."""
+    return bool(_lib.lib.pk_ln_mlp_wide_supported(C, hidden, 0 if _wide_forced() else M))
 
 
 def _wide_forced():
@@ -1041,9 +1021,8 @@ def _wide_forced():
 
 
 def wide_attn_enabled(C, heads, n_windows=0):
-    """Forward-only fused attention half of the head_dim-40 twins (pk_attn_block_wide_fwd); POSE_FUSED_ATTN_WIDE=0 switches it off."""
-    return os.environ.get("POSE_FUSED_ATTN_WIDE", "1") != "0" and bool(
-        _lib.lib.pk_attn_block_wide_supported(C, heads, 0 if _wide_forced() else n_windows))
+    """Forward-only fused attention half of the head_dim-40 twins (pk_attn_block_wide_fwd)."""
+    return bool(_lib.lib.pk_attn_block_wide_supported(C, heads, 0 if _wide_forced() else n_windows))
 
 
 def attn_half_wide_forward(x, g1, b1, table, wqkv, bqkv, wproj, bproj, scale1, heads, c_real=0, attn_scale=0.0):
@@ -1073,11 +1052,11 @@ def mlp_half_wide_forward(x, g2, b2, w1, bias1, w2, bias2, scale2, c_real=0):
 
 
 def fused_attn_enabled(C, heads, c_real=0, attn_scale=0.0, train=True):
-    """POSE_FUSED_ATTN (training) / POSE_FUSED_ATTN_EVAL (forward only) = channel counts that take the fused attention half."""
+    """The channel counts that take the fused attention half, in training and forward only."""
     ok = c_real in (0, C) and not attn_scale and bool(_lib.lib.pk_attn_block_supported(C, heads))
     # Measured in the captured training step (B = 64): the fused backward pays at C = 32 (3 076 img/s vs 3 003 with C = 64 fused as
     # well: its 2-head backward holds one wave per SIMD and 133 KB of LDS); forward-only use takes both widths.
-    return ok and C in _fused_widths("POSE_FUSED_ATTN" if train else "POSE_FUSED_ATTN_EVAL", "32" if train else "32,64")
+    return ok and C in ((32,) if train else (32, 64))
 
 
 def attn_half_fused_forward(x, g1, b1, table, wqkv, bqkv, wproj, bproj, scale1, heads, save=False):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""print ms_per_step / value / launches of bench.py JSON lines given as files (helper of the scripts/gpu_*.sh A/B loops)"""
+"""print ms_per_step / value / launches of bench.py JSON lines given as files (helper of A/B runs)"""
 import json
 import sys
 for f in sys.argv[1:]:

@@ -33,7 +33,7 @@ k = dict(stp["kernels"])
 k.update(iso["kernels"])           # the isolated pass wins for the kernels it covers (one shape per kernel name)
 json.dump({"note": iso["note"], "sources": "isolated probes (scripts/prof_kernels.py isolated) over a whole eager step (… step)", "kernels": k},
           open("gpurun_out/r04_pmc_traffic.json", "w"), indent=1)
-for n in ("k_conv8p", "k_wgrad3", "k_conv3h<64, 64>", "k_igemm2<128, 32, 4, 1, 64, 0>", "k_reduce_many", "k_attn_bwd<32>", "k_mlp_fwd<32>"):
+for n in ("k_conv8p", "k_wgrad3", "k_conv3h<64, 64>", "k_igemm2<128, 32, 4, 1, 64, 3>", "k_reduce_many", "k_attn_bwd<32>", "k_mlp_fwd<32>"):
     print(n, k.get(n))
 PY
 sed "s/r03_pmc_sq_counters/r04_pmc_sq_counters/g" scripts/gpu_pmc_sq.sh > gpurun_out/_sq.sh; bash gpurun_out/_sq.sh > gpurun_out/r04_sq.log 2>&1 || tail -3 gpurun_out/r04_sq.log
