@@ -422,6 +422,25 @@ int pk_pack_weights(void* flat_dst_bf16, const void* desc_table, const int32_t* 
 int pk_embed_boxes(float* twin_base, const void* desc_table, const int* block_desc, const int* block_first, int n_blocks,
                    int direction, void* stream);
 
+/* Pose overlays (utils/visualization.py), drawn in place on a uint8 batch images (N,H,W,3), H, W <= 8192.
+ * pk_draw_shapes: boxes (Q,4) fp32 x1 y1 x2 y2 with box_image_index (Q,), one colour (channel order of the image) and thickness; then
+ *   poses (P,K,2) fp32 image pixels, scores (P,K), image_index (P,); both index tables non-decreasing.  limbs (L,2) int32 (a limb naming
+ *   a joint outside 0..K-1 is skipped), colors (C,3) uint8 (joint k and limbs starting at k take colors[k % C]).  Coverage is decided
+ *   in integers on 16 samples per pixel in units of 1/8 px (rule: DESIGN.md "Drawing on the device"); per image boxes first, then per
+ *   pose limbs in table order and joints in index order (disc, white ring), drawn iff score >= score_threshold and everything finite.
+ *   point_radius 0..64, line_thickness / box_thickness 1..64.  No atomics: identical bits on every run.
+ * pk_heatmap_overlay: heatmaps (N,K,h,w) fp32 -> max over K, bilinear resize to (H,W) (half-pixel rule), per-image min/max of the
+ *   resized plane, idx = floor(255 (m - min) / (max - min + 1e-8)), out = (img (256 - a) + lut[idx] a + 128) >> 8 with
+ *   a = clamp(rint(256 alpha), 0, 256).  lut: (256,3) uint8; index_u8 (optional): (N,H,W) uint8 receives idx;
+ *   ws: pk_heatmap_overlay_ws_floats(...) floats.                                                                                    */
+int pk_draw_shapes(void* images_u8, int N, int H, int W, const float* poses, const float* scores, const int32_t* image_index, int P,
+                   int K, const int32_t* limbs, int L, const void* colors_u8, int C, const float* boxes,
+                   const int32_t* box_image_index, int Q, int box_c0, int box_c1, int box_c2, int box_thickness,
+                   float score_threshold, int point_radius, int line_thickness, void* stream);
+int pk_heatmap_overlay_ws_floats(int N, int K, int h, int w, int H, int W);
+int pk_heatmap_overlay(void* images_u8, const float* heatmaps, float alpha, const void* lut_u8, void* index_u8, float* ws, int N,
+                       int K, int h, int w, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

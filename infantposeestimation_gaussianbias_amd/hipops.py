@@ -436,6 +436,73 @@ def nms_pose(preds, maxvals, distance_threshold=5.0):
     return out, keep.bool().view(B, K, 1)
 
 
+# ------------------------------------------------------------------------------------------------ overlays
+U8 = torch.uint8
+
+
+def _chk_images(images):
+    """(N,H,W,3) uint8 device batch that the drawing kernels change IN PLACE (so no .contiguous() copy: it must be contiguous already)."""
+    images = _chk(images, U8, "images")
+    if images.dim() != 4 or images.shape[-1] != 3:
+        raise _lib.PoseKernelError(f"images: expected (N, H, W, 3), got {tuple(images.shape)}")
+    return images
+
+
+def draw_shapes(images, poses=None, scores=None, image_index=None, limbs=None, colors=None, boxes=None, box_image_index=None,
+                box_color=(0, 255, 0), box_thickness=2, score_threshold=0.3, point_radius=4, line_thickness=2):
+    """Skeletons and boxes rasterised IN PLACE on a contiguous (N,H,W,3) uint8 batch, one launch (pk_draw_shapes).  poses (P,K,2) image
+    pixels, scores (P,K), image_index (P,) int32 non-decreasing, limbs (L,2) int32, colors (C,3) uint8 in the image's channel order;
+    boxes (Q,4) x1 y1 x2 y2 with box_image_index (Q,) int32 non-decreasing.  Returns `images`."""
+    if not (isinstance(images, torch.Tensor) and images.is_contiguous()):
+        raise _lib.PoseKernelError("images: expected a contiguous CUDA(HIP) uint8 tensor (drawn in place)")
+    images = _chk_images(images)
+    N, H, W, _ = images.shape
+    P = K = L = C = Q = 0
+    if poses is not None:
+        poses, image_index = _chk(poses, name="poses"), _chk(image_index, I32, "image_index")
+        P, K = int(poses.shape[0]), int(poses.shape[1])
+        scores = _chk(scores, name="scores")
+        colors = _chk(colors, U8, "colors")
+        C = int(colors.shape[0])
+        if tuple(poses.shape) != (P, K, 2) or tuple(scores.shape) != (P, K) or image_index.numel() != P or tuple(colors.shape) != (C, 3):
+            raise _lib.PoseKernelError("draw_shapes: poses (P,K,2), scores (P,K), image_index (P,), colors (C,3)")
+        if limbs is not None and limbs.numel():
+            limbs = _chk(limbs, I32, "limbs")
+            L = int(limbs.shape[0])
+            if tuple(limbs.shape) != (L, 2):
+                raise _lib.PoseKernelError("draw_shapes: limbs (L,2)")
+        else:
+            limbs = None
+    if boxes is not None:
+        boxes, box_image_index = _chk(boxes, name="boxes"), _chk(box_image_index, I32, "box_image_index")
+        Q = int(boxes.shape[0])
+        if tuple(boxes.shape) != (Q, 4) or box_image_index.numel() != Q:
+            raise _lib.PoseKernelError("draw_shapes: boxes (Q,4), box_image_index (Q,)")
+    b0, b1, b2 = (int(c) for c in box_color)
+    _call_if(N * H * W, "pk_draw_shapes", images, N, H, W, poses if P else None, scores if P else None, image_index if P else None, P, K,
+             limbs if P else None, L if P else 0, colors if P else None, C, boxes if Q else None, box_image_index if Q else None, Q, b0, b1, b2,
+             int(box_thickness), float(score_threshold), int(point_radius), int(line_thickness), stream_ptr())
+    return images
+
+
+def heatmap_overlay(images, heatmaps, alpha, lut, want_index=False):
+    """The heatmap overlay blended IN PLACE into a contiguous (N,H,W,3) uint8 batch (pk_heatmap_overlay): heatmaps (N,K,h,w) fp32,
+    lut (256,3) uint8 in the image's channel order.  Returns the (N,H,W) uint8 colour-index plane if asked for, else None."""
+    if not (isinstance(images, torch.Tensor) and images.is_contiguous()):
+        raise _lib.PoseKernelError("images: expected a contiguous CUDA(HIP) uint8 tensor (drawn in place)")
+    images, heatmaps, lut = _chk_images(images), _chk(heatmaps, name="heatmaps"), _chk(lut, U8, "lut")
+    N, H, W, _ = images.shape
+    if heatmaps.dim() != 4 or heatmaps.shape[0] != N or tuple(lut.shape) != (256, 3):
+        raise _lib.PoseKernelError(f"heatmap_overlay: heatmaps (N,K,h,w) for N = {N} images and a (256,3) lut, got {tuple(heatmaps.shape)}, {tuple(lut.shape)}")
+    _, K, h, w = heatmaps.shape
+    index = torch.empty(N, H, W, dtype=U8, device=images.device) if want_index else None
+    if N * H * W == 0:
+        return index
+    ws = torch.empty(max(1, _lib.lib.pk_heatmap_overlay_ws_floats(N, K, h, w, H, W)), dtype=F32, device=images.device)
+    call("pk_heatmap_overlay", images, heatmaps, float(alpha), lut, index, ws, N, K, h, w, H, W, stream_ptr())
+    return index
+
+
 # ------------------------------------------------------------------------------------------------ optimiser
 def adamw_step(param, grad, exp_avg, exp_avg_sq, flags, param_bf16, lr_dev, step_dev, beta1, beta2, eps, weight_decay, grad_scale=1.0):
     call("pk_adamw_step", param, grad, exp_avg, exp_avg_sq, flags, param_bf16, param.numel(), lr_dev, step_dev, float(beta1), float(beta2),

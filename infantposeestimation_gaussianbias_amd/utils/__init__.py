@@ -1,5 +1,9 @@
 """Utils module."""
 from .metrics import AverageMeter, COCOEvaluator, MetricLogger
 from . import postprocess
+from . import visualization
+from .visualization import (COCO_COLORS, COCO_SKELETON, create_grid_image, draw_bbox, draw_heatmaps, draw_poses, draw_skeleton,
+                            save_visualization)
 
-__all__ = ['AverageMeter', 'COCOEvaluator', 'MetricLogger', 'postprocess']
+__all__ = ['AverageMeter', 'COCOEvaluator', 'MetricLogger', 'postprocess', 'visualization', 'draw_skeleton', 'draw_heatmaps', 'draw_bbox',
+           'draw_poses', 'create_grid_image', 'save_visualization', 'COCO_SKELETON', 'COCO_COLORS']

@@ -6,7 +6,8 @@ Pre- and post-processing run on the device: the BGR -> RGB swap, the affine crop
 mean/std normalisation of inference.py:64-110 are ONE kernel per batch (pk_affine_crop_normalize, OpenCV's 8-bit warpAffine arithmetic
 as restated in oracle/warp.py), the model's flip-test inference and decode follow (PoseEstimator.inference), and the heat-px -> image
 mapping of inference.py:142-175 is one kernel (pk_affine_coords).  `predict_batch` really batches (the reference loops over predict).
-Visualisation (cv2 drawing) is outside the path: `visualize` needs OpenCV on the machine.
+Visualisation is on the device too: `visualize` / `visualize_batch` draw through utils/visualization.py (pk_draw_shapes,
+pk_heatmap_overlay: this project's own integer rasterisation rule, not OpenCV's pixels) and files are written with Pillow.
 """
 import argparse
 import os
@@ -23,6 +24,7 @@ from infantposeestimation_gaussianbias_amd.configs import get_config  # noqa: E4
 from infantposeestimation_gaussianbias_amd.datasets.transforms import DeviceCropper, get_affine_matrix  # noqa: E402
 from infantposeestimation_gaussianbias_amd.models import build_model  # noqa: E402
 from infantposeestimation_gaussianbias_amd.utils.postprocess import heatmap_to_image_coords  # noqa: E402
+from infantposeestimation_gaussianbias_amd.utils.visualization import COCO_SKELETON, draw_poses, draw_skeleton, write_image  # noqa: E402
 
 
 class PoseInference:
@@ -87,18 +89,36 @@ class PoseInference:
     def predict(self, img: np.ndarray, bbox: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
         return self.predict_batch([img], [bbox])[0]
 
+    # ---- inference.py:238-262
     def visualize(self, img, keypoints, scores, score_threshold: float = 0.3, output_path: Optional[str] = None):
-        try:
-            import cv2
-        except ImportError as e:
-            raise RuntimeError("visualize() draws with OpenCV, which is not installed (third-party, outside the inference path)") from e
-        vis = img.copy()
-        for (x, y), s in zip(keypoints, scores):
-            if s >= score_threshold:
-                cv2.circle(vis, (int(x), int(y)), 3, (0, 255, 0), -1)
+        """The skeleton of one prediction on a copy of `img` (BGR); saved too when `output_path` is given."""
+        vis = draw_skeleton(img, keypoints, scores, score_threshold=score_threshold, skeleton=COCO_SKELETON)
         if output_path:
-            cv2.imwrite(output_path, vis)
+            write_image(vis, output_path)
         return vis
+
+    def visualize_batch(self, imgs, results, bboxes=None, heatmaps=None, score_threshold: float = 0.3):
+        """Overlays for a batch of same-sized frames in one heatmap launch (if given) and one shape launch (draw_poses).
+
+        imgs: list of (H, W, 3) BGR uint8 arrays, or one (N, H, W, 3) array / device tensor.  results[i]: the (keypoints, scores) of frame
+        i, or a list of such pairs for several persons.  bboxes[i]: None, one (x1, y1, x2, y2) or a list of them.  heatmaps: (N, K, h, w).
+        Returns a list of arrays for a list, else the batch in the kind it came in."""
+        as_list = isinstance(imgs, (list, tuple))
+        batch = np.stack(imgs) if as_list else imgs
+        kps, scs, idx, boxes, bidx = [], [], [], [], []
+        for i, res in enumerate(results):
+            for kp, sc in ([res] if isinstance(res, tuple) else res):
+                kps.append(np.asarray(kp, np.float32))
+                scs.append(np.asarray(sc, np.float32))
+                idx.append(i)
+        for i, bb in enumerate(bboxes or []):
+            if bb is not None:
+                for b in np.asarray(bb, np.float32).reshape(-1, 4):
+                    boxes.append(b)
+                    bidx.append(i)
+        out = draw_poses(batch, np.stack(kps) if kps else None, np.stack(scs) if kps else None, idx, boxes=np.stack(boxes) if boxes else None,
+                         box_image_index=bidx, heatmaps=heatmaps, score_threshold=score_threshold, alpha=0.3)
+        return list(out) if as_list else out
 
 
 def detect_persons(img: np.ndarray) -> List[np.ndarray]:
@@ -120,10 +140,17 @@ def main(args):
         for k, ((x, y), s) in enumerate(zip(kp, sc)):
             print(f'  kpt {k:2d}: ({x:8.2f}, {y:8.2f})  score {s:.3f}')
     if args.output:
-        # inference.py:296-300 of the reference: draw and save.  Drawing is OpenCV's (visualize raises RuntimeError without cv2).
-        vis = img
-        for n, (kp, sc) in enumerate(results):
-            vis = pose.visualize(vis, kp, sc, score_threshold=args.threshold, output_path=args.output if n == len(results) - 1 else None)
+        # inference.py:296-300 of the reference: draw and save -- here every person of the image in one call
+        heatmaps = None
+        if args.draw_heatmaps:
+            if len(bboxes) == 1 and np.array_equal(np.asarray(bboxes[0], np.float64), [0, 0, img.shape[1], img.shape[0]]):
+                with torch.no_grad():
+                    heatmaps = pose.model(pose.preprocess(img, bboxes[0])[0])['heatmaps'].float()
+            else:
+                print('--draw_heatmaps: skipped (only drawn for a single whole-image box)')
+        vis = pose.visualize_batch(img[None], [results], bboxes=[bboxes] if args.draw_bbox else None, heatmaps=heatmaps,
+                                   score_threshold=args.threshold)[0]
+        write_image(vis, args.output)
         print(f'Result saved to: {args.output}')
 
 
@@ -137,4 +164,9 @@ if __name__ == '__main__':
     p.add_argument('--threshold', type=float, default=0.3)
     p.add_argument('--bbox', type=float, nargs=4, default=None)
     p.add_argument('--config', type=str, default=None)
+    p.add_argument('--draw_bbox', action='store_true', help='also draw the person boxes into --output')
+    p.add_argument('--draw_heatmaps', action='store_true',
+                   help='also overlay the predicted heatmaps (alpha 0.3) into --output; only for a single whole-image box, where the '
+                        'model crop and the image coincide up to the crop\'s affine map (the map is stretched over the image, as the '
+                        'reference does); skipped with a message otherwise')
     main(p.parse_args())
