@@ -108,6 +108,18 @@ int pk_coco_kpt_eval(const double* oks, const int64_t* oks_off, const int32_t* g
  * convolution's input layout (channels 3..7 zero).                                                                                 */
 int pk_affine_crop_normalize(const void* src_u8, const void* desc_table, int n_samples, int out_w, int out_h, float* out_nchw_f32,
                              void* out_nhwc8_bf16, const float* mean3, const float* std3, void* stream);
+/* The same crop with the reference's CustomColorJitter (data/examples.py:367-401) between the 8-bit warp and the normalisation.
+ * jitter_table rows (16 bytes): { int32 enable; float b, c, s } (brightness, contrast, saturation factors), one per sample.  With
+ * u the crop's bytes, N = 3 out_w out_h and S their exact integer sum, every operation rounded once to float32 (no FMA):
+ *   m = (float)((double)S / (255.0 N) * (double)b);   x = u / 255 * b;   x = (x - m) * c + m;   g = ((x0 + x1) + x2) / 3 per pixel;
+ *   x = g + (x - g) * s;   u' = (int)(min(max(x, 0), 1) * 255);   then ((u' / 255) - mean) / std as above.
+ * A row with enable == 0 gives exactly pk_affine_crop_normalize's output for that sample (factors 1, 1, 1 do not: the / 255 * 255
+ * round trip truncates).  Two launches on `stream`; ws: pk_affine_crop_jitter_ws_bytes(n_samples, out_w, out_h) bytes, 4-byte aligned
+ * (the query returns PK_ERR_INVALID for a refused shape: 765 out_w out_h must stay below 2^32).                                     */
+int pk_affine_crop_jitter_ws_bytes(int n_samples, int out_w, int out_h);
+int pk_affine_crop_jitter_normalize(const void* src_u8, const void* desc_table, const void* jitter_table, int n_samples, int out_w, int out_h,
+                                    float* out_nchw_f32, void* out_nhwc8_bf16, const float* mean3, const float* std3, void* ws,
+                                    int64_t ws_bytes, void* stream);
 
 /* ---- D4: flip-test merge (models/pose_estimator.py:303-319): out = (a + swapLR(flipW(b)))/2 ------------- */
 int pk_flip_merge(const float* a, const float* b_flipped, const int32_t* partner, float* out,

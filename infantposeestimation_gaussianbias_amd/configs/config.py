@@ -4,7 +4,9 @@ Same dataclass fields and defaults, so `cfg.data.input_size`, `cfg.model.backbon
 identically.  Extension over the reference: `get_config(path_or_name)` also accepts
   * a preset name ("hrformer_small", "hrformer_base", "hrnet_w32", "hrnet_w48", "hrnet_w18", "preemie"), or
   * a legacy-format yaml (reference configs/*.yaml, written by root config.py:135-224): `MODEL.NUM_JOINTS`,
-    `MODEL.IMAGE_SIZE`, `MODEL.HEATMAP_SIZE`, `MODEL.SIGMA`, `TRAIN.*` are mapped onto the dataclass fields.
+    `MODEL.IMAGE_SIZE`, `MODEL.HEATMAP_SIZE`, `MODEL.SIGMA`, `TRAIN.*` are mapped onto the dataclass fields, and
+    `DATA.COLOR_JITTER.{BRIGHTNESS,CONTRAST,SATURATION}` onto `cfg.train.color_jitter` (a yaml that names it trains with it; a
+    missing sub-key reads as 0, and a block that is empty or all zero leaves jitter off).
 """
 import os
 from dataclasses import dataclass, field
@@ -72,6 +74,10 @@ class TrainConfig:
     checkpoint_dir: str = 'checkpoints/'
     device: str = 'cuda'
     fp16: bool = True        # "mixed precision on": bf16 on MI355X (no GradScaler needed)
+    # Colour jitter of the training crops (legacy yaml DATA.COLOR_JITTER, `train.py --color_jitter`): None or the (brightness, contrast,
+    # saturation) ranges.  Plain class attributes, NOT dataclass fields: the field set stays the reference's (asdict, __init__, ==).
+    color_jitter = None
+    color_jitter_prob = 0.5
 
 
 @dataclass
@@ -138,6 +144,12 @@ def _apply_legacy_yaml(cfg: Config, path: str) -> Config:
                            ('VAL_INTERVAL', 'val_interval', int)):
         if src in t:
             setattr(cfg.train, dst, cast(t[src]))
+    cj = (y.get('DATA', {}) or {}).get('COLOR_JITTER')
+    if cj is not None:
+        # an empty or all-zero block stays off: ranges (0, 0, 0) would still send half the samples through factors (1, 1, 1), which is
+        # not the identity (u / 255 * 255 truncates)
+        rng = tuple(float((cj or {}).get(k, 0) or 0) for k in ('BRIGHTNESS', 'CONTRAST', 'SATURATION'))
+        cfg.train.color_jitter = rng if any(rng) else None
     cfg.exp_name = os.path.splitext(os.path.basename(path))[0]
     return cfg
 

@@ -117,7 +117,8 @@ class DeviceBatcher:
 
     def _build(self, samples):
         d = self.cfg.data
-        img32, img16 = self.cropper([s["img"] for s in samples], [s["matrix"] for s in samples], [s.get("flip", False) for s in samples])
+        img32, img16 = self.cropper([s["img"] for s in samples], [s["matrix"] for s in samples], [s.get("flip", False) for s in samples],
+                                    jitter=[s.get("jitter") for s in samples])
         kp, vis = self._keypoints_to_device(samples)
         target, weight = generate_target(kp, vis, d.input_size, d.heatmap_size, d.sigma)
         f32 = lambda k: torch.from_numpy(np.stack([np.asarray(s[k], np.float32) for s in samples]))
@@ -161,7 +162,8 @@ class DeviceBatcher:
 def build_coco_dataloader(cfg, is_train: bool = True, device="cuda"):
     """coco_dataset.py:253-306 with the image work moved to the device."""
     d, t = cfg.data, cfg.train
-    tf = get_train_transforms(d.input_size, t.flip_prob, t.rotation_factor, t.scale_factor) if is_train else get_val_transforms(d.input_size)
+    tf = (get_train_transforms(d.input_size, t.flip_prob, t.rotation_factor, t.scale_factor, color_jitter=t.color_jitter,
+                               color_jitter_prob=t.color_jitter_prob) if is_train else get_val_transforms(d.input_size))
     ds = COCOPoseDataset(d.data_root, d.train_ann if is_train else d.val_ann, d.train_img_prefix if is_train else d.val_img_prefix, d.input_size,
                          d.heatmap_size, d.sigma, d.num_keypoints, tf, is_train, d.flip_pairs)
     loader = torch.utils.data.DataLoader(ds, batch_size=t.batch_size, shuffle=is_train, num_workers=t.num_workers, collate_fn=collate_records,

@@ -6,6 +6,8 @@
   * the image work (affine crop, mirror, BGR->RGB, ToTensor, normalise) is NOT done per sample with OpenCV: the transforms only record
     `data['matrix']` / `data['flip']`, and `DeviceCropper` warps the whole batch in one kernel (pk_affine_crop_normalize) straight into
     the network's input layout.  At ~3 000 img/s per GPU the reference's 4 DataLoader workers doing cv2.warpAffine would be ~7x too slow.
+    Photometric augmentation follows the same split: `ColorJitter` only draws the factors (`data['jitter']`), the crop's launch
+    sequence applies them (pk_affine_crop_jitter_normalize).
 """
 from typing import Dict, List, Optional, Tuple
 
@@ -168,9 +170,30 @@ class RandomHalfBody:
         return data
 
 
-def get_train_transforms(input_size, flip_prob=0.5, rotation_factor=40.0, scale_factor=(0.5, 1.5), rng=None) -> Compose:
-    return Compose([RandomFlip(flip_prob, rng), RandomHalfBody(0.3, rng=rng), RandomBBoxTransform(rotation_factor, scale_factor, rng=rng),
-                    TopdownAffineWithRotation(input_size)])
+class ColorJitter:
+    """The decisions of the reference's CustomColorJitter (data/examples.py:367-401): the same draws in the same order -- `rand()`,
+    and unless it is above `prob`, `uniform` for brightness, contrast and saturation.  Records `data['jitter'] = (b, c, s)` or None;
+    the image is jittered by the crop's launch sequence on the device (`DeviceCropper(..., jitter=)`)."""
+
+    def __init__(self, brightness: float = 0.2, contrast: float = 0.2, saturation: float = 0.2, prob: float = 0.5, rng=None):
+        self.brightness, self.contrast, self.saturation, self.prob, self.rng = brightness, contrast, saturation, prob, rng or np.random
+
+    def __call__(self, data: Dict) -> Dict:
+        data['jitter'] = None
+        if self.rng.rand() > self.prob:
+            return data
+        data['jitter'] = tuple(1 + self.rng.uniform(-r, r) for r in (self.brightness, self.contrast, self.saturation))
+        return data
+
+
+def get_train_transforms(input_size, flip_prob=0.5, rotation_factor=40.0, scale_factor=(0.5, 1.5), rng=None, color_jitter=None,
+                         color_jitter_prob=0.5) -> Compose:
+    """`color_jitter`: None (no photometric augmentation, no extra draws) or the (brightness, contrast, saturation) ranges."""
+    tf = [RandomFlip(flip_prob, rng), RandomHalfBody(0.3, rng=rng), RandomBBoxTransform(rotation_factor, scale_factor, rng=rng),
+          TopdownAffineWithRotation(input_size)]
+    if color_jitter is not None:
+        tf.append(ColorJitter(*color_jitter, prob=color_jitter_prob, rng=rng))
+    return Compose(tf)
 
 
 def get_val_transforms(input_size) -> Compose:
@@ -178,17 +201,24 @@ def get_val_transforms(input_size) -> Compose:
 
 
 _CROP_DTYPE = np.dtype([("off", "<i8"), ("H", "<i4"), ("W", "<i4"), ("flip", "<i4"), ("bgr", "<i4"), ("minv", "<f8", (6,))])
+_JITTER_DTYPE = np.dtype([("enable", "<i4"), ("b", "<f4"), ("c", "<f4"), ("s", "<f4")])
 
 
 class DeviceCropper:
     """Batched affine crop + mirror + normalise on the GPU.  `images`: list of (H,W,3) uint8 arrays (numpy or torch, host);
-    `matrices`: the forward 2x3 crop matrices; -> (fp32 NCHW batch | None, bf16 NHWC-8 batch | None)."""
+    `matrices`: the forward 2x3 crop matrices; `jitter`: per image None or the (b, c, s) factors of `ColorJitter`;
+    -> (fp32 NCHW batch | None, bf16 NHWC-8 batch | None).  The work goes to the current stream; the scratch of the jitter launches is
+    kept per stream, so one cropper may serve several streams.  That cache is never pruned: one allocation (12.6 MB at B = 64, 256 x 192)
+    stays for every stream the cropper has ever been called on -- sized for the project's one or two streams, not for a cropper shared by
+    many short-lived ones."""
 
     def __init__(self, input_size, device="cuda", nchw=True, nhwc8=True):
         self.w, self.h, self.device, self.nchw, self.nhwc8 = int(input_size[0]), int(input_size[1]), torch.device(device), nchw, nhwc8
         # two reusable pinned staging buffers (pin_memory() per batch is a hipHostMalloc of ~15 MB each time); a slot is rewritten only
         # after the host-to-device copy that last read it has completed (its event)
         self._pinned, self._pin_ev, self._slot = [None, None], [None, None], 0
+        self._jitter_ws = {}        # workspace of the jitter launches per stream, kept between calls: calls on one stream are ordered, a
+                                    # second stream must not overwrite the crop scratch the first one's second launch still reads
 
     def _staging(self, nbytes):
         if not torch.cuda.is_available():
@@ -200,10 +230,30 @@ class DeviceCropper:
             self._pinned[i] = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8).pin_memory()
         return self._pinned[i][:nbytes], i
 
-    def __call__(self, images, matrices, flips=None, bgr=False):
+    def _jitter_table(self, jitter, B):
+        """-> (table, workspace bytes), or (None, 0) when no sample is jittered (the plain call)."""
+        if jitter is None:
+            return None, 0
+        if len(jitter) != B:
+            raise _lib.PoseKernelError(f"DeviceCropper: {len(jitter)} jitter entries for {B} images")
+        if all(j is None for j in jitter):
+            return None, 0
+        tab = np.zeros(B, _JITTER_DTYPE)
+        for i, j in enumerate(jitter):
+            if j is not None:
+                if len(j) != 3 or not np.all(np.isfinite(np.asarray(j, np.float32))):
+                    raise _lib.PoseKernelError(f"DeviceCropper: jitter {i} must be three finite factors (b, c, s), got {j!r}")
+                tab[i] = (1, j[0], j[1], j[2])
+        need = _lib.lib.pk_affine_crop_jitter_ws_bytes(B, self.w, self.h)
+        if need <= 0:
+            raise _lib.PoseKernelError(_lib.lib.pk_last_error_string().decode())
+        return tab, need
+
+    def __call__(self, images, matrices, flips=None, bgr=False, jitter=None):
         B = len(images)
         if B == 0 or len(matrices) != B:
             raise _lib.PoseKernelError("DeviceCropper: need one matrix per image")
+        jtab, ws_bytes = self._jitter_table(jitter, B)
         desc = np.zeros(B, _CROP_DTYPE)
         sizes, off = [], 0
         for i, im in enumerate(images):
@@ -213,8 +263,9 @@ class DeviceCropper:
             desc[i] = (off, im.shape[0], im.shape[1], int(bool(flips[i])) if flips is not None else 0, int(bool(bgr)), invert_affine(matrices[i]))
             sizes.append(im)
             off += (im.size + 15) // 16 * 16
-        nd = desc.nbytes
-        host, slot = self._staging(off + (nd + 15) // 16 * 16)          # [images | descriptor table]: ONE host-to-device copy
+        nd, nj = desc.nbytes, 0 if jtab is None else jtab.nbytes
+        joff = off + (nd + 15) // 16 * 16
+        host, slot = self._staging(joff + (nj + 15) // 16 * 16)         # [images | descriptor table | jitter table]: ONE host-to-device copy
         # plain memcpy through a numpy view: a torch slice assignment fans every 0.9 MB image out over all intra-op threads (128 on the
         # GPU host: 21 ms per 64 images against 1.4 ms; scripts/probes/cropper_phases.py)
         hv = host.numpy()
@@ -222,6 +273,8 @@ class DeviceCropper:
             o = int(desc[i]["off"])
             np.copyto(hv[o:o + im.size], np.ascontiguousarray(im).reshape(-1))
         np.copyto(hv[off:off + nd], desc.view(np.uint8))
+        if nj:
+            np.copyto(hv[joff:joff + nj], jtab.view(np.uint8))
         dev_buf = host.to(self.device, non_blocking=True)
         if slot is not None:
             self._pin_ev[slot] = torch.cuda.Event()
@@ -229,6 +282,14 @@ class DeviceCropper:
         src, dtab = dev_buf[:off], dev_buf[off:off + nd]
         out32 = torch.empty(B, 3, self.h, self.w, dtype=torch.float32, device=self.device) if self.nchw else None
         out16 = torch.empty(B, self.h, self.w, 8, dtype=torch.bfloat16, device=self.device) if self.nhwc8 else None
-        call("pk_affine_crop_normalize", src, dtab, B, self.w, self.h, out32, out16, MEAN.ctypes.data, STD.ctypes.data, stream_ptr())
+        if jtab is None:
+            call("pk_affine_crop_normalize", src, dtab, B, self.w, self.h, out32, out16, MEAN.ctypes.data, STD.ctypes.data, stream_ptr())
+        else:
+            st = stream_ptr()
+            ws = self._jitter_ws.get(st)
+            if ws is None or ws.numel() < ws_bytes:
+                ws = self._jitter_ws[st] = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
+            call("pk_affine_crop_jitter_normalize", src, dtab, dev_buf[joff:joff + nj], B, self.w, self.h, out32, out16, MEAN.ctypes.data,
+                 STD.ctypes.data, ws, ws.numel(), st)
         dev_buf.record_stream(torch.cuda.current_stream())
         return out32, out16

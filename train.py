@@ -6,7 +6,8 @@
 
 Differences from the reference loop (train.py:131-228): no per-step `loss.item()` host sync (losses are read back only at the
 log interval), bf16 instead of fp16+GradScaler, fused AdamW over a flat parameter buffer, optional hipGraph replay
-(`--graph`).  With POSE_SYNTHETIC=1 the loader yields device-resident synthetic batches (no COCO on disk needed).
+(`--graph`), colour jitter on the device (`--color_jitter B C S`, or DATA.COLOR_JITTER of a legacy yaml).  With POSE_SYNTHETIC=1 the
+loader yields device-resident synthetic batches (no COCO on disk needed; they are not jittered).
 """
 import argparse
 import logging
@@ -78,6 +79,10 @@ def main(args):
         cfg.train.max_epochs = args.epochs
     if args.lr:
         cfg.train.lr = args.lr
+    if args.color_jitter is not None:
+        cfg.train.color_jitter = tuple(args.color_jitter)
+    if args.color_jitter_prob is not None:
+        cfg.train.color_jitter_prob = args.color_jitter_prob
     world, rank, local = int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0))
     torch.cuda.set_device(local)
     if world > 1:
@@ -132,4 +137,7 @@ if __name__ == "__main__":
     p.add_argument("--resume", type=str, default=None)
     p.add_argument("--config", type=str, default=None, help="preset name or legacy yaml (extension over the reference)")
     p.add_argument("--graph", action="store_true", help="replay the step as a captured hipGraph")
+    p.add_argument("--color_jitter", type=float, nargs=3, default=None, metavar=("B", "C", "S"),
+                   help="brightness / contrast / saturation ranges of the colour jitter applied to training crops on the device")
+    p.add_argument("--color_jitter_prob", type=float, default=None, help="share of the samples that are jittered (default 0.5)")
     main(p.parse_args())
