@@ -444,7 +444,15 @@ int pk_embed_boxes(float* twin_base, const void* desc_table, const int* block_de
  * pk_heatmap_overlay: heatmaps (N,K,h,w) fp32 -> max over K, bilinear resize to (H,W) (half-pixel rule), per-image min/max of the
  *   resized plane, idx = floor(255 (m - min) / (max - min + 1e-8)), out = (img (256 - a) + lut[idx] a + 128) >> 8 with
  *   a = clamp(rint(256 alpha), 0, 256).  lut: (256,3) uint8; index_u8 (optional): (N,H,W) uint8 receives idx;
- *   ws: pk_heatmap_overlay_ws_floats(...) floats.                                                                                    */
+ *   ws: pk_heatmap_overlay_ws_floats(...) floats.
+ * pk_heatmap_overlay_patches: one stack per person.  heatmaps (P,K,h,w) fp32; patch_image_index (P,) int32 non-decreasing, each in
+ *   [0, N) (NOT checked here: the caller guarantees it; a frame may have none or many); patch_matrix (P,6) float64 on the device, the
+ *   2x3 map from frame pixels to heat-map pixels (the crop matrix with (w,h) as its output size).  m_p = max over K, lo_p / hi_p =
+ *   min / max of m_p over its own plane; frame pixel (X,Y) is covered by p iff (s,t) = M_p (X,Y,1) (float64) has 0 <= s <= w-1 and
+ *   0 <= t <= h-1; v = max over the covering p of (bilinear(m_p; s,t) - lo_p) / (hi_p - lo_p + 1e-8); idx = clamp(floor(255 v)), NaN -> 0;
+ *   covered pixels get the blend of pk_heatmap_overlay, the others keep their bytes.  index_u8 / cover_u8 (optional): (N,H,W) uint8
+ *   receive idx (0 where uncovered) and the number of covering patches (saturating at 255).  P <= 65535.  No atomics.
+ *   ws: pk_heatmap_overlay_patches_ws_floats(...) floats.                                                                            */
 int pk_draw_shapes(void* images_u8, int N, int H, int W, const float* poses, const float* scores, const int32_t* image_index, int P,
                    int K, const int32_t* limbs, int L, const void* colors_u8, int C, const float* boxes,
                    const int32_t* box_image_index, int Q, int box_c0, int box_c1, int box_c2, int box_thickness,
@@ -452,6 +460,10 @@ int pk_draw_shapes(void* images_u8, int N, int H, int W, const float* poses, con
 int pk_heatmap_overlay_ws_floats(int N, int K, int h, int w, int H, int W);
 int pk_heatmap_overlay(void* images_u8, const float* heatmaps, float alpha, const void* lut_u8, void* index_u8, float* ws, int N,
                        int K, int h, int w, int H, int W, void* stream);
+int pk_heatmap_overlay_patches_ws_floats(int P, int K, int h, int w);
+int pk_heatmap_overlay_patches(void* images_u8, const float* heatmaps, const int32_t* patch_image_index, const double* patch_matrix,
+                               float alpha, const void* lut_u8, void* index_u8, void* cover_u8, float* ws, int N, int P, int K, int h,
+                               int w, int H, int W, void* stream);
 
 #ifdef __cplusplus
 }

@@ -273,12 +273,15 @@ __device__ __forceinline__ void ov_taps(int o, int n_in, int n_out, int& i0, int
     i1 = min(i0 + 1, n_in - 1);
     f = s - (float)i0;
 }
+__device__ __forceinline__ float ov_bilinear(const float* __restrict__ m, int w, int y0, int y1, int x0, int x1, float fy, float fx) {
+    return (m[y0 * w + x0] * (1.f - fx) + m[y0 * w + x1] * fx) * (1.f - fy) + (m[y1 * w + x0] * (1.f - fx) + m[y1 * w + x1] * fx) * fy;
+}
 __device__ __forceinline__ float ov_resized(const float* __restrict__ m, int h, int w, int H, int W, int y, int x) {
     int y0, y1, x0, x1;
     float fy, fx;
     ov_taps(y, h, H, y0, y1, fy);
     ov_taps(x, w, W, x0, x1, fx);
-    return (m[y0 * w + x0] * (1.f - fx) + m[y0 * w + x1] * fx) * (1.f - fy) + (m[y1 * w + x0] * (1.f - fx) + m[y1 * w + x1] * fx) * fy;
+    return ov_bilinear(m, w, y0, y1, x0, x1, fy, fx);
 }
 static inline int ov_blocks(int H, int W) {
     const int64_t n = ((int64_t)H * W + 2047) / 2048;
@@ -383,4 +386,162 @@ extern "C" int pk_heatmap_overlay(void* images_u8, const float* heatmaps, float 
     hipLaunchKernelGGL(k_overlay_blend, dim3((H * W + 1023) / 1024, N), dim3(256), 0, (hipStream_t)stream, (uint8_t*)images_u8,
                        (const float*)mplane, (const float*)partial, nb, (const uint8_t*)lut_u8, (uint8_t*)index_u8, a256, h, w, H, W);
     return pk_launch_status("pk_heatmap_overlay");
+}
+
+// ================================================================================================ heatmap overlay, one stack per person
+// Top-down use: patch p is the (K,h,w) stack of one person, patch_matrix[p] the 2x3 float64 map from pixels of frame
+// patch_image_index[p] to heat-map pixels (the crop matrix with the heat-map size as its output size: heat pixel x is input pixel
+// x w_in / w, the decode's convention).  Rule ("Heatmaps where the crop lies"): m_p = max over K; lo_p / hi_p = min / max of
+// m_p over its own h x w plane; frame pixel (X, Y) maps to (s, t) = M_p (X, Y, 1) in float64 and is covered by p iff 0 <= s <= w - 1 and
+// 0 <= t <= h - 1; there v_p = (bilinear(m_p; s, t) - lo_p) / (hi_p - lo_p + 1e-8) with the tap expression of ov_resized; a covered
+// pixel takes v = max over its covering patches (NaN ignored unless every one is NaN), idx = clamp(floor(255 v), 0, 255), NaN -> 0,
+// and the integer blend of pk_heatmap_overlay; an uncovered pixel keeps its bytes.  A maximum and a count: no order, no atomics.
+__device__ __forceinline__ double ovp_map(const double a, const double b, const double c, const int X, const int Y) {
+    return (a * (double)X + b * (double)Y) + c;       // every operation rounds monotonically: over a rectangle the extremes are at its corners
+}
+
+// one workgroup per patch: min and max of its own max plane, fixed order (strided partials, wave butterflies, four waves in order)
+__global__ void __launch_bounds__(256) k_overlay_patch_minmax(const float* __restrict__ mplane, float* __restrict__ stats, int hw) {
+    __shared__ float s_lo[4], s_hi[4];
+    const int p = blockIdx.x;
+    const float* m = mplane + (size_t)p * hw;
+    float lo = INFINITY, hi = -INFINITY;
+    for (int i = threadIdx.x; i < hw; i += 256) {
+        const float v = m[i];
+        lo = fminf(lo, v);
+        hi = fmaxf(hi, v);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        lo = fminf(lo, __shfl_xor(lo, o, 64));
+        hi = fmaxf(hi, __shfl_xor(hi, o, 64));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        s_lo[threadIdx.x >> 6] = lo;
+        s_hi[threadIdx.x >> 6] = hi;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        stats[2 * (size_t)p] = fminf(fminf(s_lo[0], s_lo[1]), fminf(s_lo[2], s_lo[3]));
+        stats[2 * (size_t)p + 1] = fmaxf(fmaxf(s_hi[0], s_hi[1]), fmaxf(s_hi[2], s_hi[3]));
+    }
+}
+
+// Gather over the tiles of k_draw_shapes: a workgroup owns a 32 x 8 tile of one frame, finds the frame's patches by binary search in the
+// non-decreasing index and walks them 256 at a time, one candidate per thread.  A candidate survives unless the tile lies wholly on one
+// side of its heat-map rectangle: s and t are evaluated at the tile's four corner pixels with the expression every pixel uses, and as
+// that expression is monotone in X and in Y the test can never drop a patch that covers a pixel of the tile (it needs no inverse matrix,
+// so a singular or ill-conditioned matrix costs nothing but the cull; it is also tighter than the bounding box of a rotated crop).
+// Survivors go to LDS (ballot compaction as in k_draw_shapes) and every thread folds them into its own pixel in registers; all lanes
+// read the same record, a broadcast.  A tile no patch reaches never reads the image.
+__global__ void __launch_bounds__(256) k_overlay_patches_blend(uint8_t* __restrict__ img, const float* __restrict__ mplane,
+                                                               const float* __restrict__ stats, const int32_t* __restrict__ patch_img,
+                                                               const double* __restrict__ patch_matrix, const uint8_t* __restrict__ lut,
+                                                               uint8_t* __restrict__ index, uint8_t* __restrict__ cover, int a256, int P,
+                                                               int h, int w, int H, int W) {
+    __shared__ double s_m[256][6];
+    __shared__ float s_lo[256], s_den[256];
+    __shared__ int s_p[256];
+    __shared__ int s_wcnt[4];
+    const int n = blockIdx.z, t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int tx0 = blockIdx.x * DRAW_TW, ty0 = blockIdx.y * DRAW_TH;
+    const int tx1 = min(tx0 + DRAW_TW - 1, W - 1), ty1 = min(ty0 + DRAW_TH - 1, H - 1);
+    const int px = tx0 + (t & (DRAW_TW - 1)), py = ty0 + (t >> 5);
+    const bool live = px < W && py < H;
+    const size_t at = ((size_t)n * H + (live ? py : 0)) * W + (live ? px : 0);
+    const int p_lo = draw_lower_bound(patch_img, P, n), total = draw_lower_bound(patch_img, P, n + 1) - p_lo;
+    const double smax = (double)(w - 1), tmax = (double)(h - 1);
+    const int hw = h * w;
+    float v = NAN;                                    // fmaxf returns the other operand for a NaN: the first covering patch replaces it
+    int cnt = 0;
+    for (int base = 0; base < total; base += 256) {
+        const int cand = base + t;
+        bool keep = false;
+        double m[6];
+        if (cand < total) {
+#pragma unroll
+            for (int i = 0; i < 6; ++i) m[i] = patch_matrix[(size_t)(p_lo + cand) * 6 + i];
+            const double sa = ovp_map(m[0], m[1], m[2], tx0, ty0), sb = ovp_map(m[0], m[1], m[2], tx1, ty0);
+            const double sc = ovp_map(m[0], m[1], m[2], tx0, ty1), sd = ovp_map(m[0], m[1], m[2], tx1, ty1);
+            const double ta = ovp_map(m[3], m[4], m[5], tx0, ty0), tb = ovp_map(m[3], m[4], m[5], tx1, ty0);
+            const double tc = ovp_map(m[3], m[4], m[5], tx0, ty1), td = ovp_map(m[3], m[4], m[5], tx1, ty1);
+            const bool out = (sa < 0. && sb < 0. && sc < 0. && sd < 0.) || (sa > smax && sb > smax && sc > smax && sd > smax) ||
+                             (ta < 0. && tb < 0. && tc < 0. && td < 0.) || (ta > tmax && tb > tmax && tc > tmax && td > tmax);
+            keep = !out;                              // a NaN compares false: kept here, covered nowhere
+        }
+        const unsigned long long bal = __ballot(keep);
+        if (lane == 0) s_wcnt[wv] = __popcll(bal);
+        __syncthreads();
+        int off = 0, count = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int c = s_wcnt[i];
+            off += i < wv ? c : 0;
+            count += c;
+        }
+        if (keep) {
+            const int slot = off + __popcll(bal & ((1ull << lane) - 1ull));      // < 256
+#pragma unroll
+            for (int i = 0; i < 6; ++i) s_m[slot][i] = m[i];
+            const float lo = stats[2 * (size_t)(p_lo + cand)];
+            s_lo[slot] = lo;
+            s_den[slot] = (stats[2 * (size_t)(p_lo + cand) + 1] - lo) + 1e-8f;
+            s_p[slot] = p_lo + cand;
+        }
+        __syncthreads();
+        if (live) {
+            for (int i = 0; i < count; ++i) {
+                const double s = ovp_map(s_m[i][0], s_m[i][1], s_m[i][2], px, py), u = ovp_map(s_m[i][3], s_m[i][4], s_m[i][5], px, py);
+                if (!(s >= 0. && s <= smax && u >= 0. && u <= tmax)) continue;
+                const int x0 = (int)s, y0 = (int)u;   // floor of a value in [0, n - 1]
+                const int x1 = min(x0 + 1, w - 1), y1 = min(y0 + 1, h - 1);
+                const float fx = (float)(s - (double)x0), fy = (float)(u - (double)y0);
+                const float r = ov_bilinear(mplane + (size_t)s_p[i] * hw, w, y0, y1, x0, x1, fy, fx);
+                v = fmaxf(v, __fdiv_rn(r - s_lo[i], s_den[i]));
+                ++cnt;
+            }
+        }
+        __syncthreads();                              // the records are rewritten by the next 256 candidates
+    }
+    if (!live) return;
+    int idx = 0;
+    if (cnt > 0) {
+        const float s = floorf(255.f * v);
+        idx = s >= 0.f ? (s <= 255.f ? (int)s : 255) : 0;      // NaN -> 0
+        uint8_t* p = img + at * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) p[c] = (uint8_t)(((int)p[c] * (256 - a256) + (int)lut[idx * 3 + c] * a256 + 128) >> 8);
+    }
+    if (index) index[at] = (uint8_t)idx;
+    if (cover) cover[at] = (uint8_t)min(cnt, 255);
+}
+
+extern "C" int pk_heatmap_overlay_patches_ws_floats(int P, int K, int h, int w) {
+    if (P <= 0 || K <= 0 || h <= 0 || w <= 0) return 0;
+    const int64_t n = (int64_t)P * h * w + (int64_t)P * 2;
+    return n > 0x7fffffff ? 0 : (int)n;
+}
+
+extern "C" int pk_heatmap_overlay_patches(void* images_u8, const float* heatmaps, const int32_t* patch_image_index, const double* patch_matrix,
+                                          float alpha, const void* lut_u8, void* index_u8, void* cover_u8, float* ws, int N, int P, int K, int h,
+                                          int w, int H, int W, void* stream) {
+    PK_REQUIRE(images_u8 && heatmaps && patch_image_index && patch_matrix && lut_u8 && ws, "pk_heatmap_overlay_patches: null pointer");
+    PK_REQUIRE(N > 0 && N <= 65535 && P > 0 && K > 0 && h > 0 && w > 0 && H > 0 && W > 0,
+               "pk_heatmap_overlay_patches: bad shape N=%d P=%d K=%d h=%d w=%d H=%d W=%d", N, P, K, h, w, H, W);
+    PK_REQUIRE(P <= 65535, "pk_heatmap_overlay_patches: at most 65535 patches in one call (got %d)", P);
+    PK_REQUIRE(H <= DRAW_MAX_HW && W <= DRAW_MAX_HW && h <= DRAW_MAX_HW && w <= DRAW_MAX_HW, "pk_heatmap_overlay_patches: planes up to %d x %d",
+               DRAW_MAX_HW, DRAW_MAX_HW);
+    PK_REQUIRE(pk_heatmap_overlay_patches_ws_floats(P, K, h, w) > 0, "pk_heatmap_overlay_patches: workspace size overflows");
+    PK_REQUIRE(alpha == alpha, "pk_heatmap_overlay_patches: alpha is NaN");
+    const float a = rintf(256.f * alpha);
+    const int a256 = a <= 0.f ? 0 : (a >= 256.f ? 256 : (int)a);
+    const int hw = h * w;
+    float* mplane = ws;
+    float* stats = ws + (size_t)P * hw;
+    hipLaunchKernelGGL(k_overlay_max, dim3((hw + 255) / 256, P), dim3(256), 0, (hipStream_t)stream, heatmaps, mplane, K, hw);
+    hipLaunchKernelGGL(k_overlay_patch_minmax, dim3(P), dim3(256), 0, (hipStream_t)stream, (const float*)mplane, stats, hw);
+    hipLaunchKernelGGL(k_overlay_patches_blend, dim3((W + DRAW_TW - 1) / DRAW_TW, (H + DRAW_TH - 1) / DRAW_TH, N), dim3(256), 0,
+                       (hipStream_t)stream, (uint8_t*)images_u8, (const float*)mplane, (const float*)stats, patch_image_index, patch_matrix,
+                       (const uint8_t*)lut_u8, (uint8_t*)index_u8, (uint8_t*)cover_u8, a256, P, h, w, H, W);
+    return pk_launch_status("pk_heatmap_overlay_patches");
 }

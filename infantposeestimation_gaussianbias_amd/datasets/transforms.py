@@ -249,28 +249,41 @@ class DeviceCropper:
             raise _lib.PoseKernelError(_lib.lib.pk_last_error_string().decode())
         return tab, need
 
-    def __call__(self, images, matrices, flips=None, bgr=False, jitter=None):
-        B = len(images)
+    def __call__(self, images, matrices, flips=None, bgr=False, jitter=None, image_index=None):
+        """`image_index` (one entry per crop): crop i reads images[image_index[i]], so several crops (the persons of one frame) share
+        one staged and uploaded image; `matrices`, `flips` and `jitter` then have one entry per crop.  Without it crop i reads image i."""
+        if image_index is None:
+            src_of = range(len(images))
+        else:
+            src_of = [int(j) for j in image_index]
+            if any(j < 0 or j >= len(images) for j in src_of):
+                raise _lib.PoseKernelError(f"DeviceCropper: image_index entries must be in [0, {len(images)}), got {src_of}")
+        B = len(src_of)
         if B == 0 or len(matrices) != B:
-            raise _lib.PoseKernelError("DeviceCropper: need one matrix per image")
+            raise _lib.PoseKernelError("DeviceCropper: need one matrix per image" if image_index is None else
+                                       f"DeviceCropper: {len(matrices)} matrices for {B} image_index entries")
+        if image_index is not None and flips is not None and len(flips) != B:
+            raise _lib.PoseKernelError(f"DeviceCropper: {len(flips)} flips for {B} image_index entries")
         jtab, ws_bytes = self._jitter_table(jitter, B)
-        desc = np.zeros(B, _CROP_DTYPE)
-        sizes, off = [], 0
+        sizes, offs, off = [], [], 0
         for i, im in enumerate(images):
             im = im.numpy() if torch.is_tensor(im) else np.asarray(im)
             if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
                 raise _lib.PoseKernelError(f"DeviceCropper: image {i} must be (H,W,3) uint8, got {im.dtype} {im.shape}")
-            desc[i] = (off, im.shape[0], im.shape[1], int(bool(flips[i])) if flips is not None else 0, int(bool(bgr)), invert_affine(matrices[i]))
             sizes.append(im)
+            offs.append(off)
             off += (im.size + 15) // 16 * 16
+        desc = np.zeros(B, _CROP_DTYPE)
+        for i, j in enumerate(src_of):
+            desc[i] = (offs[j], sizes[j].shape[0], sizes[j].shape[1], int(bool(flips[i])) if flips is not None else 0, int(bool(bgr)),
+                       invert_affine(matrices[i]))
         nd, nj = desc.nbytes, 0 if jtab is None else jtab.nbytes
         joff = off + (nd + 15) // 16 * 16
         host, slot = self._staging(joff + (nj + 15) // 16 * 16)         # [images | descriptor table | jitter table]: ONE host-to-device copy
         # plain memcpy through a numpy view: a torch slice assignment fans every 0.9 MB image out over all intra-op threads (128 on the
         # GPU host: 21 ms per 64 images against 1.4 ms; scripts/probes/cropper_phases.py)
         hv = host.numpy()
-        for i, im in enumerate(sizes):
-            o = int(desc[i]["off"])
+        for o, im in zip(offs, sizes):
             np.copyto(hv[o:o + im.size], np.ascontiguousarray(im).reshape(-1))
         np.copyto(hv[off:off + nd], desc.view(np.uint8))
         if nj:

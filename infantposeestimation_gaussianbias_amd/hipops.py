@@ -503,6 +503,44 @@ def heatmap_overlay(images, heatmaps, alpha, lut, want_index=False):
     return index
 
 
+def heatmap_overlay_patches(images, heatmaps, image_index, matrices, alpha, lut, want_index=False, want_cover=False):
+    """One heatmap stack per person, each blended IN PLACE where its crop lies in its frame (pk_heatmap_overlay_patches): images a
+    contiguous (N,H,W,3) uint8 batch, heatmaps (P,K,h,w) fp32, image_index (P,) the frame of each patch, non-decreasing and in [0, N),
+    matrices (P,6) or (P,2,3) float64, frame pixels -> heat-map pixels.  The index and the matrices are checked here, on the host (the
+    kernel trusts them), so they are taken as host data; a device tensor is copied back first.  P = 0 or an empty batch launches
+    nothing.  Returns (index, cover): the (N,H,W) uint8 colour-index plane (0 where uncovered) and the count of covering patches
+    (saturating at 255), each None unless asked for."""
+    if not (isinstance(images, torch.Tensor) and images.is_contiguous()):
+        raise _lib.PoseKernelError("images: expected a contiguous CUDA(HIP) uint8 tensor (drawn in place)")
+    images, heatmaps, lut = _chk_images(images), _chk(heatmaps, name="heatmaps"), _chk(lut, U8, "lut")
+    N, H, W, _ = images.shape
+    if heatmaps.dim() != 4 or tuple(lut.shape) != (256, 3):
+        raise _lib.PoseKernelError(f"heatmap_overlay_patches: heatmaps (P,K,h,w) and a (256,3) lut, got {tuple(heatmaps.shape)}, {tuple(lut.shape)}")
+    P, K, h, w = heatmaps.shape
+    host = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)     # noqa: E731
+    idx, mats = host(image_index).reshape(-1), host(matrices)
+    if idx.size != P or mats.size != 6 * P:
+        raise _lib.PoseKernelError(f"heatmap_overlay_patches: {P} patches need image_index ({P},) and matrices ({P},6), got {idx.shape}, {mats.shape}")
+    if idx.size and idx.dtype.kind not in "iu":
+        raise _lib.PoseKernelError(f"heatmap_overlay_patches: image_index must be integer, got {idx.dtype}")
+    idx, mats = idx.astype(np.int64), np.ascontiguousarray(mats, np.float64).reshape(P, 6)
+    if P and (idx.min() < 0 or idx.max() >= N or np.any(np.diff(idx) < 0)):
+        raise _lib.PoseKernelError(f"heatmap_overlay_patches: image_index must be non-decreasing with every entry in [0, {N}), got {idx.tolist()}")
+    if not np.all(np.isfinite(mats)):
+        raise _lib.PoseKernelError("heatmap_overlay_patches: a matrix entry is not finite")
+    launch = N * H * W > 0 and P > 0
+    plane = torch.empty if launch else torch.zeros         # the kernel writes every pixel of both planes
+    index = plane(N, H, W, dtype=U8, device=images.device) if want_index else None
+    cover = plane(N, H, W, dtype=U8, device=images.device) if want_cover else None
+    if not launch:
+        return index, cover
+    n_ws = _lib.lib.pk_heatmap_overlay_patches_ws_floats(P, K, h, w)
+    ws = torch.empty(max(1, n_ws), dtype=F32, device=images.device)
+    call("pk_heatmap_overlay_patches", images, heatmaps, torch.from_numpy(idx.astype(np.int32)).to(images.device),
+         torch.from_numpy(mats).to(images.device), float(alpha), lut, index, cover, ws, N, P, K, h, w, H, W, stream_ptr())
+    return index, cover
+
+
 # ------------------------------------------------------------------------------------------------ optimiser
 def adamw_step(param, grad, exp_avg, exp_avg_sq, flags, param_bf16, lr_dev, step_dev, beta1, beta2, eps, weight_decay, grad_scale=1.0):
     call("pk_adamw_step", param, grad, exp_avg, exp_avg_sq, flags, param_bf16, param.numel(), lr_dev, step_dev, float(beta1), float(beta2),

@@ -2,8 +2,9 @@
 from .metrics import AverageMeter, COCOEvaluator, MetricLogger
 from . import postprocess
 from . import visualization
-from .visualization import (COCO_COLORS, COCO_SKELETON, create_grid_image, draw_bbox, draw_heatmaps, draw_poses, draw_skeleton,
-                            save_visualization)
+from .visualization import (COCO_COLORS, COCO_SKELETON, create_grid_image, draw_bbox, draw_heatmaps, draw_person_heatmaps, draw_poses,
+                            draw_skeleton, save_person_visualization, save_visualization)
 
 __all__ = ['AverageMeter', 'COCOEvaluator', 'MetricLogger', 'postprocess', 'visualization', 'draw_skeleton', 'draw_heatmaps', 'draw_bbox',
-           'draw_poses', 'create_grid_image', 'save_visualization', 'COCO_SKELETON', 'COCO_COLORS']
+           'draw_poses', 'draw_person_heatmaps', 'create_grid_image', 'save_visualization', 'save_person_visualization', 'COCO_SKELETON',
+           'COCO_COLORS']

@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from .. import _lib, hipops
+from ..datasets.transforms import get_affine_matrix
 
 _JOINTS = ("nose", "left_eye", "right_eye", "left_ear", "right_ear", "left_shoulder", "right_shoulder", "left_elbow", "right_elbow",
            "left_wrist", "right_wrist", "left_hip", "right_hip", "left_knee", "right_knee", "left_ankle", "right_ankle")
@@ -102,7 +103,7 @@ def _check_sizes(point_radius=0, line_thickness=1, thickness=1):
 def draw_poses(images, keypoints, scores, image_index, boxes=None, box_image_index=None, heatmaps=None, score_threshold: float = 0.3,
                skeleton: Sequence[Tuple[int, int]] = COCO_SKELETON, colors: Sequence[Tuple[int, int, int]] = COCO_COLORS,
                point_radius: int = 4, line_thickness: int = 2, box_color: Tuple[int, int, int] = (0, 255, 0), box_thickness: int = 2,
-               alpha: float = 0.5):
+               alpha: float = 0.5, heatmap_centers=None, heatmap_scales=None, heatmap_rotations=None, heatmap_image_index=None):
     """Batched overlays for served / video use: (N, H, W, 3) uint8 frames of one size -> a new batch with everything drawn.
 
     keypoints (P, K, 2) image pixels, scores (P, K) or None (all drawn), image_index (P,) non-decreasing frame of each pose: several
@@ -110,19 +111,33 @@ def draw_poses(images, keypoints, scores, image_index, boxes=None, box_image_ind
     stack per frame.  One overlay launch (if heatmaps are given) and one shape launch for the whole batch; per frame the heatmap goes
     underneath, then boxes in index order, then the poses in index order (limbs in table order, then joints: disc and white ring).
     Limbs naming a joint >= K are skipped and the palette wraps, so K = 13 works with the COCO tables.
+
+    With `heatmap_centers` and `heatmap_scales` (P', 2) the heatmaps are per person instead: (P', K', h, w), each laid where its crop
+    (center, scale, `heatmap_rotations` degrees, default 0) lies in frame `heatmap_image_index` (default: the poses' `image_index`), as
+    `draw_person_heatmaps` does; still underneath boxes and poses.
     """
     batch, restore = _images_in(images)
+    patches = None
+    if heatmap_centers is not None or heatmap_scales is not None:
+        if heatmaps is None or heatmap_centers is None or heatmap_scales is None:
+            raise ValueError("draw_poses: per-person heatmaps need heatmaps, heatmap_centers and heatmap_scales together")
+        if heatmap_image_index is None and keypoints is not None:
+            heatmap_image_index = image_index                 # one stack per pose, in the order of the poses
+        patches = (heatmap_centers, heatmap_scales, heatmap_rotations, heatmap_image_index)
     _draw_into(batch, keypoints, scores, image_index, boxes, box_image_index, heatmaps, score_threshold, skeleton, colors, point_radius,
-               line_thickness, box_color, box_thickness, alpha)
+               line_thickness, box_color, box_thickness, alpha, patches)
     return restore(batch)
 
 
 def _draw_into(batch, keypoints, scores, image_index, boxes=None, box_image_index=None, heatmaps=None, score_threshold=0.3,
-               skeleton=COCO_SKELETON, colors=COCO_COLORS, point_radius=4, line_thickness=2, box_color=(0, 255, 0), box_thickness=2, alpha=0.5):
+               skeleton=COCO_SKELETON, colors=COCO_COLORS, point_radius=4, line_thickness=2, box_color=(0, 255, 0), box_thickness=2, alpha=0.5,
+               patches=None):
     """draw_poses on a batch this module owns (a fresh copy of the caller's images), in place."""
     _check_sizes(point_radius, line_thickness, box_thickness)
     dev = batch.device
-    if heatmaps is not None:
+    if patches is not None:
+        _patches_into(batch, heatmaps, alpha, *patches)
+    elif heatmaps is not None:
         hm = _dev(heatmaps, torch.float32, dev)
         hipops.heatmap_overlay(batch, hm[None] if hm.dim() == 3 else hm, alpha, _table("lut", heatmap_lut(), np.uint8, dev))
     kp = sc = idx = bx = bidx = None
@@ -161,6 +176,50 @@ def draw_heatmaps(img, heatmaps, alpha: float = 0.5):
     hm = _dev(heatmaps, torch.float32, dev)
     hm = hm[None] if hm.dim() == 3 else hm
     hipops.heatmap_overlay(batch, hm, alpha, _table("lut", heatmap_lut(), np.uint8, dev))
+    return restore(batch)
+
+
+def crop_heatmap_matrices(centers, scales, heatmap_size, rotations=None) -> np.ndarray:
+    """(P, 2, 3) float64 maps from image pixels to heat-map pixels of the crops (center, scale, rotation in degrees): the crop matrix
+    with the heat-map size (w, h) as its output size.  Heat pixel x is input pixel x w_in / w -- the decode's convention, not the
+    half-pixel one -- so this equals diag(w / w_in, h / h_in) times the crop matrix the network's input was cut with."""
+    c, s = np.asarray(centers, np.float64).reshape(-1, 2), np.asarray(scales, np.float64).reshape(-1, 2)
+    r = np.zeros(len(c)) if rotations is None else np.asarray(rotations, np.float64).reshape(-1)
+    if not (len(c) == len(s) == len(r)):
+        raise ValueError(f"crop_heatmap_matrices: {len(c)} centers, {len(s)} scales, {len(r)} rotations")
+    return np.stack([get_affine_matrix(c[i], s[i], heatmap_size, r[i]) for i in range(len(c))]) if len(c) else np.zeros((0, 2, 3))
+
+
+def _patches_into(batch, heatmaps, alpha, centers=None, scales=None, rotations=None, image_index=None, matrices=None):
+    """Per-person heatmaps blended into a batch this module owns, in place (hipops.heatmap_overlay_patches)."""
+    dev = batch.device
+    hm = _dev(heatmaps, torch.float32, dev)
+    hm = hm[None] if hm.dim() == 3 else hm
+    if hm.dim() != 4:
+        raise ValueError(f"heatmaps: expected (P, K, h, w), or (K, h, w) for one person, got {tuple(hm.shape)}")
+    P = int(hm.shape[0])
+    if matrices is None:
+        if centers is None or scales is None:
+            raise ValueError("per-person heatmaps need centers and scales, or matrices")
+        matrices = crop_heatmap_matrices(centers, scales, (int(hm.shape[3]), int(hm.shape[2])), rotations)
+    elif centers is not None or scales is not None or rotations is not None:
+        raise ValueError("per-person heatmaps take centers / scales / rotations or matrices, not both")
+    if image_index is None:
+        if batch.shape[0] != 1:
+            raise ValueError("per-person heatmaps on a batch of frames need image_index")
+        image_index = np.zeros(P, np.int32)
+    hipops.heatmap_overlay_patches(batch, hm, image_index, matrices, alpha, _table("lut", heatmap_lut(), np.uint8, dev))
+
+
+def draw_person_heatmaps(img, heatmaps, centers=None, scales=None, rotations=None, image_index=None, matrices=None, alpha: float = 0.5):
+    """Overlay each person's heatmaps where that person's crop lies in the frame (top-down use; rule: DESIGN.md, "Heatmaps where the crop
+    lies").  heatmaps (P, K, h, w), or (K, h, w) for one person; the crops as `centers` / `scales` (P, 2) with optional `rotations` (P,)
+    in degrees -- what the network's input was cut with -- or directly as `matrices` (P, 2, 3), image pixels -> heat-map pixels.  A
+    batch (N, H, W, 3) needs `image_index` (P,), the non-decreasing frame of each person.  Each stack is reduced to its maximum over K
+    and normalised to its own range; where persons overlap the larger value wins, whatever their order; pixels outside every crop keep
+    their bytes.  Returns a new image.  (`draw_heatmaps` keeps the reference's signature and stretches one stack over the frame.)"""
+    batch, restore = _images_in(img)
+    _patches_into(batch, heatmaps, alpha, centers, scales, rotations, image_index, matrices)
     return restore(batch)
 
 
@@ -213,6 +272,18 @@ def save_visualization(img, output_path: str, keypoints=None, scores=None, heatm
         result = draw_bbox(result, bbox)
     if heatmaps is not None:
         result = draw_heatmaps(result, heatmaps, alpha=0.3)
+    if keypoints is not None:
+        result = draw_skeleton(result, keypoints, scores)
+    write_image(result, output_path)
+
+
+def save_person_visualization(img, output_path: str, keypoints=None, scores=None, heatmaps=None, bbox=None, center=None, scale=None):
+    """`save_visualization` for a person whose box is not the whole image: the heatmaps go where the crop (center, scale) lies."""
+    result = _images_in(img)[0][0]
+    if bbox is not None:
+        result = draw_bbox(result, bbox)
+    if heatmaps is not None:
+        result = draw_person_heatmaps(result, heatmaps, centers=center, scales=scale, alpha=0.3)
     if keypoints is not None:
         result = draw_skeleton(result, keypoints, scores)
     write_image(result, output_path)

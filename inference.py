@@ -7,7 +7,8 @@ mean/std normalisation of inference.py:64-110 are ONE kernel per batch (pk_affin
 as restated in oracle/warp.py), the model's flip-test inference and decode follow (PoseEstimator.inference), and the heat-px -> image
 mapping of inference.py:142-175 is one kernel (pk_affine_coords).  `predict_batch` really batches (the reference loops over predict).
 Visualisation is on the device too: `visualize` / `visualize_batch` draw through utils/visualization.py (pk_draw_shapes,
-pk_heatmap_overlay: this project's own integer rasterisation rule, not OpenCV's pixels) and files are written with Pillow.
+pk_heatmap_overlay, pk_heatmap_overlay_patches: this project's own integer rasterisation rule, not OpenCV's pixels) and files are written
+with Pillow.
 """
 import argparse
 import os
@@ -86,6 +87,29 @@ class PoseInference:
         return [(kp_img[i], sc[i]) for i in range(len(imgs))]
 
     @torch.no_grad()
+    def predict_persons(self, img: np.ndarray, bboxes: List[np.ndarray], return_heatmaps: bool = False):
+        """Every person of ONE image: the image is staged and uploaded once and all crops read it (`DeviceCropper(image_index=)`;
+        `predict_batch([img] * len(bboxes), bboxes)` sends it once per person and gives the same numbers).  -> the per-person
+        [(keypoints, scores)]; with `return_heatmaps` also the heatmaps (P, K, h, w) of the un-flipped pass (one more forward) and the
+        centers and scales (P, 2) of the crops, which is what `visualize_batch(heatmaps=, heatmap_centers=, heatmap_scales=)` takes."""
+        if len(bboxes) == 0:
+            raise ValueError("predict_persons: no boxes")
+        cs = [self._center_scale(img, bb) for bb in bboxes]
+        mats = [get_affine_matrix(c, s, self.input_size, 0) for c, s in cs]
+        x, _ = self._crop([img], mats, None, bgr=True, image_index=[0] * len(bboxes))
+        centers, scales = np.stack([c for c, _ in cs]), np.stack([s for _, s in cs])
+        if self.flip_test:
+            kp, sc = self.model.inference(x, flip=True, flip_pairs=self.flip_pairs)
+        else:
+            kp, sc = self.model.inference(x, flip=False)
+        kp_img, _ = self.postprocess(kp, sc, centers, scales)
+        sc = sc.cpu().numpy()
+        results = [(kp_img[i], sc[i]) for i in range(len(bboxes))]
+        if not return_heatmaps:
+            return results
+        return results, self.model(x)['heatmaps'].float(), centers, scales
+
+    @torch.no_grad()
     def predict(self, img: np.ndarray, bbox: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
         return self.predict_batch([img], [bbox])[0]
 
@@ -97,11 +121,14 @@ class PoseInference:
             write_image(vis, output_path)
         return vis
 
-    def visualize_batch(self, imgs, results, bboxes=None, heatmaps=None, score_threshold: float = 0.3):
+    def visualize_batch(self, imgs, results, bboxes=None, heatmaps=None, score_threshold: float = 0.3, heatmap_centers=None,
+                        heatmap_scales=None):
         """Overlays for a batch of same-sized frames in one heatmap launch (if given) and one shape launch (draw_poses).
 
         imgs: list of (H, W, 3) BGR uint8 arrays, or one (N, H, W, 3) array / device tensor.  results[i]: the (keypoints, scores) of frame
-        i, or a list of such pairs for several persons.  bboxes[i]: None, one (x1, y1, x2, y2) or a list of them.  heatmaps: (N, K, h, w).
+        i, or a list of such pairs for several persons.  bboxes[i]: None, one (x1, y1, x2, y2) or a list of them.  heatmaps: (N, K, h, w),
+        one stack stretched over each frame; with `heatmap_centers` / `heatmap_scales` (P, 2) instead (P, K, h, w), one stack per person
+        in the order of `results`, each drawn where its crop lies (`predict_persons(..., return_heatmaps=True)` returns all three).
         Returns a list of arrays for a list, else the batch in the kind it came in."""
         as_list = isinstance(imgs, (list, tuple))
         batch = np.stack(imgs) if as_list else imgs
@@ -117,7 +144,8 @@ class PoseInference:
                     boxes.append(b)
                     bidx.append(i)
         out = draw_poses(batch, np.stack(kps) if kps else None, np.stack(scs) if kps else None, idx, boxes=np.stack(boxes) if boxes else None,
-                         box_image_index=bidx, heatmaps=heatmaps, score_threshold=score_threshold, alpha=0.3)
+                         box_image_index=bidx, heatmaps=heatmaps, score_threshold=score_threshold, alpha=0.3,
+                         heatmap_centers=heatmap_centers, heatmap_scales=heatmap_scales)
         return list(out) if as_list else out
 
 
@@ -133,23 +161,22 @@ def main(args):
     rgb = np.asarray(Image.open(args.input).convert("RGB"))
     img = rgb[:, :, ::-1].copy()                          # the reference hands BGR (cv2.imread) to PoseInference
     bboxes = [np.array(args.bbox)] if args.bbox else detect_persons(img)
+    whole = len(bboxes) == 1 and np.array_equal(np.asarray(bboxes[0], np.float64), [0, 0, img.shape[1], img.shape[0]])
+    want_hm = bool(args.output and args.draw_heatmaps)
     t0 = time.time()
-    results = pose.predict_batch([img] * len(bboxes), bboxes)
+    out = pose.predict_persons(img, bboxes, return_heatmaps=want_hm)
+    results, heatmaps, centers, scales = out if want_hm else (out, None, None, None)
     print(f'Inference time: {(time.time() - t0) * 1000:.2f} ms')
     for kp, sc in results:
         for k, ((x, y), s) in enumerate(zip(kp, sc)):
             print(f'  kpt {k:2d}: ({x:8.2f}, {y:8.2f})  score {s:.3f}')
     if args.output:
-        # inference.py:296-300 of the reference: draw and save -- here every person of the image in one call
-        heatmaps = None
-        if args.draw_heatmaps:
-            if len(bboxes) == 1 and np.array_equal(np.asarray(bboxes[0], np.float64), [0, 0, img.shape[1], img.shape[0]]):
-                with torch.no_grad():
-                    heatmaps = pose.model(pose.preprocess(img, bboxes[0])[0])['heatmaps'].float()
-            else:
-                print('--draw_heatmaps: skipped (only drawn for a single whole-image box)')
+        # inference.py:296-300 of the reference: draw and save -- here every person of the image in one call.  A single whole-image box
+        # keeps the reference's picture (the map stretched over the image); real person boxes get each map where its crop lies.
+        if whole:
+            centers = scales = None
         vis = pose.visualize_batch(img[None], [results], bboxes=[bboxes] if args.draw_bbox else None, heatmaps=heatmaps,
-                                   score_threshold=args.threshold)[0]
+                                   score_threshold=args.threshold, heatmap_centers=centers, heatmap_scales=scales)[0]
         write_image(vis, args.output)
         print(f'Result saved to: {args.output}')
 
@@ -166,7 +193,6 @@ if __name__ == '__main__':
     p.add_argument('--config', type=str, default=None)
     p.add_argument('--draw_bbox', action='store_true', help='also draw the person boxes into --output')
     p.add_argument('--draw_heatmaps', action='store_true',
-                   help='also overlay the predicted heatmaps (alpha 0.3) into --output; only for a single whole-image box, where the '
-                        'model crop and the image coincide up to the crop\'s affine map (the map is stretched over the image, as the '
-                        'reference does); skipped with a message otherwise')
+                   help='also overlay the predicted heatmaps (alpha 0.3) into --output: each person\'s map where that person\'s crop lies in '
+                        'the image; for a single whole-image box the map is stretched over the image, as the reference does')
     main(p.parse_args())
