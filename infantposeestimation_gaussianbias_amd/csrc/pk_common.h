@@ -12,6 +12,12 @@
 
 #define PK_WAVE 64
 
+// MFMA operand / accumulator registers and 16-byte memory words, as the implicit-GEMM and weight-gradient units (pk_igemm.hip, pk_wgrad.hip) use them
+typedef __attribute__((ext_vector_type(8))) short bf16x8;
+typedef __attribute__((ext_vector_type(4))) float f32x4;
+typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
+#define OOB_OFF 0x80000000u      // buffer-load offset beyond num_records: the hardware returns zeros
+
 void pk_set_error(const char* fmt, ...);
 
 #define PK_REQUIRE(cond, ...)          \

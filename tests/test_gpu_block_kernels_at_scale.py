@@ -1,5 +1,5 @@
 """GPU tests (`-m gpu`) of the transformer-block kernels (csrc/pk_block.hip, csrc/pk_attn.hip, the weight-gradient and slab-reduction
-kernels of csrc/pk_igemm.hip) at the window and row counts training runs.
+kernels of csrc/pk_wgrad.hip) at the window and row counts training runs.
 
 The block kernels are persistent: the release build caps every grid at a compile-time constant and each wave (or workgroup) walks
 several windows / 32-row groups in a grid-stride loop, carrying register accumulators and LDS from one item to the next.  Only a
