@@ -392,7 +392,7 @@ class Trainer:
 
     # -- eager path --------------------------------------------------------------------------------------------
     def _fwd_bwd(self, batch):
-        nnops._PENDING.clear()         # reductions registered by a step that did not finish (exception) must not leak into this one
+        nnops.discard_deferred()       # reductions registered by a step that did not finish (exception) must not leak into this one
         self.opt.zero_grad()
         # the device input pipeline hands over the stem's own layout (bf16 NHWC, 8-channel pixels): no conversion launch
         x = batch["img_nhwc8"] if batch.get("img_nhwc8") is not None else batch["img"]
@@ -455,7 +455,7 @@ class Trainer:
                 self.comm._pending.clear()
                 for bk in self.comm.buckets:
                     bk["got"] = 0
-                nnops._PENDING.clear()
+                nnops.discard_deferred()
                 continue
             finally:
                 self.comm.suspended = False

@@ -214,18 +214,15 @@ class _Unit(torch.autograd.Function):
                 Bq, Ho, Wo, Cout = raws[k].shape
                 M = Bq * Ho * Wo
                 g_p, b_p = params[3 * k + 1], params[3 * k + 2]
-                (dgamma, sg), (dbeta, sb) = nnops._sink(g_p), nnops._sink(b_p)
-                if not sg:
-                    grads[3 * k + 1] = dgamma
-                if not sb:
-                    grads[3 * k + 2] = dbeta
+                dgamma, dbeta = nnops._Dest(g_p), nnops._Dest(b_p)
+                grads[3 * k + 1], grads[3 * k + 2] = dgamma.grad(), dbeta.grad()
                 nb = _lib.lib.pk_bn_bwd_group_blocks(M)
                 part = nnops._e((nb, 2, Cout), F32, dev)
                 draws[k] = nnops._e(tuple(raws[k].shape), BF16, dev)
                 keep.append(part)
                 bits = masks[k] if (mask is not None and mask is ys[k]) else None      # the step's own ReLU: its bit mask instead of y
                 bn_rows.append(dict(dy=_p(dy), y_act=0 if bits is not None else _p(mask), raw=_p(raws[k]), save_mean=_p(means[k]),
-                                    save_rstd=_p(rstds[k]), gamma=_p(g_p), partial=_p(part), dgamma=_p(dgamma), dbeta=_p(dbeta), dx=_p(draws[k]),
+                                    save_rstd=_p(rstds[k]), gamma=_p(g_p), partial=_p(part), dgamma=_p(dgamma.t), dbeta=_p(dbeta.t), dx=_p(draws[k]),
                                     relu_mask=_p(bits), rows=M, C=Cout, relu=1 if mask is not None else 0))
             _launch("pk_bn_bwd_group", BNB_DT, bn_rows)
             plain, dil, wg1, wg3, single = [], [], [], [], []
@@ -241,26 +238,25 @@ class _Unit(torch.autograd.Function):
                     contrib[l.j].append(dx)
                 else:
                     dys[l.prev] = (dx, ys[l.prev])       # the previous chain step ends in a ReLU of its own
-                w_p = params[3 * k]
-                dst, sw = nnops._sink(w_p)
-                if sw and nnops.deferral_enabled():
+                dw = nnops._Dest(params[3 * k])
+                if nnops._deferrable(dw):
                     S = _lib.lib.pk_wgrad_group_slices(Bq * Ho * Wo, Cout, Cin, ks, stride)
                     total = Cout * ks * ks * Cin
-                    ws = nnops._workspace(dst, "wg", S * total)
+                    ws = nnops._workspace(dw.t, "wg", S * total)
                     (wg3 if stride == 2 else wg1).append(dict(x=_p(xin), grad_out=_p(draws[k]), workspace=_p(ws), B=Bq, Hs=Hs, Ws=Ws, Ho=Ho, Wo=Wo,
                                                               N=Cout, Cin=Cin, ksize=ks, stride=stride))
-                    nnops._defer(ws.data_ptr(), dst, total, S, total, 1, Cout, ks * ks, Cin)
+                    nnops._reduce([nnops._row((ws, 0), (dw.t, 0), total, S, total, layout=1, N=Cout, T=ks * ks, Cin=Cin)], True)
                 else:
-                    single.append((k, xin, Cout, Cin, ks, stride, (Bq, Hs, Ws, Ho, Wo), dst, sw))
+                    single.append((k, xin, Cout, Cin, ks, stride, (Bq, Hs, Ws, Ho, Wo), dw))
             for grp in (plain, dil):
                 if grp:
                     _launch("pk_conv2d_group", CONV_DT, grp)
             for grp in (wg1, wg3):
                 if grp:
                     _launch("pk_wgrad_group", WG_DT, grp)
-            for k, xin, Cout, Cin, ks, stride, geom, dst, sw in single:      # no gradient sink (plain autograd): the per-layer kernel + its reduce
-                dw = nnops._wgrad(xin, draws[k], Cout, Cin, ks, stride, geom, out=dst, deferred=False)
-                grads[3 * k] = None if sw else dw
+            for k, xin, Cout, Cin, ks, stride, geom, dw in single:      # no gradient sink (plain autograd): the per-layer kernel + its reduce
+                nnops._wgrad(xin, draws[k], Cout, Cin, ks, stride, geom, out=dw.t)
+                grads[3 * k] = dw.grad()
         # 3. input gradients: identity route (masked by the sum's ReLU) + the data gradients of the routes that start at x_j
         dxs, rows = [None] * n, []
         for j in range(n):

@@ -30,6 +30,19 @@ def _e(shape, dtype, dev):
     return torch.empty(shape, dtype=dtype, device=dev)
 
 
+# Optional per-sample DropPath scale of a block half: fp32 for the kernels, an empty tensor in save_for_backward when there is none.
+def _scale(s):
+    return None if s is None else s.float().contiguous()
+
+
+def _stash(s, like):
+    return s if s is not None else like.new_empty(0)
+
+
+def _unstash(s):
+    return s if s.numel() else None
+
+
 # Gradient sink: a parameter may carry `_pk_grad_sink`, an fp32 view of the engine's flat gradient buffer.  Backward kernels
 # then store that parameter's gradient THERE (plain store: every parameter is used once per step) and hand None to autograd,
 # which removes ~800 `grad += g` launches per step.  Set by engine.FlatAdamW(direct_grads=True); absent = ordinary autograd.
@@ -62,12 +75,21 @@ def grad_sink_of(param):
     return dst
 
 
-def _sink(param):
-    """-> (destination tensor, direct?) for the gradient of `param`."""
-    dst = grad_sink_of(param)
-    if dst is not None:
-        return dst, True
-    return _e(tuple(param.shape), F32, param.device), False
+class _Dest:
+    """Where one parameter's gradient goes.  `t` is the fp32 tensor the kernels write: the parameter's gradient sink (`direct`: autograd
+    gets None) or a fresh tensor that is handed to autograd.  `param=None`: a fresh tensor of `shape` that no parameter owns, or, without
+    a shape, a gradient nobody wants: nothing to write, nothing for autograd, and no reason to reduce anything now."""
+    __slots__ = ("t", "direct")
+
+    def __init__(self, param, shape=None, dev=None):
+        self.t = None if param is None else grad_sink_of(param)
+        self.direct = self.t is not None or (param is None and shape is None)
+        if not self.direct:
+            self.t = _e(tuple(param.shape), F32, param.device) if param is not None else _e(shape, F32, dev)
+
+    def grad(self):
+        """What autograd gets for this parameter."""
+        return None if self.direct else self.t
 
 
 def _up8(n):
@@ -87,13 +109,21 @@ _TABLES = {}            # key (tuple of rows) -> device table; never evicted: a 
 
 
 def deferral_enabled():
-    import os
     return os.environ.get("POSE_DEFER_REDUCE", "1") != "0"
 
 
-def _workspace(sink, tag, numel):
-    """Persistent fp32 workspace attached to the gradient-sink tensor it serves (lives and dies with the model's gradient
-    buffer, so a captured hipGraph can keep its pointer).  `freeze_workspaces` marks them after a capture."""
+def _deferrable(*dests):
+    """True when the reductions into these destinations can wait for finalize_deferred(): all are gradient sinks, so nothing
+    downstream in backward (autograd included) reads them."""
+    return all(d.direct for d in dests) and deferral_enabled()
+
+
+def _workspace(sink, tag, numel, deferred=True):
+    """fp32 room for partial sums.  When their reduction is deferred: the persistent workspace `tag` attached to the gradient-sink
+    tensor it serves (lives and dies with the model's gradient buffer, so a captured hipGraph can keep its pointer;
+    `freeze_workspaces` marks them after a capture).  Otherwise a throw-away tensor."""
+    if not deferred:
+        return _e((numel,), F32, sink.device)
     d = getattr(sink, "_pk_ws", None)
     if d is None:
         d = sink._pk_ws = {}
@@ -119,21 +149,41 @@ def freeze_workspaces(model):
                 sk._pk_ws_frozen = True
 
 
-def _defer(part_ptr, out, slab_stride, S, K, layout=0, N=0, T=1, Cin=1, out_stride=1, out_offset=0):
-    _PENDING.append((part_ptr, out.data_ptr() + 4 * out_offset, slab_stride, S, K, layout, N, T, Cin, out_stride, 0))
+def _row(part, out, stride, S, K, *, layout=0, N=0, T=1, Cin=1, ostride=1):
+    """One pk_reduce_many row (fields of _REDUCE_DTYPE): sum S slabs of K floats, `stride` floats apart; `part` and `out` are
+    (fp32 tensor, offset in floats)."""
+    return (part[0].data_ptr() + 4 * part[1], out[0].data_ptr() + 4 * out[1], stride, S, K, layout, N, T, Cin, ostride, 0)
+
+
+def _block_table(sizes, per_block, dev):
+    """Work list of a launch over several descriptors: descriptor i gets ceil(sizes[i] / per_block) workgroups.
+    -> (descriptor of each workgroup, first workgroup of that descriptor, number of workgroups)."""
+    blk_desc, blk_first, nb = [], [], 0
+    for i, n in enumerate(sizes):
+        k = -(-n // per_block)
+        blk_desc += [i] * k
+        blk_first += [nb] * k
+        nb += k
+    return torch.tensor(blk_desc, dtype=I32, device=dev), torch.tensor(blk_first, dtype=I32, device=dev), nb
 
 
 def _reduce_table(key, dev):
     desc = np.array(list(key), dtype=_REDUCE_DTYPE)
-    blk_desc, blk_first, nb = [], [], 0
-    cols = _lib.lib.pk_reduce_many_cols()
-    for i, r in enumerate(key):
-        k = -(-r[4] // cols)
-        blk_desc += [i] * k
-        blk_first += [nb] * k
-        nb += k
-    return dict(desc=torch.from_numpy(desc.view(np.uint8)).to(dev), nb=nb, blk_desc=torch.tensor(blk_desc, dtype=I32, device=dev),
-                blk_first=torch.tensor(blk_first, dtype=I32, device=dev))
+    blk_desc, blk_first, nb = _block_table([r[4] for r in key], _lib.lib.pk_reduce_many_cols(), dev)
+    return dict(desc=torch.from_numpy(desc.view(np.uint8)).to(dev), nb=nb, blk_desc=blk_desc, blk_first=blk_first)
+
+
+def _reduce(rows, deferred, dev=None):
+    """Slab sums into gradient sinks wait for finalize_deferred(); those whose destinations are ordinary tensors (read by autograd
+    right after backward returns) are summed now, by one uncached pk_reduce_many launch on `dev`."""
+    if deferred:
+        _PENDING.extend(rows)
+        return
+    tab = _reduce_table(tuple(rows), dev)
+    call("pk_reduce_many", tab["desc"], tab["blk_desc"], tab["blk_first"], tab["nb"], stream_ptr())
+    for t in tab.values():                      # keep the table alive until the launch has consumed it
+        if torch.is_tensor(t):
+            t.record_stream(torch.cuda.current_stream())
 
 
 def finalize_deferred():
@@ -151,13 +201,9 @@ def finalize_deferred():
     call("pk_reduce_many", tab["desc"], tab["blk_desc"], tab["blk_first"], tab["nb"], stream_ptr())
 
 
-def _reduce_now(rows, dev):
-    """Slab sums whose destinations are ordinary tensors (no gradient sink): one uncached pk_reduce_many launch."""
-    tab = _reduce_table(tuple(rows), dev)
-    call("pk_reduce_many", tab["desc"], tab["blk_desc"], tab["blk_first"], tab["nb"], stream_ptr())
-    for t in tab.values():                      # keep the table alive until the launch has consumed it
-        if torch.is_tensor(t):
-            t.record_stream(torch.cuda.current_stream())
+def discard_deferred():
+    """Forget the rows of a step that did not finish (an exception, an abandoned hipGraph capture): they must not leak into the next."""
+    _PENDING.clear()
 
 
 # ================================================================================================ backward milestones
@@ -242,16 +288,8 @@ class WeightCache:
         if self.flat is None or self.flat.numel() != off or self.flat.device != dev:
             self.flat = torch.empty(off, dtype=BF16, device=dev)
         desc = np.array(rows, dtype=_PACK_DTYPE)
-        blk_desc, blk_first, nb = [], [], 0
-        for i, r in enumerate(rows):
-            k = -(-r[8] // 1024)
-            blk_desc += [i] * k
-            blk_first += [nb] * k
-            nb += k
         self._desc = torch.from_numpy(desc.view(np.uint8)).to(dev)
-        self._blk_desc = torch.tensor(blk_desc, dtype=I32, device=dev)
-        self._blk_first = torch.tensor(blk_first, dtype=I32, device=dev)
-        self._nb = nb
+        self._blk_desc, self._blk_first, self._nb = _block_table([r[8] for r in rows], 1024, dev)
         for kind, w, o, shape in layout:
             view = self.flat[o:o + shape[0] * shape[1] * shape[2]].view(shape)
             (self.fwd if kind == "f" else self.dgrad)[id(w)] = view
@@ -342,12 +380,13 @@ def _conv_dgrad(g, wd, Cin, ksize, stride, in_hw, addend=None):
 
 
 def _wgrad(x, g, N, Cin, ksize, stride, geom, a_map=None, g_map=None, g_scale=None, g_rps=0, M=None, oihw=True, out=None,
-           dbias=None, deferred=False, win=None):
+           dbias=None, deferred=False, win=None, n_real=None):
     """-> fp32 gradient (N, Cin, k, k) for conv (geom=(B,Hs,Ws,Ho,Wo)) or (N, Cin) for linear (geom=None); `out` = destination.
     `dbias` (fp32, <= N entries) additionally receives the bias gradient (column sums of the same scaled/gathered rows).
     `win=(B, H, W)`: the row maps are nnops.window_rowmap(B, H, W) (lets the library take its streaming kernel, which recomputes the map).
-    `deferred=True` (only when every output is a gradient sink, i.e. nothing downstream in backward reads the result): only the
-    split-M slabs are written here, their reduction is postponed to finalize_deferred()."""
+    `deferred=True` (only when every output is a gradient sink, see _deferrable): only the split-M slabs are written here, into the
+    persistent workspace of `out`; their reduction is postponed to finalize_deferred().  There `n_real` (1x1 only) sums just the
+    first n_real of the N rows into `out`: N is an 8-aligned row count, `out` and `dbias` hold the real rows."""
     T = ksize * ksize
     if geom is None:
         B = Hs = Ws = Ho = Wo = 0
@@ -360,21 +399,28 @@ def _wgrad(x, g, N, Cin, ksize, stride, geom, a_map=None, g_map=None, g_scale=No
     S = _lib.lib.pk_wgrad_slices(M, N, Cin, ksize, stride, Hs, Ws, flags)
     layout = 1 if (geom is not None and oihw) else 0
     n_bias = 0 if dbias is None else dbias.numel()
-    if deferred and out is not None and deferral_enabled():
-        # slabs into a persistent workspace, reduction postponed to finalize_deferred()
-        ws = _workspace(out, "w", S * N * (T * Cin + 1))
-        call("pk_wgrad_bf16", x, g, ws, None, None, n_bias, a_map, g_map, g_scale, g_rps, M, N, Cin, ksize, stride, B, Hs, Ws, Ho, Wo,
-             layout, stream_ptr())
-        total = N * T * Cin
-        _defer(ws.data_ptr(), out, total, S, total, layout, N, T, Cin)
-        if n_bias:
-            _defer(ws.data_ptr() + 4 * S * total, dbias, N, S, n_bias)
-        return out
-    ws = _e((S * N * (T * Cin + 1),), F32, x.device)
+    deferred = deferred and out is not None
+    total = N * T * Cin
     dw = out if out is not None else _e((N, Cin, ksize, ksize) if geom is not None else (N, Cin), F32, x.device)
-    call("pk_wgrad_bf16", x, g, ws, dw, dbias, n_bias, a_map, g_map, g_scale, g_rps, M, N, Cin, ksize,
-         stride, B, Hs, Ws, Ho, Wo, layout, stream_ptr())
+    ws = _workspace(dw, "w", S * (total + N), deferred)
+    call("pk_wgrad_bf16", x, g, ws, None if deferred else dw, None if deferred else dbias, n_bias, a_map, g_map, g_scale, g_rps, M, N, Cin,
+         ksize, stride, B, Hs, Ws, Ho, Wo, layout, stream_ptr())
+    if deferred:
+        if n_real is None:
+            rows = [_row((ws, 0), (out, 0), total, S, total, layout=layout, N=N, T=T, Cin=Cin)]
+        else:
+            rows = [_row((ws, 0), (out, 0), total, S, n_real * Cin)]
+        if n_bias:
+            rows.append(_row((ws, S * total), (dbias, 0), N, S, n_bias))
+        _reduce(rows, True)
     return dw
+
+
+def _linear_wgrad(w_param, b_param, x, g, N, Cin, **kw):
+    """Weight and bias gradient of a linear layer, each into its destination -> what autograd gets for the two."""
+    dw, db = _Dest(w_param), _Dest(b_param)
+    _wgrad(x, g, N, Cin, 1, 1, None, out=dw.t, dbias=db.t, deferred=_deferrable(dw, db), **kw)
+    return dw.grad(), db.grad()
 
 
 def _colsum(g, rows, N, rowmap=None, row_scale=None, rps=0, out=None):
@@ -412,6 +458,40 @@ def _bn_eval_affine(wc, bn, gamma, beta):
     return ent[1:]
 
 
+def _bn_forward(raw, part, gamma, beta, bn, res, relu, training, mask):
+    """BatchNorm (+residual) (+ReLU, its bit mask into `mask`) of a raw conv output: on the batch statistics finalized from the partial
+    sums `part` [rows][2][C] in training mode, on the running statistics otherwise.  -> (y, mean, rstd)"""
+    C = raw.shape[-1]
+    M, dev = raw.numel() // C, raw.device
+    y = _e(tuple(raw.shape), BF16, dev)
+    if training:
+        _wc().bn_eval.pop(id(bn), None)        # the kernel below rewrites the running statistics in place (no version bump)
+        scale, shift, mean, rstd = (_e((C,), F32, dev) for _ in range(4))
+        # finalize + apply: one fused launch for small tensors, two kernels otherwise (the library decides)
+        call("pk_bn_train_fwd", raw, part, part.shape[0], C, M, gamma, beta, bn.running_mean, bn.running_var, bn.num_batches_tracked,
+             0.1, 1e-5, res, y, mean, rstd, scale, shift, 1 if relu else 0, mask, stream_ptr())
+    else:
+        scale, shift, mean, rstd = _bn_eval_affine(_wc(), bn, gamma, beta)
+        call("pk_bn_act", raw, scale, shift, res, y, M, C, 1 if relu else 0, mask, stream_ptr())
+    return y, mean, rstd
+
+
+def _bn_backward(dy, y, mask, raw, mean, rstd, gamma, g_param, b_param, relu, training, has_res):
+    """BatchNorm backward; the ReLU is masked by the forward's output `y` or its bit mask `mask`.
+    -> (draw, dres or None, dgamma and dbeta as autograd gets them)"""
+    C = raw.shape[-1]
+    M, dev = raw.numel() // C, raw.device
+    nb = _lib.lib.pk_bn_bwd_blocks(M)
+    part, sums = _e((nb, 2, C), F32, dev), _e((2 * C,), F32, dev)
+    dgamma, dbeta = _Dest(g_param), _Dest(b_param)
+    draw = _e(tuple(raw.shape), BF16, dev)
+    dres = _e(tuple(raw.shape), BF16, dev) if has_res else None
+    # (eval mode, bit 1: the running statistics are constants, the input gradient is gamma * rstd * g without the batch-mean terms)
+    call("pk_bn_bwd", dy, y, raw, mean, rstd, gamma, part, sums, dgamma.t, dbeta.t, draw, dres, M, C,
+         (1 if relu else 0) | (0 if training else 2), mask, stream_ptr())
+    return draw, dres, dgamma.grad(), dbeta.grad()
+
+
 class _ConvBnAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, gamma, beta, residual, bn, stride, relu, training, skip_out=None, skip_in=None, infer=False):
@@ -433,21 +513,9 @@ class _ConvBnAct(torch.autograd.Function):
             call("pk_conv2d_affine_nhwc", x, wf, y, scale, shift, res, 1 if relu else 0, B, Hs, Ws, Cin, Cout, ksize, stride, Ho, Wo, stream_ptr())
             return y
         raw, part = _conv_raw(x, wf, Cout, ksize, stride, training)
-        scale, shift = _e((Cout,), F32, dev), _e((Cout,), F32, dev)
-        mean, rstd = _e((Cout,), F32, dev), _e((Cout,), F32, dev)
-        y = _e(raw.shape, BF16, dev)
         # ReLU mask as one bit per element (a byte per 16-byte chunk): BatchNorm backward reads it instead of y (1/16 of the bytes)
         mask = _e((M * Cout // 8,), torch.uint8, dev) if (relu and not infer) else None
-        if training:
-            wc.bn_eval.pop(id(bn), None)        # the kernel below rewrites the running statistics in place (no version bump)
-            # finalize + apply: one fused launch for small tensors, two kernels otherwise (the library decides)
-            call("pk_bn_train_fwd", raw, part, part.shape[0], Cout, M, gamma, beta, bn.running_mean, bn.running_var, bn.num_batches_tracked,
-                 0.1, 1e-5, res, y, mean, rstd, scale, shift, 1 if relu else 0, mask, stream_ptr())
-        else:
-            # eval: scale / shift are constants of the parameters -- computed once (4 small ATen launches) and kept until the weights or
-            # the statistics change (was: 4 launches per BatchNorm layer and forward, 320 per HRFormer-base inference step)
-            scale, shift, mean, rstd = _bn_eval_affine(wc, bn, gamma, beta)
-            call("pk_bn_act", raw, scale, shift, res, y, M, Cout, 1 if relu else 0, mask, stream_ptr())
+        y, mean, rstd = _bn_forward(raw, part, gamma, beta, bn, res, relu, training, mask)
         ctx.save_for_backward(x, raw, y if mask is None else mask, mean, rstd, gamma, wd)
         ctx.has_mask = mask is not None
         ctx.meta = (stride, relu, training, residual is not None, Cin_real, ksize, (B, Hs, Ws, Ho, Wo))
@@ -457,17 +525,10 @@ class _ConvBnAct(torch.autograd.Function):
     def backward(ctx, dy):
         x, raw, y, mean, rstd, gamma, wd = ctx.saved_tensors
         stride, relu, training, has_res, Cin_real, ksize, (B, Hs, Ws, Ho, Wo) = ctx.meta
-        dev, Cout, Cin, M = dy.device, raw.shape[-1], x.shape[-1], B * Ho * Wo
-        dy = dy.contiguous()
-        nb = _lib.lib.pk_bn_bwd_blocks(M)
+        Cout, Cin = raw.shape[-1], x.shape[-1]
         w_p, g_p, b_p = ctx.params
-        part, sums = _e((nb, 2, Cout), F32, dev), _e((2 * Cout,), F32, dev)
-        (dgamma, sg), (dbeta, sb) = _sink(g_p), _sink(b_p)
-        draw = _e(raw.shape, BF16, dev)
-        dres = _e(raw.shape, BF16, dev) if has_res else None
-        # (eval mode, bit 1: the running statistics are constants, the input gradient is gamma * rstd * g without the batch-mean terms)
-        call("pk_bn_bwd", dy, None if ctx.has_mask else y, raw, mean, rstd, gamma, part, sums, dgamma, dbeta, draw, dres, M, Cout,
-             (1 if relu else 0) | (0 if training else 2), y if ctx.has_mask else None, stream_ptr())
+        draw, dres, dgamma, dbeta = _bn_backward(dy.contiguous(), None if ctx.has_mask else y, y if ctx.has_mask else None, raw, mean, rstd,
+                                                 gamma, g_p, b_p, relu, training, has_res)
         addend = None
         if ctx.skip_in is not None:
             addend, ctx.skip_in.g = ctx.skip_in.g, None
@@ -483,10 +544,10 @@ class _ConvBnAct(torch.autograd.Function):
                 dst.copy_(dw)
                 dw = None
         else:
-            dst, sw = _sink(w_p)
-            dw = _wgrad(x, draw, Cout, Cin, ksize, stride, (B, Hs, Ws, Ho, Wo), out=dst, deferred=sw)
-            dw = None if sw else dw
-        return dx, dw, None if sg else dgamma, None if sb else dbeta, dres, None, None, None, None, None, None, None
+            w = _Dest(w_p)
+            _wgrad(x, draw, Cout, Cin, ksize, stride, (B, Hs, Ws, Ho, Wo), out=w.t, deferred=_deferrable(w))
+            dw = w.grad()
+        return dx, dw, dgamma, dbeta, dres, None, None, None, None, None, None, None
 
 
 def conv_bn_act(x, conv, bn, relu=False, residual=None, training=False, skip_out=None, skip_in=None):
@@ -546,11 +607,11 @@ class _StackDeconv(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         Cin, Cout, k, _ = ctx.shape
-        dst, direct = _sink(ctx.param)
-        dst.zero_()
+        dw = _Dest(ctx.param)
+        dw.t.zero_()
         for cls, tap, ky, kx in _deconv_taps(k):
-            dst[:, :, ky, kx] = g[cls * Cout:(cls + 1) * Cout, :, tap // 3, tap % 3].t()
-        return None if direct else dst
+            dw.t[:, :, ky, kx] = g[cls * Cout:(cls + 1) * Cout, :, tap // 3, tap % 3].t()
+        return dw.grad()
 
 
 class _ConvW(torch.autograd.Function):
@@ -587,35 +648,17 @@ class _BnActOnly(torch.autograd.Function):
     def forward(ctx, raw, part, gamma, beta, bn, relu, training):
         ctx.params = (gamma, beta)
         raw = raw.contiguous()
-        C = raw.shape[-1]
-        M = raw.numel() // C
-        dev = raw.device
-        y = _e(tuple(raw.shape), BF16, dev)
-        if training:
-            _wc().bn_eval.pop(id(bn), None)
-            scale, shift, mean, rstd = (_e((C,), F32, dev) for _ in range(4))
-            call("pk_bn_train_fwd", raw, part, part.shape[0], C, M, gamma, beta, bn.running_mean, bn.running_var, bn.num_batches_tracked, 0.1, 1e-5,
-                 None, y, mean, rstd, scale, shift, 1 if relu else 0, None, stream_ptr())
-        else:
-            scale, shift, mean, rstd = _bn_eval_affine(_wc(), bn, gamma, beta)
-            call("pk_bn_act", raw, scale, shift, None, y, M, C, 1 if relu else 0, None, stream_ptr())
+        y, mean, rstd = _bn_forward(raw, part, gamma, beta, bn, None, relu, training, None)
         ctx.save_for_backward(raw, y, mean, rstd, gamma)
-        ctx.meta = (relu, training, M, C)
+        ctx.meta = (relu, training)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         raw, y, mean, rstd, gamma = ctx.saved_tensors
-        relu, training, M, C = ctx.meta
-        dev = dy.device
-        g_p, b_p = ctx.params
-        (dgamma, sg), (dbeta, sb) = _sink(g_p), _sink(b_p)
-        nb = _lib.lib.pk_bn_bwd_blocks(M)
-        part, sums = _e((nb, 2, C), F32, dev), _e((2 * C,), F32, dev)
-        draw = _e(tuple(raw.shape), BF16, dev)
-        call("pk_bn_bwd", dy.contiguous(), y, raw, mean, rstd, gamma, part, sums, dgamma, dbeta, draw, None, M, C, (1 if relu else 0) | (0 if training else 2),
-             None, stream_ptr())
-        return draw, None, None if sg else dgamma, None if sb else dbeta, None, None, None
+        relu, training = ctx.meta
+        draw, _, dgamma, dbeta = _bn_backward(dy.contiguous(), y, None, raw, mean, rstd, gamma, *ctx.params, relu, training, False)
+        return draw, None, dgamma, dbeta, None, None, None
 
 
 def deconv_bn_relu(x, deconv, bn, training):
@@ -664,23 +707,18 @@ class _HeadOut(torch.autograd.Function):
         call("pk_nchw_f32_to_nhwc_bf16", dout.contiguous(), y if softplus else None, g, B, N, H, W, Np, stream_ptr())
         dx = _e((B, H, W, Cin), BF16, x.device)
         call("pk_conv2d_nhwc", g, wd, dx, None, None, B, H, W, Np, Cin, 1, 1, 0, H, W, 0, 0, None, stream_ptr())
-        w_p, b_p = ctx.params
-        dst_w, dst_b = grad_sink_of(w_p), grad_sink_of(b_p)
-        if dst_w is not None and dst_b is not None and deferral_enabled():
+        w, b = (_Dest(p) for p in ctx.params)
+        geom = (B, H, W, H, W)
+        if _deferrable(w, b):
             # slabs only; the step's one pk_reduce_many sums the first N of the Np (8-aligned) rows straight into the sinks (was: a reduce
             # launch + two copies per head output, at the very start of backward)
-            M = B * H * W
-            S = _lib.lib.pk_wgrad_slices(M, Np, Cin, 1, 1, H, W, 0)
-            ws = _workspace(dst_w, "w", S * Np * (Cin + 1))
-            call("pk_wgrad_bf16", x, g, ws, None, None, N, None, None, None, 0, M, Np, Cin, 1, 1, B, H, W, H, W, 1, stream_ptr())
-            _defer(ws.data_ptr(), dst_w, Np * Cin, S, N * Cin)
-            _defer(ws.data_ptr() + 4 * S * Np * Cin, dst_b, Np, S, N)
+            _wgrad(x, g, Np, Cin, 1, 1, geom, out=w.t, dbias=b.t, deferred=True, n_real=N)
             return dx, None, None, None
         db = _e((N,), F32, x.device)
-        dw = _wgrad(x, g, Np, Cin, 1, 1, (B, H, W, H, W), dbias=db)[:N]
-        if dst_w is not None and dst_b is not None:
-            dst_w.copy_(dw)
-            dst_b.copy_(db)
+        dw = _wgrad(x, g, Np, Cin, 1, 1, geom, dbias=db)[:N]
+        if w.direct and b.direct:
+            w.t.copy_(dw)
+            b.t.copy_(db)
             return dx, None, None, None
         return dx, dw.contiguous(), db.contiguous(), None
 
@@ -723,17 +761,14 @@ def _layernorm_bwd(dy, x2d, mean, rstd, gamma, dres, g_param=None, b_param=None,
     M, C = x2d.shape
     nb = _lib.lib.pk_ln_bwd_blocks(M)
     dx = _e((M, C), BF16, x2d.device)
-    (dg, sg) = _sink(g_param) if g_param is not None else (_e((C,), F32, x2d.device), False)
-    (db, sb) = _sink(b_param) if b_param is not None else (_e((C,), F32, x2d.device), False)
-    if sg and sb and deferral_enabled():
-        part = _workspace(dg, "ln", nb * 2 * C)
-        call("pk_layernorm_bwd", dy, x2d, mean, rstd, gamma, dres, dx, part, None, None, M, C, c_real, stream_ptr())
-        _defer(part.data_ptr(), dg, 2 * C, nb, C)
-        _defer(part.data_ptr() + 4 * C, db, 2 * C, nb, C)
-        return dx, None, None
-    part = _e((nb, 2, C), F32, x2d.device)
-    call("pk_layernorm_bwd", dy, x2d, mean, rstd, gamma, dres, dx, part, dg, db, M, C, c_real, stream_ptr())
-    return dx, (None if sg else dg), (None if sb else db)
+    dg, db = _Dest(g_param, (C,), x2d.device), _Dest(b_param, (C,), x2d.device)
+    deferred = _deferrable(dg, db)
+    part = _workspace(dg.t, "ln", nb * 2 * C, deferred)
+    call("pk_layernorm_bwd", dy, x2d, mean, rstd, gamma, dres, dx, part, None if deferred else dg.t, None if deferred else db.t, M, C, c_real,
+         stream_ptr())
+    if deferred:
+        _reduce([_row((part, 0), (dg.t, 0), 2 * C, nb, C), _row((part, C), (db.t, 0), 2 * C, nb, C)], True)
+    return dx, dg.grad(), db.grad()
 
 
 def _linear(x, w, out_rows, N, K, bias=None, residual=None, res_scale=None, a_map=None, o_map=None, preact=None, gelu_of=None,
@@ -763,49 +798,39 @@ class _AttnHalf(torch.autograd.Function):
         o = _e((Mw, C), BF16, x.device)
         lse = _e((B * nwin * heads * WS * WS,), F32, x.device)
         call("pk_window_attn_fwd", qkv, table, o, lse, B * nwin, heads, C, attn_scale, stream_ptr())
-        s1 = None if scale1 is None else scale1.float().contiguous()
+        s1 = _scale(scale1)
         y = _linear(o, wc.fwd[id(wproj)], M, C, C, bias=bproj, residual=x2, res_scale=s1, o_map=amap, M=Mw, rps=H * W)
-        ctx.save_for_backward(x2, u, mean, rstd, qkv, o, lse, g1, table, s1 if s1 is not None else x.new_empty(0),
-                              wc.dgrad[id(wqkv)], wc.dgrad[id(wproj)], amap)
-        ctx.meta = (B, H, W, C, heads, nwin, s1 is not None)
+        ctx.save_for_backward(x2, u, mean, rstd, qkv, o, lse, g1, table, _stash(s1, x), wc.dgrad[id(wqkv)], wc.dgrad[id(wproj)], amap)
+        ctx.meta = (B, H, W, C, heads, nwin)
         return y.view(B, H, W, C)
 
     @staticmethod
     def backward(ctx, dy):
         x2, u, mean, rstd, qkv, o, lse, g1, table, s1, wqkv_t, wproj_t, amap = ctx.saved_tensors
-        B, H, W, C, heads, nwin, has_s = ctx.meta
-        s1 = s1 if has_s else None
+        B, H, W, C, heads, nwin = ctx.meta
+        s1 = _unstash(s1)
         M, Mw = B * H * W, B * nwin * WS * WS
         dev = dy.device
         dy2 = dy.contiguous().view(M, C)
         # proj: rows of the GEMM are window-order tokens, dy rows are gathered through the map; DropPath scale per sample
         pg1, pb1, ptab, pwqkv, pbqkv, pwproj, pbproj = ctx.params
         d_o = _linear(dy2, wproj_t, Mw, C, C, res_scale=s1, a_map=amap, rps=nwin * WS * WS)
-        dst, s_wp = _sink(pwproj)
-        dbproj, s_bp = _sink(pbproj)
-        dwproj = _wgrad(o, dy2, C, C, 1, 1, None, g_map=amap, g_scale=s1, g_rps=H * W, M=Mw, out=dst, dbias=dbproj,
-                        deferred=s_wp and s_bp, win=(B, H, W))
+        dwproj, dbproj = _linear_wgrad(pwproj, pbproj, o, dy2, C, C, g_map=amap, g_scale=s1, g_rps=H * W, M=Mw, win=(B, H, W))
         # attention core
         dqkv = _e((Mw, 3 * C), BF16, dev)
-        dtable, s_t = _sink(ptab)
+        dtable = _Dest(ptab)
+        deferred = _deferrable(dtable)
         n_part = _lib.lib.pk_window_attn_bwd_ws_floats(B * nwin, heads)
-        if s_t and deferral_enabled():
-            part = _workspace(dtable, "rpb", n_part)
-            call("pk_window_attn_bwd", qkv, table, o, d_o, lse, dqkv, part, None, B * nwin, heads, C, ctx.pad[1], stream_ptr())
-            per_head = n_part // 169 // heads
-            for hh in range(heads):      # group g = k*heads + h holds 169 partial sums of head h
-                _defer(part.data_ptr() + 4 * 169 * hh, dtable, 169 * heads, per_head, 169, out_stride=heads, out_offset=hh)
-        else:
-            part = _e((n_part,), F32, dev)
-            call("pk_window_attn_bwd", qkv, table, o, d_o, lse, dqkv, part, dtable, B * nwin, heads, C, ctx.pad[1], stream_ptr())
+        part = _workspace(dtable.t, "rpb", n_part, deferred)
+        call("pk_window_attn_bwd", qkv, table, o, d_o, lse, dqkv, part, None if deferred else dtable.t, B * nwin, heads, C, ctx.pad[1],
+             stream_ptr())
+        if deferred:                  # group g = k*heads + h holds 169 partial sums of head h
+            _reduce([_row((part, 169 * hh), (dtable.t, hh), 169 * heads, n_part // 169 // heads, 169, ostride=heads) for hh in range(heads)], True)
         # qkv linear: scatter the token gradients back to pixel rows (pad tokens dropped)
         du = _linear(dqkv, wqkv_t, M, C, 3 * C, o_map=amap, M=Mw)
-        dst, s_wq = _sink(pwqkv)
-        dbqkv, s_bq = _sink(pbqkv)
-        dwqkv = _wgrad(u, dqkv, 3 * C, C, 1, 1, None, a_map=amap, M=Mw, out=dst, dbias=dbqkv, deferred=s_wq and s_bq, win=(B, H, W))
+        dwqkv, dbqkv = _linear_wgrad(pwqkv, pbqkv, u, dqkv, 3 * C, C, a_map=amap, M=Mw, win=(B, H, W))
         dx, dg1, db1 = _layernorm_bwd(du, x2, mean, rstd, g1, dy2, pg1, pb1, ctx.pad[0])
-        return (dx.view(B, H, W, C), dg1, db1, None if s_t else dtable, None if s_wq else dwqkv, None if s_bq else dbqkv,
-                None if s_wp else dwproj, None if s_bp else dbproj, None, None, None, None)
+        return dx.view(B, H, W, C), dg1, db1, dtable.grad(), dwqkv, dbqkv, dwproj, dbproj, None, None, None, None
 
 
 class _MlpHalf(torch.autograd.Function):
@@ -823,31 +848,26 @@ class _MlpHalf(torch.autograd.Function):
         v, mean, rstd = _layernorm(x2, g2, b2, c_real)
         z = _e((M, Hd), BF16, x.device)
         h = _linear(v, wc.fwd[id(w1)], M, Hd, C, bias=bias1, preact=z, act=1)
-        s2 = None if scale2 is None else scale2.float().contiguous()
+        s2 = _scale(scale2)
         y = _linear(h, wc.fwd[id(w2)], M, C, Hd, bias=bias2, residual=x2, res_scale=s2, rps=H * W)
-        ctx.save_for_backward(x2, v, mean, rstd, z, h, g2, s2 if s2 is not None else x.new_empty(0), wc.dgrad[id(w1)], wc.dgrad[id(w2)])
-        ctx.meta = (B, H, W, C, Hd, s2 is not None)
+        ctx.save_for_backward(x2, v, mean, rstd, z, h, g2, _stash(s2, x), wc.dgrad[id(w1)], wc.dgrad[id(w2)])
+        ctx.meta = (B, H, W, C, Hd)
         return y.view(B, H, W, C)
 
     @staticmethod
     def backward(ctx, dy):
         x2, v, mean, rstd, z, h, g2, s2, w1_t, w2_t = ctx.saved_tensors
-        B, H, W, C, Hd, has_s = ctx.meta
-        s2 = s2 if has_s else None
+        B, H, W, C, Hd = ctx.meta
+        s2 = _unstash(s2)
         M = B * H * W
         dy2 = dy.contiguous().view(M, C)
         pg2, pb2, pw1, pbias1, pw2, pbias2 = ctx.params
         dz = _linear(dy2, w2_t, M, Hd, C, res_scale=s2, gelu_of=z, rps=H * W)        # (dy W2) * s2 * gelu'(z)
-        dst, s_w2 = _sink(pw2)
-        db2, s_b2 = _sink(pbias2)
-        dw2 = _wgrad(h, dy2, C, Hd, 1, 1, None, g_scale=s2, g_rps=H * W, M=M, out=dst, dbias=db2, deferred=s_w2 and s_b2)
+        dw2, db2 = _linear_wgrad(pw2, pbias2, h, dy2, C, Hd, g_scale=s2, g_rps=H * W, M=M)
         dv = _linear(dz, w1_t, M, C, Hd)
-        dst, s_w1 = _sink(pw1)
-        db1, s_b1 = _sink(pbias1)
-        dw1 = _wgrad(v, dz, Hd, C, 1, 1, None, M=M, out=dst, dbias=db1, deferred=s_w1 and s_b1)
+        dw1, db1 = _linear_wgrad(pw1, pbias1, v, dz, Hd, C, M=M)
         dx, dg2, dbt2 = _layernorm_bwd(dv, x2, mean, rstd, g2, dy2, pg2, pb2, ctx.c_real)
-        return (dx.view(B, H, W, C), dg2, dbt2, None if s_w1 else dw1, None if s_b1 else db1, None if s_w2 else dw2,
-                None if s_b2 else db2, None, None)
+        return dx.view(B, H, W, C), dg2, dbt2, dw1, db1, dw2, db2, None, None
 
 
 class _WindowAttnOnly(torch.autograd.Function):
@@ -959,53 +979,38 @@ class _MlpHalfFused(torch.autograd.Function):
         x = x.contiguous()
         B, H, W, C = x.shape
         M = B * H * W
-        s2 = None if scale2 is None else scale2.float().contiguous()
+        s2 = _scale(scale2)
         y = _e((B, H, W, C), BF16, x.device)
         call("pk_ln_mlp_fwd", x, g2, b2, wc.fwd[id(w1)], bias1, wc.fwd[id(w2)], bias2, s2, y, M, C, H * W, 1e-5, stream_ptr())
-        ctx.save_for_backward(x, g2, b2, bias1, s2 if s2 is not None else x.new_empty(0), wc.fwd[id(w1)], wc.dgrad[id(w1)], wc.dgrad[id(w2)])
-        ctx.meta = (B, H, W, C, s2 is not None)
+        ctx.save_for_backward(x, g2, b2, bias1, _stash(s2, x), wc.fwd[id(w1)], wc.dgrad[id(w1)], wc.dgrad[id(w2)])
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, g2, b2, bias1, s2, w1f, w1t, w2t = ctx.saved_tensors
-        B, H, W, C, has_s = ctx.meta
-        s2 = s2 if has_s else None
+        B, H, W, C = x.shape
+        s2 = _unstash(s2)
         M, Hd, dev = B * H * W, 4 * C, dy.device
         dy = dy.contiguous()
-        pg2, pb2, pw1, pbias1, pw2, pbias2 = ctx.params
-        (dg, sg), (db, sb) = _sink(pg2), _sink(pb2)
-        (dw1, s_w1), (db1, s_b1), (dw2, s_w2), (dbb2, s_b2) = _sink(pw1), _sink(pbias1), _sink(pw2), _sink(pbias2)
-        all_sinks = sg and sb and s_w1 and s_b1 and s_w2 and s_b2 and deferral_enabled()
+        dg, db, dw1, db1, dw2, db2 = dests = [_Dest(p) for p in ctx.params]
+        deferred = _deferrable(*dests)
         nbx, nbw = _lib.lib.pk_ln_mlp_dx_blocks(M, C), _lib.lib.pk_ln_mlp_dw_blocks(M, C)
         HS, SL = _lib.lib.pk_ln_mlp_hidden_slice(C), _lib.lib.pk_ln_mlp_slab_floats(C)
         ns = Hd // HS
-        if all_sinks:
-            lnp, slabs = _workspace(dg, "mlp_ln", nbx * 2 * C), _workspace(dw1, "mlp_w", ns * nbw * SL)
-        else:
-            lnp, slabs = _e((nbx * 2 * C,), F32, dev), _e((ns * nbw * SL,), F32, dev)
+        lnp = _workspace(dg.t, "mlp_ln", nbx * 2 * C, deferred)
+        slabs = _workspace(dw1.t, "mlp_w", ns * nbw * SL, deferred)
         dx = _e((B, H, W, C), BF16, dev)
         call("pk_ln_mlp_bwd_dx", dy, x, g2, b2, w1f, bias1, w1t, w2t, s2, dx, lnp, M, C, H * W, 1e-5, stream_ptr())
         call("pk_ln_mlp_bwd_dw", dy, x, g2, b2, w1f, bias1, w2t, s2, slabs, M, C, H * W, 1e-5, stream_ptr())
-        rows = []
-
-        def red(part_off, out, S, K, stride, layout=0, T=1, Cin=1, out_stride=1, out_offset=0, base=slabs):
-            rows.append((base.data_ptr() + 4 * part_off, out.data_ptr() + 4 * out_offset, stride, S, K, layout, 0, T, Cin, out_stride, 0))
-
-        red(0, dg, nbx, C, 2 * C, base=lnp)
-        red(C, db, nbx, C, 2 * C, base=lnp)
+        rows = [_row((lnp, 0), (dg.t, 0), 2 * C, nbx, C), _row((lnp, C), (db.t, 0), 2 * C, nbx, C)]
         for y in range(ns):
             o = y * nbw * SL
-            red(o, dw1, nbw, HS * C, SL, out_offset=y * HS * C)                                          # rows h0 .. h0+HS of [4C][C]
-            red(o + HS * C, dw2, nbw, C * HS, SL, layout=2, T=Hd, Cin=HS, out_stride=1, out_offset=y * HS)   # columns h0 .. of [C][4C]
-            red(o + 2 * HS * C, db1, nbw, HS, SL, out_offset=y * HS)
-        red(2 * HS * C + HS, dbb2, nbw, C, SL)
-        if all_sinks:
-            _PENDING.extend(rows)
-            return dx, None, None, None, None, None, None, None
-        _reduce_now(rows, dev)
-        return (dx, None if sg else dg, None if sb else db, None if s_w1 else dw1, None if s_b1 else db1, None if s_w2 else dw2,
-                None if s_b2 else dbb2, None)
+            rows += [_row((slabs, o), (dw1.t, y * HS * C), SL, nbw, HS * C),                                     # rows h0 .. h0+HS of [4C][C]
+                     _row((slabs, o + HS * C), (dw2.t, y * HS), SL, nbw, C * HS, layout=2, T=Hd, Cin=HS),        # columns h0 .. of [C][4C]
+                     _row((slabs, o + 2 * HS * C), (db1.t, y * HS), SL, nbw, HS)]
+        rows.append(_row((slabs, 2 * HS * C + HS), (db2.t, 0), SL, nbw, C))
+        _reduce(rows, deferred, dev)
+        return (dx, *(d.grad() for d in dests), None)
 
 
 def wide_mlp_enabled(C, hidden, M=0):
@@ -1033,7 +1038,7 @@ def attn_half_wide_forward(x, g1, b1, table, wqkv, bqkv, wproj, bproj, scale1, h
     B, H, W, C = x.shape
     amap, nwin = window_rowmap(B, H, W, x.device)
     y = _e((B, H, W, C), BF16, x.device)
-    s1 = None if scale1 is None else scale1.float().contiguous()
+    s1 = _scale(scale1)
     call("pk_attn_block_wide_fwd", x, amap, g1, b1, table, wc.fwd[id(wqkv)], bqkv, wc.fwd[id(wproj)], bproj, s1, y, B * nwin, nwin, heads, C,
          c_real or C, attn_scale or float(C // heads) ** -0.5, 1e-5, stream_ptr())
     return y
@@ -1044,7 +1049,7 @@ def mlp_half_wide_forward(x, g2, b2, w1, bias1, w2, bias2, scale2, c_real=0):
     wc = _wc()
     x = x.contiguous()
     B, H, W, C = x.shape
-    s2 = None if scale2 is None else scale2.float().contiguous()
+    s2 = _scale(scale2)
     y = _e((B, H, W, C), BF16, x.device)
     call("pk_ln_mlp_wide_fwd", x, g2, b2, wc.fwd[id(w1)], bias1, wc.fwd[id(w2)], bias2, s2, y, B * H * W, C, c_real or C, w1.shape[0], H * W, 1e-5,
          stream_ptr())
@@ -1070,7 +1075,7 @@ def attn_half_fused_forward(x, g1, b1, table, wqkv, bqkv, wproj, bproj, scale1, 
     y = _e((B, H, W, C), BF16, x.device)
     o = _e((nw * WS * WS, C), BF16, x.device) if save else None
     lse = _e((nw * heads * WS * WS,), F32, x.device) if save else None
-    s1 = None if scale1 is None else scale1.float().contiguous()
+    s1 = _scale(scale1)
     call("pk_attn_block_fwd", x, amap, g1, b1, table, wc.fwd[id(wqkv)], bqkv, wc.fwd[id(wproj)], bproj, s1, y, o, lse, nw, nwin, heads, C,
          1e-5, stream_ptr())
     return y, o, lse, amap
@@ -1087,56 +1092,42 @@ class _AttnHalfFused(torch.autograd.Function):
         wc = _wc()
         x = x.contiguous()
         y, o, lse, amap = attn_half_fused_forward(x, g1, b1, table, wqkv, bqkv, wproj, bproj, scale1, heads, save=True)
-        s1 = None if scale1 is None else scale1.float().contiguous()
-        ctx.save_for_backward(x, g1, b1, table, bqkv, s1 if s1 is not None else x.new_empty(0), o, lse, wc.fwd[id(wqkv)], wc.dgrad[id(wqkv)],
+        ctx.save_for_backward(x, g1, b1, table, bqkv, _stash(_scale(scale1), x), o, lse, wc.fwd[id(wqkv)], wc.dgrad[id(wqkv)],
                               wc.dgrad[id(wproj)], amap)
-        ctx.meta = (heads, s1 is not None)
+        ctx.heads = heads
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, g1, b1, table, bqkv, s1, o, lse, wqkv_f, wqkv_t, wproj_t, amap = ctx.saved_tensors
-        heads, has_s = ctx.meta
-        s1 = s1 if has_s else None
+        heads, s1 = ctx.heads, _unstash(s1)
         B, H, W, C = x.shape
         dev, M = dy.device, B * H * W
         nw = amap.numel() // (WS * WS)
         nwin, Mw = nw // B, nw * WS * WS
         dy = dy.contiguous()
         pg1, pb1, ptab, pwqkv, pbqkv, pwproj, pbproj = ctx.params
-        (dg, sg), (db, sb) = _sink(pg1), _sink(pb1)
+        dg, db = _Dest(pg1), _Dest(pb1)
         # with_rpe=False (hrformer.py:145-191): the table is the shared all-zero constant, not a parameter -- its partial sums go to a
         # scratch workspace nobody reduces, so the LayerNorm rows keep the deferred (hipGraph-capturable) path
         no_tab = getattr(ptab, "_pk_zero_table", False)
-        dtable, s_t = (None, True) if no_tab else _sink(ptab)
+        dtable = _Dest(None if no_tab else ptab)
         nb = _lib.lib.pk_attn_block_blocks(nw)
-        small_sinks = sg and sb and s_t and deferral_enabled()
-        if small_sinks:
-            lnp = _workspace(dg, "attn_ln", nb * 2 * C)
-            rpb = _workspace(dg if no_tab else dtable, "attn_rpb_void" if no_tab else "attn_rpb", nb * 4 * heads * 169)
-        else:
-            lnp, rpb = _e((nb * 2 * C,), F32, dev), _e((nb * 4 * heads * 169,), F32, dev)
+        deferred = _deferrable(dg, db, dtable)
+        lnp = _workspace(dg.t, "attn_ln", nb * 2 * C, deferred)
+        rpb = _workspace(dg.t if no_tab else dtable.t, "attn_rpb_void" if no_tab else "attn_rpb", nb * 4 * heads * 169, deferred)
         dx = _e((B, H, W, C), BF16, dev)
         dqkv, u_w = _e((Mw, 3 * C), BF16, dev), _e((Mw, C), BF16, dev)
         call("pk_attn_block_bwd", dy, x, amap, g1, b1, table, wqkv_f, bqkv, wqkv_t, wproj_t, s1, o, lse, dx, dqkv, u_w, lnp, rpb, nw, nwin,
              heads, C, 1e-5, stream_ptr())
-        rows = [(lnp.data_ptr(), dg.data_ptr(), 2 * C, nb, C, 0, 0, 1, 1, 1, 0), (lnp.data_ptr() + 4 * C, db.data_ptr(), 2 * C, nb, C, 0, 0, 1, 1, 1, 0)]
+        rows = [_row((lnp, 0), (dg.t, 0), 2 * C, nb, C), _row((lnp, C), (db.t, 0), 2 * C, nb, C)]
         for hh in range(0 if no_tab else heads):              # partial [wave][head][169] -> table[e][head]
-            rows.append((rpb.data_ptr() + 4 * 169 * hh, dtable.data_ptr() + 4 * hh, 169 * heads, nb * 4, 169, 0, 0, 1, 1, heads, 0))
-        if small_sinks:
-            _PENDING.extend(rows)
-        else:
-            _reduce_now(rows, dev)
+            rows.append(_row((rpb, 169 * hh), (dtable.t, hh), 169 * heads, nb * 4, 169, ostride=heads))
+        _reduce(rows, deferred, dev)
         # weight gradients: plain [tokens] x [features] GEMMs over the window-ordered rows
-        dst, s_wq = _sink(pwqkv)
-        dbqkv, s_bq = _sink(pbqkv)
-        dwqkv = _wgrad(u_w, dqkv, 3 * C, C, 1, 1, None, M=Mw, out=dst, dbias=dbqkv, deferred=s_wq and s_bq)
-        dst, s_wp = _sink(pwproj)
-        dbproj, s_bp = _sink(pbproj)
-        dwproj = _wgrad(o, dy.view(M, C), C, C, 1, 1, None, g_map=amap, g_scale=s1, g_rps=H * W, M=Mw, out=dst, dbias=dbproj,
-                        deferred=s_wp and s_bp, win=(B, H, W))
-        return (dx, None if sg else dg, None if sb else db, None if s_t else dtable, None if s_wq else dwqkv, None if s_bq else dbqkv,
-                None if s_wp else dwproj, None if s_bp else dbproj, None, None)
+        dwqkv, dbqkv = _linear_wgrad(pwqkv, pbqkv, u_w, dqkv, 3 * C, C, M=Mw)
+        dwproj, dbproj = _linear_wgrad(pwproj, pbproj, o, dy.view(M, C), C, C, g_map=amap, g_scale=s1, g_rps=H * W, M=Mw, win=(B, H, W))
+        return dx, dg.grad(), db.grad(), dtable.grad(), dwqkv, dbqkv, dwproj, dbproj, None, None
 
 
 def window_block(x, blk, heads, scale1=None, scale2=None):
@@ -1165,6 +1156,17 @@ def window_block(x, blk, heads, scale1=None, scale2=None):
 
 
 # ================================================================================================ exchange unit
+def _fuse_sum_launch(xs, out, relu):
+    """out = (relu of) the sum of the NHWC bf16 tensors xs, the smaller ones bilinearly up-sampled to out's size."""
+    B, H, W, C = out.shape
+    # host arrays: the C-ABI reads them before the launch returns (pointer table is copied into the kernel arguments)
+    ptrs = torch.tensor([t.data_ptr() for t in xs], dtype=torch.int64)
+    hs = torch.tensor([t.shape[1] for t in xs], dtype=torch.int32)
+    wsz = torch.tensor([t.shape[2] for t in xs], dtype=torch.int32)
+    call("pk_fuse_sum", ptrs.data_ptr(), hs.data_ptr(), wsz.data_ptr(), len(xs), out, B, H, W, C, 1 if relu else 0, stream_ptr())
+    return out
+
+
 class _FuseSum(torch.autograd.Function):
     """relu(sum_i up(x_i)) with bilinear (align_corners=False) up-sampling of the lower-resolution inputs fused in."""
 
@@ -1174,12 +1176,7 @@ class _FuseSum(torch.autograd.Function):
         ref = max(xs, key=lambda t: t.shape[1] * t.shape[2])
         B, H, W, C = ref.shape
         dev = ref.device
-        ptrs = torch.tensor([t.data_ptr() for t in xs], dtype=torch.int64)
-        hs = torch.tensor([t.shape[1] for t in xs], dtype=torch.int32)
-        wsz = torch.tensor([t.shape[2] for t in xs], dtype=torch.int32)
-        out = _e((B, H, W, C), BF16, dev)
-        # host arrays: the C-ABI reads them before the launch returns (pointer table is copied into the kernel arguments)
-        call("pk_fuse_sum", ptrs.data_ptr(), hs.data_ptr(), wsz.data_ptr(), len(xs), out, B, H, W, C, 1 if relu else 0, stream_ptr())
+        out = _fuse_sum_launch(xs, _e((B, H, W, C), BF16, dev), relu)
         ctx.save_for_backward(out)
         ctx.meta = (relu, [tuple(t.shape) for t in xs])
         return out
@@ -1209,12 +1206,7 @@ def sum_same_shape(ts):
     """Plain sum of 2-4 NHWC bf16 tensors of one shape in ONE launch (no autograd): used for fan-out gradient accumulation."""
     ts = [t.contiguous() for t in ts]
     B, H, W, C = ts[0].shape
-    out = _e((B, H, W, C), BF16, ts[0].device)
-    ptrs = torch.tensor([t.data_ptr() for t in ts], dtype=torch.int64)
-    hs = torch.tensor([H] * len(ts), dtype=torch.int32)
-    wsz = torch.tensor([W] * len(ts), dtype=torch.int32)
-    call("pk_fuse_sum", ptrs.data_ptr(), hs.data_ptr(), wsz.data_ptr(), len(ts), out, B, H, W, C, 0, stream_ptr())
-    return out
+    return _fuse_sum_launch(ts, _e((B, H, W, C), BF16, ts[0].device), False)
 
 
 def fuse_sum(xs, relu=True):

@@ -495,8 +495,8 @@ def test_window_attention_at_training_window_counts(L, N, d, heads, nw):
     o, lse, dq, part, dt = run(0, nw, True)
     _, _, dq0, part0, _ = run(0, nw, False)
     dt_many = nan_t((169 + 8, heads))                  # 8 guard rows: no write past K
-    N._reduce_now([(part0.data_ptr() + 4 * 169 * hh, dt_many.data_ptr() + 4 * hh, 169 * heads, per_head, 169, 0, 0, 1, 1, heads, 0)
-                   for hh in range(heads)], torch.device(DEV))
+    N._reduce([N._row(part=(part0, 169 * hh), out=(dt_many, hh), stride=169 * heads, S=per_head, K=169, ostride=heads)
+               for hh in range(heads)], False, torch.device(DEV))
     chunks = []
     for w0 in range(0, nw, 512):
         n = min(512, nw - w0)
@@ -790,10 +790,10 @@ def test_reduce_many_scalar_path_layouts_and_bounds(L, N):
             idx = ((i // (Cin * T)) * Cin + i % Cin) * T + (i // Cin) % T
         else:
             idx = (i // Cin) * T + (i % Cin) * ostride
-        rows.append((pool.data_ptr() + 4 * base, out.data_ptr(), stride, S, K, layout, 0, T, Cin, ostride, 0))
+        rows.append(N._row(part=(pool, base), out=(out, 0), stride=stride, S=S, K=K, layout=layout, T=T, Cin=Cin, ostride=ostride))
         checks.append((out, idx, p64.sum(0), p64.abs().sum(0), S, (stride, S, K, layout)))
     assert off <= pool.numel()
-    N._reduce_now(rows, torch.device(DEV))
+    N._reduce(rows, False, torch.device(DEV))
     torch.cuda.synchronize()
     for out, idx, ref, ab, S, spec in checks:
         ratio = float(((out[idx].double() - ref).abs() / ((-(-S // 16) + 16) * U * ab + 1e-30)).max())
