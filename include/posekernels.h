@@ -125,6 +125,22 @@ int pk_affine_crop_jitter_normalize(const void* src_u8, const void* desc_table, 
 int pk_flip_merge(const float* a, const float* b_flipped, const int32_t* partner, float* out,
                   int B, int K, int H, int W, void* stream);
 
+/* ---- D4 over several crop scales: multi-scale flip test (this project's own specification; the reference names the option in its yaml,
+ * ADVANCED.MULTI_SCALE_TEST / SCALE_LIST, and never implemented it).  stack (S*F*B, K, H, W) fp32, pass-major: pass p = s*F + f holds
+ * rows [p*B, (p+1)*B); f = 0 is the plain crop taken with box scale scale_s * scale around the same centre, f = 1 the forward of the
+ * mirrored crop (F = 1 or 2, 1 <= S <= 8).  partner (K) int32 as for pk_flip_merge, may be NULL when F = 1.  inv_scales_host: HOST
+ * pointer to S floats, entry s = (float)(1.0 / (double)scale_s), read before the call returns and carried in the kernel's arguments
+ * (no device table, no allocation: graph-capturable).  out (B, K, H, W).  All float32, one rounding per operation, in this order:
+ *   cx = 0.5f W, cy = 0.5f H, lerp(a, b, t) = fmaf(t, b - a, a);  for s = 0 .. S-1:
+ *     us = fmaf(x - cx, inv[s], cx), vs = fmaf(y - cy, inv[s], cy);  pass s counts iff 0 <= us <= W-1 and 0 <= vs <= H-1 (inclusive);
+ *     x0 = floor(us), x1 = min(x0 + 1, W-1), lx = us - x0, same for y;
+ *     f = 0, m = stack[(s*F)*B + b, k]:            acc += lerp(lerp(m[y0][x0], m[y0][x1], lx), lerp(m[y1][x0], m[y1][x1], lx), ly), n += 1
+ *     f = 1, m = stack[(s*F+1)*B + b, partner[k]]: the same with columns W-1-x0 and W-1-x1 (same lx, no one-pixel shift),    n += 1
+ *   out = acc / n, or 0 when no pass sees the pixel.
+ * Passes that cannot see a pixel do not dilute it.  S = 1, inv = 1, F = 2 is bit for bit pk_flip_merge on finite maps.             */
+int pk_multiscale_merge(const float* stack, const int32_t* partner, const float* inv_scales_host, float* out,
+                        int S, int F, int B, int K, int H, int W, void* stream);
+
 /* ---- video post-processing (utils/postprocess.py:187-267) -------------------------------------------------------
  * pk_temporal_smooth: coords/out (T, C=2K) fp32, weights: `window` doubles as np.convolve receives them (the kernel is flipped
  * like np.convolve does; edge padding window/2 on both sides; float64 accumulation, float32 result); window must be odd.

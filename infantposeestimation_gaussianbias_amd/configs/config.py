@@ -6,8 +6,10 @@ identically.  Extension over the reference: `get_config(path_or_name)` also acce
   * a legacy-format yaml (reference configs/*.yaml, written by root config.py:135-224): `MODEL.NUM_JOINTS`,
     `MODEL.IMAGE_SIZE`, `MODEL.HEATMAP_SIZE`, `MODEL.SIGMA`, `TRAIN.*` are mapped onto the dataclass fields, and
     `DATA.COLOR_JITTER.{BRIGHTNESS,CONTRAST,SATURATION}` onto `cfg.train.color_jitter` (a yaml that names it trains with it; a
-    missing sub-key reads as 0, and a block that is empty or all zero leaves jitter off).
+    missing sub-key reads as 0, and a block that is empty or all zero leaves jitter off), and `ADVANCED.MULTI_SCALE_TEST` /
+    `ADVANCED.SCALE_LIST` onto `cfg.test_scales` (multi-scale test; off unless MULTI_SCALE_TEST is true).
 """
+import math
 import os
 from dataclasses import dataclass, field
 from typing import List, Optional, Tuple
@@ -87,6 +89,9 @@ class Config:
     train: TrainConfig = field(default_factory=TrainConfig)
     exp_name: str = 'hrformer_base_coco_256x192'
     seed: int = 42
+    # Multi-scale test (legacy yaml ADVANCED.MULTI_SCALE_TEST + SCALE_LIST, `--scales`): None (one crop per person) or the box-scale factors
+    # of the crops whose heatmaps are merged, exactly one of them 1.0.  A plain class attribute like `color_jitter`: same field set.
+    test_scales = None
 
 
 _PRESETS = {
@@ -98,6 +103,24 @@ _PRESETS = {
     'hrnet_w18': ('hrnet_w18', 'heatmap', 18, (96, 128), (24, 32), 17, 2.0),       # BASELINE config 1
     'preemie': ('hrformer_base', 'fusion', 78, (288, 384), (72, 96), 13, 1.5),     # BASELINE config 5 (K=13, sigma 1.5)
 }
+
+
+def check_test_scales(scales) -> Tuple[float, ...]:
+    """The scale list of a multi-scale test as a tuple of floats: 1 to 8 finite, positive, distinct entries, exactly one of them 1.0
+    (the base crop, in whose frame the passes are merged).  ValueError otherwise."""
+    try:
+        sc = tuple(float(s) for s in scales)
+    except (TypeError, ValueError):
+        raise ValueError(f"test scales must be a list of numbers, got {scales!r}") from None
+    if not 1 <= len(sc) <= 8:
+        raise ValueError(f"test scales: {len(sc)} entries (1 to 8)")
+    if not all(math.isfinite(s) and s > 0 for s in sc):
+        raise ValueError(f"test scales must be finite and > 0, got {sc}")
+    if len(set(sc)) != len(sc):
+        raise ValueError(f"test scales must be distinct, got {sc}")
+    if sc.count(1.0) != 1:
+        raise ValueError(f"test scales need exactly one 1.0 (the base crop), got {sc}")
+    return sc
 
 
 def _apply_preset(cfg: Config, name: str) -> Config:
@@ -150,6 +173,10 @@ def _apply_legacy_yaml(cfg: Config, path: str) -> Config:
         # not the identity (u / 255 * 255 truncates)
         rng = tuple(float((cj or {}).get(k, 0) or 0) for k in ('BRIGHTNESS', 'CONTRAST', 'SATURATION'))
         cfg.train.color_jitter = rng if any(rng) else None
+    adv = y.get('ADVANCED', {}) or {}
+    if adv.get('MULTI_SCALE_TEST'):
+        sl = adv.get('SCALE_LIST')
+        cfg.test_scales = check_test_scales(sl) if sl is not None else (1.0,)
     cfg.exp_name = os.path.splitext(os.path.basename(path))[0]
     return cfg
 

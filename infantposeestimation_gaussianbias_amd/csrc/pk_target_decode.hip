@@ -491,6 +491,82 @@ extern "C" int pk_flip_merge(const float* a, const float* b_flipped, const int32
     return pk_launch_status("pk_flip_merge");
 }
 
+// ------------------------------------------------------------------------------------------------ D4 over several crop scales
+// Multi-scale flip test: S crops of the same centre with box scale s * scale, each run plain (f = 0) and mirrored (f = 1), brought back
+// into the frame of the scale-1.0 crop and averaged.  Base heat-px u is seen by pass s at u_s = W/2 + (u - W/2) / s (pk_affine_coords'
+// convention: img = u * scale / W + centre - scale / 2); the pass is sampled there bilinearly if u_s lies on its map (borders included),
+// otherwise it contributes nothing and the divisor shrinks with it.  One workgroup per (b, k) map like k_flip_merge; the S * F source
+// maps are gathered from global memory (every map is consumed whole, so L2 serves the four taps; 6 maps of 96 x 72 do not fit in LDS).
+// Every operation is written out with one rounding each and in a fixed order (s ascending, f = 0 before f = 1): no atomics, the same
+// bits on every run, and tests/multiscale_np.py can restate it.  The 1 / s table rides in the kernel arguments (no device table).
+struct MsInv {
+    float v[8];
+};
+__device__ __forceinline__ float ms_lerp(float a, float b, float t) { return fmaf(t, __fsub_rn(b, a), a); }
+template <int S>
+__global__ void __launch_bounds__(256) k_multiscale_merge(const float* __restrict__ stack, const int32_t* __restrict__ partner,
+                                                          float* __restrict__ out, MsInv inv, int F, int B, int K, int H, int W) {
+    const int map = blockIdx.x, b = map / K, k = map - b * K, n = H * W;
+    const int kf = F == 2 ? partner[k] : k;
+    const float cx = 0.5f * (float)W, cy = 0.5f * (float)H, xmax = (float)(W - 1), ymax = (float)(H - 1);
+    float* po = out + (size_t)map * n;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const int y = i / W, x = i - y * W;
+        float acc = 0.f;
+        int cnt = 0;
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            const float us = fmaf(__fsub_rn((float)x, cx), inv.v[s], cx), vs = fmaf(__fsub_rn((float)y, cy), inv.v[s], cy);
+            if (!(us >= 0.f && us <= xmax && vs >= 0.f && vs <= ymax)) continue;
+            const int x0 = (int)floorf(us), y0 = (int)floorf(vs);
+            const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
+            const float lx = __fsub_rn(us, (float)x0), ly = __fsub_rn(vs, (float)y0);
+            const float* m = stack + (((size_t)s * F * B + b) * K + k) * n;
+            acc = __fadd_rn(acc, ms_lerp(ms_lerp(m[y0 * W + x0], m[y0 * W + x1], lx), ms_lerp(m[y1 * W + x0], m[y1 * W + x1], lx), ly));
+            ++cnt;
+            if (F == 2) {       // the mirrored crop's map: partner channel, mirrored columns, same weights (no one-pixel shift)
+                const float* mf = stack + ((((size_t)s * F + 1) * B + b) * K + kf) * n;
+                const int c0 = W - 1 - x0, c1 = W - 1 - x1;
+                acc = __fadd_rn(acc, ms_lerp(ms_lerp(mf[y0 * W + c0], mf[y0 * W + c1], lx), ms_lerp(mf[y1 * W + c0], mf[y1 * W + c1], lx), ly));
+                ++cnt;
+            }
+        }
+        po[i] = cnt > 0 ? __fdiv_rn(acc, (float)cnt) : 0.f;
+    }
+}
+template <int S>
+static void multiscale_merge_launch(const float* stack, const int32_t* partner, float* out, const MsInv& inv, int F, int B, int K, int H, int W,
+                                    hipStream_t stream) {
+    hipLaunchKernelGGL(k_multiscale_merge<S>, dim3(B * K), dim3(256), 0, stream, stack, partner, out, inv, F, B, K, H, W);
+}
+extern "C" int pk_multiscale_merge(const float* stack, const int32_t* partner, const float* inv_scales_host, float* out, int S, int F, int B,
+                                   int K, int H, int W, void* stream) {
+    PK_REQUIRE(stack && inv_scales_host && out, "pk_multiscale_merge: null pointer");
+    PK_REQUIRE(F == 1 || F == 2, "pk_multiscale_merge: F = %d passes per scale (1: plain, 2: plain + mirrored)", F);
+    PK_REQUIRE(F == 1 || partner, "pk_multiscale_merge: the mirrored passes need the partner table");
+    PK_REQUIRE(S >= 1 && S <= 8, "pk_multiscale_merge: %d scales (1 to 8)", S);
+    PK_REQUIRE(B > 0 && K > 0 && H > 0 && W > 0 && (int64_t)B * K < 0x7fffffff && (int64_t)H * W < 0x7fffffff,
+               "pk_multiscale_merge: bad shape B=%d K=%d H=%d W=%d", B, K, H, W);
+    MsInv inv = {};
+    for (int s = 0; s < S; ++s) {
+        PK_REQUIRE(inv_scales_host[s] > 0.f && inv_scales_host[s] < INFINITY, "pk_multiscale_merge: inverse scale %d is %g (finite, > 0)", s,
+                   (double)inv_scales_host[s]);
+        inv.v[s] = inv_scales_host[s];
+    }
+    const hipStream_t st = (hipStream_t)stream;
+    switch (S) {
+        case 1: multiscale_merge_launch<1>(stack, partner, out, inv, F, B, K, H, W, st); break;
+        case 2: multiscale_merge_launch<2>(stack, partner, out, inv, F, B, K, H, W, st); break;
+        case 3: multiscale_merge_launch<3>(stack, partner, out, inv, F, B, K, H, W, st); break;
+        case 4: multiscale_merge_launch<4>(stack, partner, out, inv, F, B, K, H, W, st); break;
+        case 5: multiscale_merge_launch<5>(stack, partner, out, inv, F, B, K, H, W, st); break;
+        case 6: multiscale_merge_launch<6>(stack, partner, out, inv, F, B, K, H, W, st); break;
+        case 7: multiscale_merge_launch<7>(stack, partner, out, inv, F, B, K, H, W, st); break;
+        default: multiscale_merge_launch<8>(stack, partner, out, inv, F, B, K, H, W, st); break;
+    }
+    return pk_launch_status("pk_multiscale_merge");
+}
+
 // ================================================================================================ video post-processing
 // utils/postprocess.py::temporal_smoothing (:187-223): per joint coordinate, edge-padded trajectory convolved (np.convolve,
 // i.e. with the kernel FLIPPED) with `w` weights, evaluated in float64 and stored as float32 like the reference's

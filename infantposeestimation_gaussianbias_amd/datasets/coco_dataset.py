@@ -14,7 +14,8 @@ import numpy as np
 import torch
 
 from .generate_heatmap import generate_target
-from .transforms import Compose, DeviceCropper, get_train_transforms, get_val_transforms
+from ..configs.config import check_test_scales
+from .transforms import Compose, DeviceCropper, get_train_transforms, get_val_transforms, multiscale_matrices
 
 
 class COCOPoseDataset(torch.utils.data.Dataset):
@@ -81,10 +82,17 @@ class DeviceBatcher:
 
     Prefetch (the role of the reference's DataLoader workers + pin_memory, coco_dataset.py:253-306): batch n + 1 is staged into a pinned
     buffer, copied, cropped / normalised (pk_affine_crop_normalize) and turned into targets (pk_gaussian_target) on a SIDE stream while the
-    consumer's stream runs step n; handing a batch out costs one event wait.  `prefetch=False` does the same work on the consumer's stream."""
+    consumer's stream runs step n; handing a batch out costs one event wait.  `prefetch=False` does the same work on the consumer's stream.
 
-    def __init__(self, loader, cfg, device="cuda", prefetch=True, nchw=True):
+    `test_scales` (a validation loader's multi-scale test; exactly one entry 1.0): every sample is cropped once per scale -- box scale
+    `scale * s` around the same centre, un-rotated (`multiscale_matrices`) -- in ONE cropper call over the B uploaded images; the batch
+    gains `img_scales` (S,B,3,H,W) in list order, and `img` / `img_nhwc8` are its scale-1.0 slice."""
+
+    def __init__(self, loader, cfg, device="cuda", prefetch=True, nchw=True, test_scales=None):
         self.loader, self.cfg, self.device = loader, cfg, torch.device(device)
+        self.test_scales = check_test_scales(test_scales) if test_scales is not None else None
+        if self.test_scales is not None and not nchw:
+            raise ValueError("DeviceBatcher: test_scales needs the fp32 NCHW crops (nchw=True)")
         self.cropper = DeviceCropper(cfg.data.input_size, device, nchw=nchw)
         self.dataset = getattr(loader, "dataset", None)
         self.prefetch = prefetch and torch.cuda.is_available() and self.device.type == "cuda"
@@ -117,12 +125,23 @@ class DeviceBatcher:
 
     def _build(self, samples):
         d = self.cfg.data
-        img32, img16 = self.cropper([s["img"] for s in samples], [s["matrix"] for s in samples], [s.get("flip", False) for s in samples],
-                                    jitter=[s.get("jitter") for s in samples])
+        img_scales = None
+        if self.test_scales is None:
+            img32, img16 = self.cropper([s["img"] for s in samples], [s["matrix"] for s in samples], [s.get("flip", False) for s in samples],
+                                        jitter=[s.get("jitter") for s in samples])
+        else:
+            S, B = len(self.test_scales), len(samples)
+            per = [multiscale_matrices(s["center"], s["scale"], self.test_scales, d.input_size) for s in samples]
+            flips = [s.get("flip", False) for s in samples]
+            all32, all16 = self.cropper([s["img"] for s in samples], [per[b][k] for k in range(S) for b in range(B)], flips * S,
+                                        image_index=list(range(B)) * S)
+            img_scales, base = all32.view(S, B, *all32.shape[1:]), self.test_scales.index(1.0)
+            img32, img16 = img_scales[base], (all16[base * B:(base + 1) * B] if all16 is not None else None)
         kp, vis = self._keypoints_to_device(samples)
         target, weight = generate_target(kp, vis, d.input_size, d.heatmap_size, d.sigma)
         f32 = lambda k: torch.from_numpy(np.stack([np.asarray(s[k], np.float32) for s in samples]))
-        return {"img": img32, "img_nhwc8": img16, "target": target, "target_weight": weight, "keypoints": kp, "keypoints_visible": vis,
+        batch = {} if img_scales is None else {"img_scales": img_scales}
+        return {**batch, "img": img32, "img_nhwc8": img16, "target": target, "target_weight": weight, "keypoints": kp, "keypoints_visible": vis,
                 "meta": {"image_id": torch.tensor([int(s["image_id"]) for s in samples]), "ann_id": torch.tensor([int(s["ann_id"]) for s in samples]),
                          "center": f32("center"), "scale": f32("scale"), "bbox": f32("bbox"),
                          "area": torch.tensor([float(s["area"]) for s in samples])}}
@@ -168,4 +187,4 @@ def build_coco_dataloader(cfg, is_train: bool = True, device="cuda"):
                          d.heatmap_size, d.sigma, d.num_keypoints, tf, is_train, d.flip_pairs)
     loader = torch.utils.data.DataLoader(ds, batch_size=t.batch_size, shuffle=is_train, num_workers=t.num_workers, collate_fn=collate_records,
                                          drop_last=is_train, persistent_workers=t.num_workers > 0)
-    return DeviceBatcher(loader, cfg, device)
+    return DeviceBatcher(loader, cfg, device, test_scales=None if is_train else getattr(cfg, "test_scales", None))

@@ -58,6 +58,13 @@ def get_affine_matrix(center, scale, output_size, rot: float = 0.0) -> np.ndarra
     return np.linalg.solve(a, b).reshape(2, 3)
 
 
+def multiscale_matrices(center, scale, scales, input_size) -> List[np.ndarray]:
+    """The crop matrices of a multi-scale test: per entry s of `scales` the un-rotated crop of box scale `scale * s` around the same
+    centre.  An input pixel u of the scale-1.0 crop lies at W/2 + (u - W/2) / s in the scale-s crop (what pk_multiscale_merge undoes)."""
+    scale = np.asarray(scale)
+    return [get_affine_matrix(center, scale * s, input_size, 0) for s in scales]
+
+
 def invert_affine(m) -> np.ndarray:
     """Destination -> source matrix exactly as cv::warpAffine derives it (float64)."""
     m = np.asarray(m, np.float64).copy().reshape(6)

@@ -9,6 +9,7 @@ import torch
 
 from . import _lib
 from ._lib import call, stream_ptr
+from .configs.config import check_test_scales
 
 F32, I32 = torch.float32, torch.int32
 
@@ -175,6 +176,29 @@ def flip_merge(hm, hm_from_flipped, partner):
     B, K, H, W = a.shape
     out = torch.empty_like(a)
     _call_if(B * K, "pk_flip_merge", a, b, _chk(partner, I32), out, B, K, H, W, stream_ptr())
+    return out
+
+
+def multiscale_merge(stack, scales, B, partner=None, flip=False):
+    """Multi-scale (flip) test merge, pk_multiscale_merge: stack (S*F*B, K, H, W) pass-major (pass s*F + f; f = 1 the mirrored crop's
+    forward, F = 2 with `flip`), `scales` in pass order -> (B, K, H, W) in the frame of the scale-1.0 crop."""
+    try:
+        sc = check_test_scales(scales)
+    except ValueError as e:
+        raise _lib.PoseKernelError(f"multiscale_merge: {e}") from None
+    S, F, B = len(sc), 2 if flip else 1, int(B)
+    if not isinstance(stack, torch.Tensor) or stack.dim() != 4 or B < 0 or stack.shape[0] != S * F * B:
+        raise _lib.PoseKernelError(f"multiscale_merge: stack {tuple(getattr(stack, 'shape', ()))} is not (S*F*B = {S}*{F}*{B}, K, H, W)")
+    st = _chk(stack, name="stack")
+    if flip and partner is None:
+        raise _lib.PoseKernelError("multiscale_merge: flip needs the partner table")
+    K, H, W = st.shape[1:]
+    if flip and _chk(partner, I32, "partner").numel() != K:
+        raise _lib.PoseKernelError(f"multiscale_merge: partner has {partner.numel()} entries for K = {K}")
+    inv = np.array([1.0 / s for s in sc], np.float64).astype(np.float32)      # float32(1 / float64(scale)); copied into the launch
+    out = torch.empty(B, K, H, W, dtype=F32, device=st.device)
+    _call_if(B * K * H * W, "pk_multiscale_merge", st, _chk(partner, I32, "partner") if flip else None, inv.ctypes.data, out, S, F, B, K, H, W,
+             stream_ptr())
     return out
 
 

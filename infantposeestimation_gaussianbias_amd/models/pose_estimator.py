@@ -7,6 +7,7 @@ import torch.nn as nn
 
 from .. import hipops
 from .. import dispatch as nnops
+from ..configs.config import check_test_scales
 from .fusion_head import FusionPoseLoss, HeatmapRegressionHead, SoftArgmax2D
 from .hrformer import hrformer_base, hrformer_small
 from .hrnet import hrnet_w18, hrnet_w32, hrnet_w48
@@ -136,6 +137,34 @@ class PoseEstimator(nn.Module):
             if flip and flip_pairs is not None:
                 hm_f = self.forward(torch.flip(x, dims=[-1]))["heatmaps"]
                 hm = hipops.flip_merge(hm, hm_f, self._flip_partner(flip_pairs, hm.device))
+        if self.head_type == "fusion":
+            o = dict(out)
+            o["heatmaps"] = hm
+            return self.head.decode(o, apply_offset=True)
+        return self.decode_heatmaps(hm)
+
+    @torch.no_grad()
+    def inference_multiscale(self, xs, scales, flip: bool = True, flip_pairs: Optional[list] = None):
+        """Multi-scale (flip) test -> keypoints (B,K,2) heat-px of the scale-1.0 crop, scores (B,K).  `xs`: (S,B,3,H,W) or a list of S
+        (B,3,H,W) crops of the same centres with box scale `scales[s] * scale`, in the order of `scales` (exactly one entry 1.0).  Eval mode
+        only: the S * F passes are ONE forward over S*F*B samples, pass s*F + f in rows [(s*F + f) B, (s*F + f + 1) B), f = 1 the mirrored
+        crop -- batch statistics would couple them.  The heatmaps are merged in the base crop's frame (pk_multiscale_merge); the fusion
+        head's offsets, variances and fusion_weight are those of the scale-1.0 un-flipped pass (the reference's flip-test rule, extended)."""
+        if self.training:
+            raise RuntimeError("inference_multiscale needs eval mode: in training mode batch statistics would couple the passes")
+        sc = check_test_scales(scales)
+        if not torch.is_tensor(xs):
+            xs = torch.stack(list(xs), 0)
+        if xs.dim() != 5 or xs.shape[0] != len(sc):
+            raise ValueError(f"inference_multiscale: {len(sc)} scales need crops (S,B,3,H,W) with S = {len(sc)}, got {tuple(xs.shape)}")
+        S, B = xs.shape[:2]
+        do_flip = bool(flip and flip_pairs is not None)
+        F = 2 if do_flip else 1
+        stack = torch.stack([xs, torch.flip(xs, dims=[-1])], 1) if do_flip else xs
+        every = self.forward(stack.reshape(S * F * B, *xs.shape[2:]))
+        r0 = sc.index(1.0) * F * B
+        out = {k: (v[r0:r0 + B] if torch.is_tensor(v) and v.dim() > 0 and v.shape[0] == S * F * B else v) for k, v in every.items()}
+        hm = hipops.multiscale_merge(every["heatmaps"].float(), sc, B, self._flip_partner(flip_pairs, xs.device) if do_flip else None, do_flip)
         if self.head_type == "fusion":
             o = dict(out)
             o["heatmaps"] = hm

@@ -6,6 +6,8 @@ Pre- and post-processing run on the device: the BGR -> RGB swap, the affine crop
 mean/std normalisation of inference.py:64-110 are ONE kernel per batch (pk_affine_crop_normalize, OpenCV's 8-bit warpAffine arithmetic
 as restated in oracle/warp.py), the model's flip-test inference and decode follow (PoseEstimator.inference), and the heat-px -> image
 mapping of inference.py:142-175 is one kernel (pk_affine_coords).  `predict_batch` really batches (the reference loops over predict).
+With `scales` (`--scales 0.8 1.0 1.2`, or the config's `test_scales`) every person is cropped once per scale -- all crops of a call in ONE
+cropper launch, each image uploaded once -- and the passes are merged on the device (PoseEstimator.inference_multiscale).
 Visualisation is on the device too: `visualize` / `visualize_batch` draw through utils/visualization.py (pk_draw_shapes,
 pk_heatmap_overlay, pk_heatmap_overlay_patches: this project's own integer rasterisation rule, not OpenCV's pixels) and files are written
 with Pillow.
@@ -22,19 +24,25 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from infantposeestimation_gaussianbias_amd.configs import get_config  # noqa: E402
-from infantposeestimation_gaussianbias_amd.datasets.transforms import DeviceCropper, get_affine_matrix  # noqa: E402
+from infantposeestimation_gaussianbias_amd.configs.config import check_test_scales  # noqa: E402
+from infantposeestimation_gaussianbias_amd.datasets.transforms import DeviceCropper, get_affine_matrix, multiscale_matrices  # noqa: E402
 from infantposeestimation_gaussianbias_amd.models import build_model  # noqa: E402
 from infantposeestimation_gaussianbias_amd.utils.postprocess import heatmap_to_image_coords  # noqa: E402
 from infantposeestimation_gaussianbias_amd.utils.visualization import COCO_SKELETON, draw_poses, draw_skeleton, write_image  # noqa: E402
 
 
 class PoseInference:
-    def __init__(self, checkpoint: Optional[str] = None, device: str = 'cuda', flip_test: bool = True, config: Optional[str] = None):
+    scales = None       # multi-scale test off unless __init__ is given (or finds in the config) a scale list
+
+    def __init__(self, checkpoint: Optional[str] = None, device: str = 'cuda', flip_test: bool = True, config: Optional[str] = None,
+                 scales=None):
         if not torch.cuda.is_available():
             raise RuntimeError("PoseInference needs an MI355X: the hot path has no CPU implementation")
         self.device = torch.device(device)
         self.flip_test = flip_test
         self.cfg = get_config(config) if config else get_config()
+        scales = scales if scales is not None else getattr(self.cfg, "test_scales", None)
+        self.scales = check_test_scales(scales) if scales is not None else None          # None: one crop per person
         self.model = build_model(self.cfg).to(self.device).eval()
         if checkpoint and os.path.isfile(checkpoint):
             ckpt = torch.load(checkpoint, map_location="cpu", weights_only=True)
@@ -60,6 +68,21 @@ class PoseInference:
         x, _ = self._crop(imgs, mats, None, bgr=True)
         return x, np.stack([c for c, _ in cs]), np.stack([s for _, s in cs])
 
+    def _crops_multiscale(self, imgs, cs, image_index):
+        """The S crops of every (center, scale) in ONE cropper call, each image staged and uploaded once -> (S, P, 3, H, W) in the order
+        of `self.scales`."""
+        S, P = len(self.scales), len(cs)
+        per = [multiscale_matrices(c, s, self.scales, self.input_size) for c, s in cs]
+        x, _ = self._crop(imgs, [per[p][k] for k in range(S) for p in range(P)], None, bgr=True, image_index=list(image_index) * S)
+        return x.view(S, P, *x.shape[1:])
+
+    def _infer(self, x):
+        """Crops (P,3,H,W), or (S,P,3,H,W) with scales -> heat-px keypoints and scores of the model's (multi-scale) flip-test inference."""
+        pairs = self.flip_pairs if self.flip_test else None
+        if self.scales is not None:
+            return self.model.inference_multiscale(x, self.scales, flip=self.flip_test, flip_pairs=pairs)
+        return self.model.inference(x, flip=self.flip_test, flip_pairs=pairs)
+
     def preprocess(self, img: np.ndarray, bbox: Optional[np.ndarray] = None):
         x, c, s = self.preprocess_batch([img], [bbox])
         return x, c[0], s[0]
@@ -77,11 +100,13 @@ class PoseInference:
 
     @torch.no_grad()
     def predict_batch(self, imgs: List[np.ndarray], bboxes: Optional[List[np.ndarray]] = None) -> List[Tuple[np.ndarray, np.ndarray]]:
-        x, centers, scales = self.preprocess_batch(imgs, bboxes)
-        if self.flip_test:
-            kp, sc = self.model.inference(x, flip=True, flip_pairs=self.flip_pairs)
+        if self.scales is None:
+            x, centers, scales = self.preprocess_batch(imgs, bboxes)
         else:
-            kp, sc = self.model.inference(x, flip=False)
+            cs = [self._center_scale(im, bboxes[i] if bboxes else None) for i, im in enumerate(imgs)]
+            x = self._crops_multiscale(imgs, cs, range(len(imgs)))
+            centers, scales = np.stack([c for c, _ in cs]), np.stack([s for _, s in cs])       # of the scale-1.0 crop: the merge's frame
+        kp, sc = self._infer(x)
         kp_img, _ = self.postprocess(kp, sc, centers, scales)
         sc = sc.cpu().numpy()
         return [(kp_img[i], sc[i]) for i in range(len(imgs))]
@@ -91,23 +116,27 @@ class PoseInference:
         """Every person of ONE image: the image is staged and uploaded once and all crops read it (`DeviceCropper(image_index=)`;
         `predict_batch([img] * len(bboxes), bboxes)` sends it once per person and gives the same numbers).  -> the per-person
         [(keypoints, scores)]; with `return_heatmaps` also the heatmaps (P, K, h, w) of the un-flipped pass (one more forward) and the
-        centers and scales (P, 2) of the crops, which is what `visualize_batch(heatmaps=, heatmap_centers=, heatmap_scales=)` takes."""
+        centers and scales (P, 2) of the crops, which is what `visualize_batch(heatmaps=, heatmap_centers=, heatmap_scales=)` takes.
+        With scales the S * P crops still cost one upload and one cropper launch; the returned heatmaps stay those of the un-flipped
+        scale-1.0 pass."""
         if len(bboxes) == 0:
             raise ValueError("predict_persons: no boxes")
         cs = [self._center_scale(img, bb) for bb in bboxes]
-        mats = [get_affine_matrix(c, s, self.input_size, 0) for c, s in cs]
-        x, _ = self._crop([img], mats, None, bgr=True, image_index=[0] * len(bboxes))
-        centers, scales = np.stack([c for c, _ in cs]), np.stack([s for _, s in cs])
-        if self.flip_test:
-            kp, sc = self.model.inference(x, flip=True, flip_pairs=self.flip_pairs)
+        if self.scales is None:
+            mats = [get_affine_matrix(c, s, self.input_size, 0) for c, s in cs]
+            x, _ = self._crop([img], mats, None, bgr=True, image_index=[0] * len(bboxes))
+            base = x
         else:
-            kp, sc = self.model.inference(x, flip=False)
+            x = self._crops_multiscale([img], cs, [0] * len(bboxes))
+            base = x[self.scales.index(1.0)]
+        centers, scales = np.stack([c for c, _ in cs]), np.stack([s for _, s in cs])
+        kp, sc = self._infer(x)
         kp_img, _ = self.postprocess(kp, sc, centers, scales)
         sc = sc.cpu().numpy()
         results = [(kp_img[i], sc[i]) for i in range(len(bboxes))]
         if not return_heatmaps:
             return results
-        return results, self.model(x)['heatmaps'].float(), centers, scales
+        return results, self.model(base)['heatmaps'].float(), centers, scales
 
     @torch.no_grad()
     def predict(self, img: np.ndarray, bbox: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
@@ -157,7 +186,7 @@ def detect_persons(img: np.ndarray) -> List[np.ndarray]:
 
 def main(args):
     from PIL import Image
-    pose = PoseInference(checkpoint=args.checkpoint, device=args.device, flip_test=not args.no_flip, config=args.config)
+    pose = PoseInference(checkpoint=args.checkpoint, device=args.device, flip_test=not args.no_flip, config=args.config, scales=args.scales)
     rgb = np.asarray(Image.open(args.input).convert("RGB"))
     img = rgb[:, :, ::-1].copy()                          # the reference hands BGR (cv2.imread) to PoseInference
     bboxes = [np.array(args.bbox)] if args.bbox else detect_persons(img)
@@ -191,6 +220,9 @@ if __name__ == '__main__':
     p.add_argument('--threshold', type=float, default=0.3)
     p.add_argument('--bbox', type=float, nargs=4, default=None)
     p.add_argument('--config', type=str, default=None)
+    p.add_argument('--scales', type=float, nargs='+', default=None,
+                   help='multi-scale test: box-scale factors of the crops per person, exactly one of them 1.0 (e.g. 0.8 1.0 1.2); '
+                        'default: the config\'s test_scales (none: single scale)')
     p.add_argument('--draw_bbox', action='store_true', help='also draw the person boxes into --output')
     p.add_argument('--draw_heatmaps', action='store_true',
                    help='also overlay the predicted heatmaps (alpha 0.3) into --output: each person\'s map where that person\'s crop lies in '

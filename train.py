@@ -10,6 +10,7 @@ log interval), bf16 instead of fp16+GradScaler, fused AdamW over a flat paramete
 loader yields device-resident synthetic batches (no COCO on disk needed; they are not jittered).
 """
 import argparse
+import copy
 import logging
 import os
 import sys
@@ -108,7 +109,10 @@ def main(args):
         if rank == 0 and ((epoch + 1) % cfg.train.val_interval == 0 or epoch == cfg.train.max_epochs - 1):
             # validation inside the training loop (train.py:231-325, 437-452 of the reference): AP decides `best.pth`
             from validate import validate
-            val_loader = val_loader or build_dataloader(cfg, is_train=False)
+            if val_loader is None:
+                val_cfg = copy.copy(cfg)
+                val_cfg.test_scales = None           # this monitor stays single-scale and un-flipped; validate.py runs the multi-scale test
+                val_loader = build_dataloader(val_cfg, is_train=False)
             metrics, _ = validate(model, val_loader, torch.device("cuda", local), cfg, logger, flip_test=False)
             model.train()
             is_best = metrics["AP"] > best_ap

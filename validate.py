@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Validation script (drop-in for the reference's validate.py: --checkpoint --data_root --batch_size --no_flip).
+"""Validation script (drop-in for the reference's validate.py: --checkpoint --data_root --batch_size --no_flip; plus --scales for the
+multi-scale test: predictions from `PoseEstimator.inference_multiscale` over the loader's `img_scales`, the loss still on `img`).
 
 Flip-test inference + decode run entirely on the GPU (`PoseEstimator.inference`: two forwards, one flip-merge kernel, one
 decode kernel); the heat-px -> image transform of validate.py:100-117 is one kernel (`heatmap_to_image_coords`) instead of a
@@ -17,6 +18,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from infantposeestimation_gaussianbias_amd.configs import get_config  # noqa: E402
+from infantposeestimation_gaussianbias_amd.configs.config import check_test_scales  # noqa: E402
 from infantposeestimation_gaussianbias_amd.datasets import build_dataloader  # noqa: E402
 from infantposeestimation_gaussianbias_amd.models import build_model  # noqa: E402
 from infantposeestimation_gaussianbias_amd.utils import AverageMeter  # noqa: E402
@@ -24,11 +26,12 @@ from infantposeestimation_gaussianbias_amd.utils.postprocess import heatmap_to_i
 
 
 @torch.no_grad()
-def validate(model, loader, device, cfg, logger, flip_test=True):
+def validate(model, loader, device, cfg, logger, flip_test=True, scales=None):
     """train.py:231-325 == validate.py:39-140 of the reference: loss + decode + image-space transform + COCOEvaluator.update per batch,
     then AP.  Decode, flip merge, the heat-px -> image transform and the evaluator's record arrays are kernels (no B x K Python loops, one
     device->host copy per batch).  AP / AR come from COCOKeypointEval when the loader's dataset has an annotation file; otherwise AP is the
-    reference's own OKS matching against the batch's ground truth mapped to image space (synthetic loaders carry no annotation file)."""
+    reference's own OKS matching against the batch's ground truth mapped to image space (synthetic loaders carry no annotation file).
+    `scales`: multi-scale test over `batch["img_scales"]` (the loader must have been built with the same `test_scales`)."""
     from infantposeestimation_gaussianbias_amd.utils import COCOEvaluator
     model.eval()
     loss_meter = AverageMeter("Loss", ":.4f")
@@ -38,7 +41,14 @@ def validate(model, loader, device, cfg, logger, flip_test=True):
     gts = []
     for i, batch in enumerate(loader):
         imgs = batch["img"].to(device)
-        kp, sc = model.inference(imgs, flip=bool(flip_test and flip_pairs), flip_pairs=flip_pairs)
+        if scales is None:
+            kp, sc = model.inference(imgs, flip=bool(flip_test and flip_pairs), flip_pairs=flip_pairs)
+        else:
+            if batch.get("img_scales") is None or batch["img_scales"].shape[0] != len(scales):
+                raise RuntimeError(f"validate: multi-scale test over {tuple(scales)} needs a loader that yields batch['img_scales'] with one "
+                                   "slice per scale (the COCO loader built from a config with the same test_scales); this loader does not, "
+                                   "and there is no single-scale fallback")
+            kp, sc = model.inference_multiscale(batch["img_scales"].to(device), scales, flip=bool(flip_test and flip_pairs), flip_pairs=flip_pairs)
         gt_kp = batch["keypoints"].to(device) if batch.get("keypoints") is not None else None
         out = model(imgs, batch["target"].to(device), batch["target_weight"].to(device), gt_keypoints=gt_kp, input_size=cfg.data.input_size)
         loss_meter.update(float(out["loss"]), imgs.size(0))
@@ -70,13 +80,15 @@ def main(args):
         cfg.data.data_root = args.data_root
     if args.batch_size:
         cfg.train.batch_size = args.batch_size
+    if args.scales:
+        cfg.test_scales = check_test_scales(args.scales)
     device = torch.device("cuda")
     loader = build_dataloader(cfg, is_train=False)
     model = build_model(cfg).to(device)
     ckpt = torch.load(args.checkpoint, map_location="cpu", weights_only=True)
     model.load_state_dict(ckpt["model_state_dict"])
     logger.info(f"Loaded checkpoint from epoch {ckpt.get('epoch', 'unknown')}")
-    metrics, _ = validate(model, loader, device, cfg, logger, flip_test=not args.no_flip)
+    metrics, _ = validate(model, loader, device, cfg, logger, flip_test=not args.no_flip, scales=cfg.test_scales)
     logger.info(f"Loss: {metrics['loss']:.4f}")
     return metrics
 
@@ -88,4 +100,6 @@ if __name__ == "__main__":
     p.add_argument("--batch_size", type=int, default=32)
     p.add_argument("--no_flip", action="store_true")
     p.add_argument("--config", type=str, default=None)
+    p.add_argument("--scales", type=float, nargs="+", default=None,
+                   help="multi-scale test: box-scale factors of the crops per sample, exactly one of them 1.0 (default: the config's test_scales)")
     main(p.parse_args())
