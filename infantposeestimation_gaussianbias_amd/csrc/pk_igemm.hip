@@ -608,7 +608,9 @@ __device__ __forceinline__ void igemm2_body(const IgemmArgs& p_in, const int bid
         static_assert(BM % STAT_ROWS == 0 && WM % GROUPS == 0, "statistics tiles must be whole wave rows");
         for (int e = tid; e < BN * GROUPS; e += 256) {       // (BN * GROUPS may exceed the 256 threads of the workgroup)
             const int g = e / BN, nl = e % BN;
-            if (n0 + nl >= p.N) continue;
+            // a group whose 128 rows all lie at or beyond M has no statistics row (M % 256 in (0, 128] on the 256-row tile: the buffer ends
+            // at ceil(M / 128) rows) -- the guard of k_conv8p
+            if (n0 + nl >= p.N || m0 + g * STAT_ROWS >= p.M) continue;
             float s = 0.f, q = 0.f;
 #pragma unroll
             for (int w = 0; w < WPG; ++w) {

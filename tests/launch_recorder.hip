@@ -138,6 +138,30 @@ template <class F> static void for_each_geo(bool with_dilated, F f) {
         for (int dil = 0; dil <= (with_dilated ? 1 : 0); ++dil) f(geo(B, hw[0], hw[1], ci, co, k, s, dil));
 }
 
+// The calls behind the problem lines (the line's head is emitted by the caller).  Option values beyond the sweeps' are for the case mode:
+// ad / re 2: addend / residual 8 bytes off a 16-byte boundary; maps 2: a_rowmap only, 3: o_rowmap only; pg 3: preact_out 8 bytes off;
+// re (linear): residual with a per-sample scale.
+static void conv_call(const Geo& g, int st, int ad, int bi, int act, int om, int oa) {
+    finish(pk_conv2d_nhwc(fake<void>(X_), fake<void>(W_), fake<void>(OUT_, oa ? 8 : 0), st ? fake<float>(STATS_) : nullptr,
+                          bi ? fake<float>(BIAS_, bi == 2 ? 4 : 0) : nullptr, g.B, g.Hs, g.Ws, g.Cin, g.Cout, g.k, g.s, g.dil, g.Ho, g.Wo,
+                          act, om, ad ? fake<void>(RES_, ad == 2 ? 8 : 0) : nullptr, STREAM));
+    emit(" rows=%d", pk_conv_stats_rows(g.B, g.Hs, g.Ws, g.Cin, g.Cout, g.k, g.s, g.Ho, g.Wo));
+    flush_line();
+}
+static void affine_call(const Geo& g, int re, int sc, int relu, int oa) {
+    finish(pk_conv2d_affine_nhwc(fake<void>(X_), fake<void>(W_), fake<void>(OUT_, oa ? 8 : 0), sc ? fake<float>(SCALE_, sc == 2 ? 4 : 0) : nullptr,
+                                 sc ? fake<float>(BIAS_, sc == 2 ? 4 : 0) : nullptr, re ? fake<void>(RES_, re == 2 ? 8 : 0) : nullptr, relu, g.B, g.Hs, g.Ws,
+                                 g.Cin, g.Cout, g.k, g.s, g.Ho, g.Wo, STREAM));
+    flush_line();
+}
+static void linear_call(int M, int N, int K, int maps, int pg, int act, int f32, int re, int rps) {
+    finish(pk_linear_bf16(fake<void>(X_), fake<void>(W_), fake<void>(OUT_), fake<float>(BIAS_), re ? fake<void>(RES_, re == 2 ? 8 : 0) : nullptr,
+                          re ? fake<float>(SCALE_) : nullptr, maps == 1 || maps == 2 ? fake<int32_t>(MAP_) : nullptr,
+                          maps == 1 || maps == 3 ? fake<int32_t>(MAP_, 0x1000000) : nullptr, pg == 1 || pg == 3 ? fake<void>(PRE_, pg == 3 ? 8 : 0) : nullptr,
+                          pg == 2 ? fake<void>(PRE_) : nullptr, M, N, K, rps, act, f32, STREAM));
+    flush_line();
+}
+
 static void sweep_conv() {
     uint32_t index = 0;
     for_each_geo(true, [&](const Geo& g) {
@@ -148,11 +172,7 @@ static void sweep_conv() {
                 set_switches(sw);
                 emit("conv B=%d %dx%d ci=%d co=%d k=%d s=%d d=%d sw=%d st=%d ad=%d bi=%d act=%d om=%d oa=%d", g.B, g.Hs, g.Ws, g.Cin, g.Cout, g.k, g.s,
                      g.dil, sw, st, ad, bi, act, om, oa);
-                finish(pk_conv2d_nhwc(fake<void>(X_), fake<void>(W_), fake<void>(OUT_, oa ? 8 : 0), st ? fake<float>(STATS_) : nullptr,
-                                      bi ? fake<float>(BIAS_, bi == 2 ? 4 : 0) : nullptr, g.B, g.Hs, g.Ws, g.Cin, g.Cout, g.k, g.s, g.dil, g.Ho, g.Wo,
-                                      act, om, ad ? fake<void>(RES_) : nullptr, STREAM));
-                emit(" rows=%d", pk_conv_stats_rows(g.B, g.Hs, g.Ws, g.Cin, g.Cout, g.k, g.s, g.Ho, g.Wo));
-                flush_line();
+                conv_call(g, st, ad, bi, act, om, oa);
             }
     });
     index = 0;
@@ -163,10 +183,7 @@ static void sweep_conv() {
                 if (!core && !sampled(index++, 24)) continue;
                 set_switches(sw);
                 emit("affine B=%d %dx%d ci=%d co=%d k=%d s=%d sw=%d re=%d sc=%d relu=%d oa=%d", g.B, g.Hs, g.Ws, g.Cin, g.Cout, g.k, g.s, sw, re, sc, relu, oa);
-                finish(pk_conv2d_affine_nhwc(fake<void>(X_), fake<void>(W_), fake<void>(OUT_, oa ? 8 : 0), sc ? fake<float>(SCALE_, sc == 2 ? 4 : 0) : nullptr,
-                                             sc ? fake<float>(BIAS_, sc == 2 ? 4 : 0) : nullptr, re ? fake<void>(RES_) : nullptr, relu, g.B, g.Hs, g.Ws,
-                                             g.Cin, g.Cout, g.k, g.s, g.Ho, g.Wo, STREAM));
-                flush_line();
+                affine_call(g, re, sc, relu, oa);
             }
     });
     set_switches(0);
@@ -176,10 +193,7 @@ static void sweep_linear() {
     for (int M : kLinM) for (int N : kLinC) for (int K : kLinC) for (int maps = 0; maps < 2; ++maps) for (int pg = 0; pg < 3; ++pg)
         for (int act = 0; act < 2; ++act) for (int f32 = 0; f32 < 2; ++f32) {
             emit("linear M=%d N=%d K=%d maps=%d pg=%d act=%d f32=%d", M, N, K, maps, pg, act, f32);      // pg: 1 = preact out, 2 = gelu_of in
-            finish(pk_linear_bf16(fake<void>(X_), fake<void>(W_), fake<void>(OUT_), fake<float>(BIAS_), nullptr, nullptr,
-                                  maps ? fake<int32_t>(MAP_) : nullptr, maps ? fake<int32_t>(MAP_, 0x1000000) : nullptr, pg == 1 ? fake<void>(PRE_) : nullptr,
-                                  pg == 2 ? fake<void>(PRE_) : nullptr, M, N, K, 0, act, f32, STREAM));
-            flush_line();
+            linear_call(M, N, K, maps, pg, act, f32, 0, 0);
         }
 }
 
@@ -256,7 +270,73 @@ static void sweep_groups() {
     flush_line();
 }
 
-int main() {
+// ---- case mode: problems from stdin, one per line, in the key=value form of the lines above; one record per input line.
+//   switches sw=S
+//   conv B= HxW ci= co= k= s= d= st= ad= bi= act= om= oa= [Ho= Wo=]          (Ho / Wo: a dilated output size other than the sweep's)
+//   affine B= HxW ci= co= k= s= re= sc= relu= oa=
+//   linear M= N= K= maps= pg= act= f32= [re= rps=]
+//   cgroup n= m=B,Hs,Ws,Cin,Cout,k,s,d,Ho,Wo,stats,scale,res,act ...          (res 2: 8 bytes off a 16-byte boundary)
+static int field(const char* line, const char* key, int dflt) {
+    const size_t n = strlen(key);
+    for (const char* c = line; (c = strstr(c, key)); c += n)
+        if ((c == line || c[-1] == ' ') && c[n] == '=') return atoi(c + n + 1);
+    return dflt;
+}
+static Geo line_geo(const char* line, int dil) {
+    int H = 0, W = 0;
+    for (const char* c = line; (c = strchr(c, ' ')); ) {
+        ++c;
+        if (sscanf(c, "%dx%d", &H, &W) == 2 && H > 0 && W > 0) break;
+    }
+    Geo g = geo(field(line, "B", 1), H, W, field(line, "ci", 8), field(line, "co", 8), field(line, "k", 1), field(line, "s", 1), dil);
+    g.Ho = field(line, "Ho", g.Ho); g.Wo = field(line, "Wo", g.Wo);
+    return g;
+}
+static int run_cases() {
+    static char line[1 << 14];
+    while (fgets(line, sizeof(line), stdin)) {
+        line[strcspn(line, "\r\n")] = 0;
+        if (!line[0]) continue;
+        emit("%s", line);
+        if (!strncmp(line, "switches ", 9)) {
+            set_switches(field(line, "sw", 0));
+            flush_line();
+        } else if (!strncmp(line, "conv ", 5)) {
+            conv_call(line_geo(line, field(line, "d", 0)), field(line, "st", 0), field(line, "ad", 0), field(line, "bi", 0), field(line, "act", 0),
+                      field(line, "om", 0), field(line, "oa", 0));
+        } else if (!strncmp(line, "affine ", 7)) {
+            affine_call(line_geo(line, 0), field(line, "re", 0), field(line, "sc", 1), field(line, "relu", 0), field(line, "oa", 0));
+        } else if (!strncmp(line, "linear ", 7)) {
+            linear_call(field(line, "M", 0), field(line, "N", 0), field(line, "K", 0), field(line, "maps", 0), field(line, "pg", 0), field(line, "act", 0),
+                        field(line, "f32", 0), field(line, "re", 0), field(line, "rps", 0));
+        } else if (!strncmp(line, "cgroup ", 7)) {
+            PkConvDesc d[PK_GROUP_MAX + 1] = {};
+            int n = 0;
+            for (const char* c = line; (c = strstr(c, " m=")) && n <= PK_GROUP_MAX; c += 3, ++n) {
+                int v[14] = {};
+                sscanf(c + 3, "%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d", v, v + 1, v + 2, v + 3, v + 4, v + 5, v + 6, v + 7, v + 8, v + 9, v + 10, v + 11, v + 12, v + 13);
+                PkConvDesc& m = d[n];
+                m.x = fake<void>(X_, n << 20); m.w = fake<void>(W_, n << 20); m.out = fake<void>(OUT_, n << 20);
+                m.B = v[0]; m.Hs = v[1]; m.Ws = v[2]; m.Cin = v[3]; m.Cout = v[4]; m.ksize = v[5]; m.stride = v[6]; m.dilated_input = v[7]; m.Ho = v[8]; m.Wo = v[9];
+                m.stats = v[10] ? fake<float>(STATS_, n << 20) : nullptr;
+                m.col_scale = v[11] ? fake<float>(SCALE_, n << 12) : nullptr;
+                m.bias = v[11] ? fake<float>(BIAS_, n << 12) : nullptr;
+                m.res = v[12] ? fake<void>(RES_, (n << 20) + (v[12] == 2 ? 8 : 0)) : nullptr;
+                m.act = v[13];
+            }
+            finish(pk_conv2d_group(d, n, STREAM));
+            flush_line();
+        } else {
+            emit(" | unknown line type");
+            flush_line();
+            return 2;
+        }
+    }
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc > 1 && !strcmp(argv[1], "--cases")) return run_cases();
     sweep_conv();
     sweep_linear();
     sweep_wgrad();

@@ -69,8 +69,10 @@ class Holder(torch.nn.Module):
 @pytest.mark.parametrize("B,H,W,Cin,Cout,k,s", [(2, 9, 7, 16, 24, 3, 1), (2, 10, 6, 8, 16, 3, 2), (1, 5, 5, 32, 40, 1, 1),
                                                 (3, 11, 13, 40, 136, 3, 1), (2, 7, 9, 24, 32, 3, 2), (4, 64, 48, 32, 256, 3, 1),
                                                 (1, 16, 12, 256, 128, 3, 1), (2, 8, 6, 64, 32, 1, 1),
-                                                # M = 67 200 >= 65 536 with a half-filled last 256-row tile: the 256 x 128 workgroup
-                                                # tile (K >= 576, N % 128 == 0) for forward, and for dgrad in the second case
+                                                # M = 67 200 = 525 row tiles of 128: the 128 x 128 x 64 tile for forward and for the second case's
+                                                # dgrad (the first case's dgrad, N = 64, takes 128 x 64 x 64; the second case's bf16 forward the ring
+                                                # kernel).  The 256 x 128 tile asks for ceil(M / 256) * (N / 128) >= 1024 workgroups, these give
+                                                # 263 and 526: tests/test_gpu_igemm_kernels.py holds that tile, with its half-filled last row tile
                                                 (6, 112, 100, 64, 128, 3, 1), (5, 120, 112, 128, 256, 3, 1),
                                                 # 256 -> 256 / 512 at 3x3: the wide weight-gradient kernel (256 x 256 tile, LDS-DMA ring): a
                                                 # slice shorter than one 32-row step, ragged slices, two n-tiles, stride 2
