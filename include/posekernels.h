@@ -149,6 +149,28 @@ int pk_temporal_smooth(const float* coords, float* out, const double* weights, i
 int pk_nms_pose(const float* preds, const float* maxvals, float* out, uint8_t* keep, int B, int K, float distance_threshold,
                 void* stream);
 
+/* ---- movement analysis and PCK on pose sequences (this project's own specification, DESIGN.md "Movement analysis and PCK": the reference
+ * imports calculate_movement_amplitude / calculate_temporal_consistency from utils.metrics -- examples/quick_start.py:159,
+ * visualization.py:385,441 -- and names PCK in both yamls, and defines none of them).  One launch each; no float atomics; every
+ * floating-point sum in a fixed order, so two runs give identical bits.
+ * pk_pck: pred, gt (N,K,2) f32; vis (N,K) f32; norm (N) f32; thresholds (n_thr) f32, 1 <= n_thr <= 16.  correct (n_thr,K) int64, valid (K)
+ *   int64 and err_sum (K) float64 ACCUMULATE: the caller zeroes them once, every launch adds its batch.  Pair (n,k) counts iff vis > 0,
+ *   norm[n] > 0 and the four coordinates are finite.  Decision in float32, one rounding per operation, no square root:
+ *   dx = px - gx, dy = py - gy, d2 = dx dx + dy dy, r = thr norm, hit iff d2 <= r r.  err_sum[k] += sum_n sqrt((double)d2) / (double)norm[n].
+ * pk_motion_stats: coords (S,T,K,2) f32 image pixels; conf (S,T,K) f32 or NULL; stats (S,K,11) float64, every element written.  Frame t of
+ *   joint k is valid iff both coordinates are finite and (conf == NULL or conf >= min_conf); a step t -> t+1 counts iff both frames are
+ *   valid, a triple iff t-1, t, t+1 are.  Columns: 0 n_valid; 1-4 min_x, max_x, min_y, max_y of the valid frames (0 without one);
+ *   5 amplitude = sqrt((max_x - min_x)^2 + (max_y - min_y)^2); 6 path length = sum over steps of |p[t+1] - p[t]|; 7 n_steps; 8 largest
+ *   step; 9 sum over triples of |(p[t+1] - 2 p[t]) + p[t-1]|; 10 n_triples.  Differences, norms sqrt(dx dx + dy dy) and sums in float64.
+ * pk_position_histogram: edges_x (nbx+1), edges_y (nby+1) float64 ascending, on the device; counts (S,K,nby,nbx) int32, overwritten.  A
+ *   valid frame (as above) falls in bin i with e[i] <= v < e[i+1], the last bin also takes v == e[nb], anything outside [e[0], e[nb]] is
+ *   dropped: np.histogram2d's rule for any edges.  nbx nby <= 16384 (one workgroup's LDS histogram), else PK_ERR_UNSUPPORTED.            */
+int pk_pck(const float* pred, const float* gt, const float* vis, const float* norm, const float* thresholds, int64_t* correct,
+           int64_t* valid, double* err_sum, int N, int K, int n_thr, void* stream);
+int pk_motion_stats(const float* coords, const float* conf, double* stats, int S, int T, int K, float min_conf, void* stream);
+int pk_position_histogram(const float* coords, const float* conf, const double* edges_x, const double* edges_y, int32_t* counts,
+                          int S, int T, int K, int nbx, int nby, float min_conf, void* stream);
+
 /* ---- L1/L2: FusionPoseLoss.forward (models/fusion_head.py:745-806 with :405-559, :637-743) ---------------
  * stats: workspace of B*K*PK_LOSS_STAT floats + B*16*4 floats + 16 floats (see PK_LOSS_WS_FLOATS);
  * losses: 7 floats (heatmap, offset, peak, variance, overlap, shape, total — already multiplied by lambdas).

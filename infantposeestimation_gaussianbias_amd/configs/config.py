@@ -7,7 +7,9 @@ identically.  Extension over the reference: `get_config(path_or_name)` also acce
     `MODEL.IMAGE_SIZE`, `MODEL.HEATMAP_SIZE`, `MODEL.SIGMA`, `TRAIN.*` are mapped onto the dataclass fields, and
     `DATA.COLOR_JITTER.{BRIGHTNESS,CONTRAST,SATURATION}` onto `cfg.train.color_jitter` (a yaml that names it trains with it; a
     missing sub-key reads as 0, and a block that is empty or all zero leaves jitter off), and `ADVANCED.MULTI_SCALE_TEST` /
-    `ADVANCED.SCALE_LIST` onto `cfg.test_scales` (multi-scale test; off unless MULTI_SCALE_TEST is true).
+    `ADVANCED.SCALE_LIST` onto `cfg.test_scales` (multi-scale test; off unless MULTI_SCALE_TEST is true), `EVAL.{METRICS, PCK_THRESHOLD,
+    MIN_KEYPOINT_VISIBILITY}` onto `cfg.eval_metrics` / `pck_threshold` / `min_keypoint_visibility`, `TEMPORAL.*` onto `cfg.temporal` and
+    `CLINICAL.*` onto `cfg.clinical` (movement analysis: utils/metrics.py, `validate.py --pck`, `inference.py --sequence`).
 """
 import math
 import os
@@ -92,6 +94,15 @@ class Config:
     # Multi-scale test (legacy yaml ADVANCED.MULTI_SCALE_TEST + SCALE_LIST, `--scales`): None (one crop per person) or the box-scale factors
     # of the crops whose heatmaps are merged, exactly one of them 1.0.  A plain class attribute like `color_jitter`: same field set.
     test_scales = None
+    # Evaluation and movement analysis (legacy yaml EVAL / TEMPORAL / CLINICAL blocks), plain class attributes as well.  eval_metrics: the
+    # metrics validate.py's command line reports ('PCK' adds PCK at pck_threshold); min_keypoint_visibility: the confidence below which a
+    # frame of a joint does not count in the movement statistics; temporal: None or (window, method) for temporal_smoothing; clinical: None
+    # or {'min_movement', 'max_movement', 'alert_low', 'alert_asymmetry'} (amplitude thresholds in pixels and which flags to raise).
+    eval_metrics = ('AP',)
+    pck_threshold = 0.2
+    min_keypoint_visibility = 0.3
+    temporal = None
+    clinical = None
 
 
 _PRESETS = {
@@ -177,6 +188,23 @@ def _apply_legacy_yaml(cfg: Config, path: str) -> Config:
     if adv.get('MULTI_SCALE_TEST'):
         sl = adv.get('SCALE_LIST')
         cfg.test_scales = check_test_scales(sl) if sl is not None else (1.0,)
+    ev = y.get('EVAL', {}) or {}
+    if ev.get('METRICS') is not None:
+        cfg.eval_metrics = tuple(str(v) for v in ev['METRICS'])
+    if 'PCK_THRESHOLD' in ev:
+        cfg.pck_threshold = float(ev['PCK_THRESHOLD'])
+    if 'MIN_KEYPOINT_VISIBILITY' in ev:
+        cfg.min_keypoint_visibility = float(ev['MIN_KEYPOINT_VISIBILITY'])
+    tp = y.get('TEMPORAL', {}) or {}
+    if tp.get('ENABLED'):
+        window = int(tp.get('WINDOW_SIZE', 5))
+        if window < 1 or window % 2 == 0:
+            raise ValueError(f"TEMPORAL.WINDOW_SIZE must be odd and positive (temporal_smoothing has no even window), got {window}")
+        cfg.temporal = (window, str(tp.get('SMOOTHING_METHOD', 'gaussian')))
+    cl = y.get('CLINICAL', {}) or {}
+    if cl.get('ENABLE_MOVEMENT_TRACKING'):
+        cfg.clinical = {'min_movement': float(cl.get('MIN_MOVEMENT_THRESHOLD', 5.0)), 'max_movement': float(cl.get('MAX_MOVEMENT_THRESHOLD', 200.0)),
+                        'alert_low': bool(cl.get('ALERT_ON_LOW_MOVEMENT', False)), 'alert_asymmetry': bool(cl.get('ALERT_ON_ASYMMETRY', False))}
     cfg.exp_name = os.path.splitext(os.path.basename(path))[0]
     return cfg
 

@@ -460,6 +460,79 @@ def nms_pose(preds, maxvals, distance_threshold=5.0):
     return out, keep.bool().view(B, K, 1)
 
 
+# ------------------------------------------------------------------------------------------------ movement analysis and PCK
+PCK_MAX_THRESHOLDS = 16
+HIST_MAX_BINS = 16384
+
+
+def pck_buffers(num_keypoints, n_thr, device):
+    """Zeroed accumulators of `pck_accumulate`: correct (n_thr, K) int64, valid (K,) int64, err_sum (K,) float64."""
+    return (torch.zeros(n_thr, num_keypoints, dtype=I64, device=device), torch.zeros(num_keypoints, dtype=I64, device=device),
+            torch.zeros(num_keypoints, dtype=F64, device=device))
+
+
+def pck_accumulate(pred, gt, visible, normalizer, thresholds, correct, valid, err_sum):
+    """One batch into the PCK accumulators, in place (pk_pck; no synchronisation).  pred, gt (N,K,2); visible (N,K); normalizer (N,);
+    thresholds (n_thr,) float32 device tensor; correct (n_thr,K) / valid (K,) int64 and err_sum (K,) float64 from `pck_buffers`.
+    Shapes are checked first (ValueError), then every tensor's device and type (PoseKernelError); nothing is launched before both."""
+    if pred.dim() != 3 or pred.shape[-1] != 2:
+        raise ValueError(f"pred: expected (N, K, 2), got {tuple(pred.shape)}")
+    N, K = int(pred.shape[0]), int(pred.shape[1])
+    n_thr = int(thresholds.numel())
+    if gt.shape != pred.shape:
+        raise ValueError(f"gt: expected {tuple(pred.shape)} like pred, got {tuple(gt.shape)}")
+    if tuple(visible.shape) != (N, K):
+        raise ValueError(f"visible: expected {(N, K)}, got {tuple(visible.shape)}")
+    if tuple(normalizer.shape) != (N,):
+        raise ValueError(f"normalizer: expected {(N,)}, got {tuple(normalizer.shape)}")
+    if thresholds.dim() != 1 or not 1 <= n_thr <= PCK_MAX_THRESHOLDS:
+        raise ValueError(f"thresholds: expected 1 to {PCK_MAX_THRESHOLDS} values in one dimension, got {tuple(thresholds.shape)}")
+    if tuple(correct.shape) != (n_thr, K) or tuple(valid.shape) != (K,) or tuple(err_sum.shape) != (K,):
+        raise ValueError(f"accumulators: expected {(n_thr, K)}, {(K,)}, {(K,)}, got {tuple(correct.shape)}, {tuple(valid.shape)}, "
+                         f"{tuple(err_sum.shape)}")
+    for t, name in ((correct, "correct"), (valid, "valid"), (err_sum, "err_sum")):
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: the accumulators are updated in place and must be contiguous")
+    pred, gt = _chk(pred, name="pred"), _chk(gt, name="gt")
+    vis, norm, thr = _chk(visible, name="visible"), _chk(normalizer, name="normalizer"), _chk(thresholds, name="thresholds")
+    correct, valid, err_sum = _chk(correct, I64, "correct"), _chk(valid, I64, "valid"), _chk(err_sum, F64, "err_sum")
+    _call_if(N * K, "pk_pck", pred, gt, vis, norm, thr, correct, valid, err_sum, N, K, n_thr, stream_ptr())
+
+
+def _sequences(coords, conf):
+    """coords (S,T,K,2) and conf (S,T,K) or None: shapes (ValueError), then device and type -> coords, conf, S, T, K."""
+    if coords.dim() != 4 or coords.shape[-1] != 2:
+        raise ValueError(f"coords: expected (S, T, K, 2), got {tuple(coords.shape)}")
+    if conf is not None and conf.shape != coords.shape[:3]:
+        raise ValueError(f"conf: expected {tuple(coords.shape[:3])}, got {tuple(conf.shape)}")
+    coords = _chk(coords, name="coords")
+    conf = None if conf is None else _chk(conf, name="conf")
+    return (coords, conf) + tuple(int(v) for v in coords.shape[:3])
+
+
+def motion_stats(coords, conf=None, min_conf=0.3):
+    """(S,T,K,2) image-pixel trajectories (+ (S,T,K) confidences) -> (S,K,11) float64 per-joint statistics (pk_motion_stats: n_valid,
+    min_x, max_x, min_y, max_y, amplitude, path length, n_steps, largest step, second-difference sum, n_triples)."""
+    coords, conf, S, T, K = _sequences(coords, conf)
+    stats = torch.zeros(S, K, 11, dtype=F64, device=coords.device)
+    _call_if(S * T * K, "pk_motion_stats", coords, conf, stats, S, T, K, float(min_conf), stream_ptr())
+    return stats
+
+
+def position_histogram(coords, edges_x, edges_y, conf=None, min_conf=0.3):
+    """(S,T,K,2) trajectories -> (S,K,nby,nbx) int32 counts of the valid frames per bin of the ascending float64 edges (host arrays or
+    device tensors of nbx + 1 / nby + 1 values), np.histogram2d's rule (pk_position_histogram)."""
+    ex, ey = (e.to(F64) if isinstance(e, torch.Tensor) else torch.from_numpy(np.array(e, dtype=np.float64)) for e in (edges_x, edges_y))
+    if ex.dim() != 1 or ey.dim() != 1 or ex.numel() < 2 or ey.numel() < 2:
+        raise ValueError(f"edges: expected one-dimensional arrays of at least 2 values, got {tuple(ex.shape)} and {tuple(ey.shape)}")
+    coords, conf, S, T, K = _sequences(coords, conf)
+    ex, ey = _chk(ex.to(coords.device), F64, "edges_x"), _chk(ey.to(coords.device), F64, "edges_y")
+    nbx, nby = int(ex.numel()) - 1, int(ey.numel()) - 1
+    counts = torch.zeros(S, K, nby, nbx, dtype=I32, device=coords.device)
+    _call_if(S * T * K, "pk_position_histogram", coords, conf, ex, ey, counts, S, T, K, nbx, nby, float(min_conf), stream_ptr())
+    return counts
+
+
 # ------------------------------------------------------------------------------------------------ overlays
 U8 = torch.uint8
 

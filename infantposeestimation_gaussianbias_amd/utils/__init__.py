@@ -1,5 +1,6 @@
 """Utils module."""
-from .metrics import AverageMeter, COCOEvaluator, MetricLogger
+from .metrics import (AverageMeter, COCOEvaluator, MetricLogger, PCKAccumulator, calculate_movement_amplitude, calculate_pck,
+                      calculate_temporal_consistency, movement_heatmap, movement_report)
 from . import postprocess
 from . import visualization
 from .visualization import (COCO_COLORS, COCO_SKELETON, create_grid_image, draw_bbox, draw_heatmaps, draw_person_heatmaps, draw_poses,
@@ -7,4 +8,5 @@ from .visualization import (COCO_COLORS, COCO_SKELETON, create_grid_image, draw_
 
 __all__ = ['AverageMeter', 'COCOEvaluator', 'MetricLogger', 'postprocess', 'visualization', 'draw_skeleton', 'draw_heatmaps', 'draw_bbox',
            'draw_poses', 'draw_person_heatmaps', 'create_grid_image', 'save_visualization', 'save_person_visualization', 'COCO_SKELETON',
-           'COCO_COLORS']
+           'COCO_COLORS', 'PCKAccumulator', 'calculate_movement_amplitude', 'calculate_pck', 'calculate_temporal_consistency',
+           'movement_heatmap', 'movement_report']

@@ -138,3 +138,161 @@ class MetricLogger:
 
     def __str__(self):
         return self.delimiter.join(f'{k}: {m.avg:.4f}' for k, m in self.meters.items())
+
+
+# ---------------------------------------------------------------------------------------------- movement analysis and PCK
+# The reference imports calculate_movement_amplitude / calculate_temporal_consistency from utils.metrics (examples/quick_start.py:159,
+# visualization.py:385,441) and names PCK in both yamls, and defines none of them: the arithmetic is this project's specification (DESIGN.md
+# "Movement analysis and PCK").  Everything is computed by three kernels (pk_motion_stats, pk_position_histogram, pk_pck); what is left on
+# the host is bookkeeping on the one array that comes back.  Numpy input is uploaded; without a GPU these raise like every other op.
+def _device_f32(x, name):
+    """numpy array or tensor -> (contiguous float32 device tensor, came_as_numpy)."""
+    import torch
+    from .. import _lib
+    if isinstance(x, torch.Tensor):
+        if not x.is_cuda:
+            raise _lib.PoseKernelError(f"{name}: expected a CUDA(HIP) tensor or a numpy array; the kernels have no CPU implementation")
+        return x.float().contiguous(), False
+    if not torch.cuda.is_available():
+        raise _lib.PoseKernelError(f"{name}: expected a CUDA(HIP) device; the kernels have no CPU implementation")
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(x), dtype=np.float32)).to(torch.device("cuda", torch.cuda.current_device())), True
+
+
+def _sequence_in(seq, confidence):
+    """(T,K,2) trajectory and (T,K) / (T,K,1) confidence or None -> device tensors (1,T,K,2), (1,T,K) or None, came_as_numpy."""
+    shape = tuple(seq.shape)
+    if len(shape) != 3 or shape[-1] != 2:
+        raise ValueError(f"sequence: expected (T, K, 2), got {shape}")
+    cshape = None if confidence is None else tuple(confidence.shape)
+    if cshape is not None and cshape not in (shape[:2], shape[:2] + (1,)):
+        raise ValueError(f"confidence: expected {shape[:2]} or {shape[:2] + (1,)}, got {cshape}")
+    coords, as_numpy = _device_f32(seq, "sequence")
+    conf = None if confidence is None else _device_f32(confidence, "confidence")[0].to(coords.device).reshape(1, *shape[:2])
+    return coords[None], conf, as_numpy
+
+
+def _sequence_stats(seq, confidence, min_confidence):
+    from .. import hipops
+    coords, conf, as_numpy = _sequence_in(seq, confidence)
+    return hipops.motion_stats(coords, conf, min_confidence)[0], as_numpy
+
+
+def calculate_movement_amplitude(keypoints_sequence, confidence=None, min_confidence: float = 0.3):
+    """Per-joint movement amplitude (K,) float64 of a (T,K,2) trajectory in pixels: the diagonal of the joint's range of motion,
+    sqrt((max_x - min_x)^2 + (max_y - min_y)^2), over the frames that are finite and (with `confidence` (T,K) or (T,K,1)) at least
+    `min_confidence`; 0 for a joint without such a frame.  numpy in -> numpy out, device tensor in -> device tensor out."""
+    stats, as_numpy = _sequence_stats(keypoints_sequence, confidence, min_confidence)
+    amp = stats[:, 5].contiguous()
+    return amp.cpu().numpy() if as_numpy else amp
+
+
+def _consistency(stats: np.ndarray) -> float:
+    triples = float(stats[:, 10].sum())
+    return float(stats[:, 9].sum()) / triples if triples > 0 else 0.0
+
+
+def calculate_temporal_consistency(keypoints_sequence, confidence=None, min_confidence: float = 0.3) -> float:
+    """Mean second-difference magnitude |p[t+1] - 2 p[t] + p[t-1]| over every joint and every triple of consecutive valid frames, in
+    px / frame^2: lower is smoother.  0.0 when there is no triple."""
+    stats, _ = _sequence_stats(keypoints_sequence, confidence, min_confidence)
+    return _consistency(stats.cpu().numpy())
+
+
+def movement_report(keypoints_sequence, confidence=None, flip_pairs=(), min_confidence: float = 0.3, min_movement: float = 5.0,
+                    max_movement: float = 200.0, asymmetry_threshold: float = 0.2, fps: Optional[float] = None) -> Dict:
+    """JSON-serialisable movement summary of one (T,K,2) trajectory, built from ONE (K,11) device->host copy.  Per joint: amplitude, path
+    length, mean and largest speed (px / frame, or px / s with `fps`), share of valid frames, and the flag 'low' (amplitude below
+    `min_movement`), 'high' (above `max_movement`) or None.  Per (left, right) pair of `flip_pairs`: ratio = |a_L - a_R| / max(a_L, a_R)
+    (0 when both are 0) and asymmetric = ratio > asymmetry_threshold (examples/quick_start.py:242,249 of the reference; 5 / 200 px are
+    its yaml's CLINICAL thresholds)."""
+    stats, _ = _sequence_stats(keypoints_sequence, confidence, min_confidence)
+    return _report_from_stats(stats.cpu().numpy(), int(keypoints_sequence.shape[0]), flip_pairs, min_movement, max_movement,
+                              asymmetry_threshold, fps)
+
+
+def _report_from_stats(st: np.ndarray, n_frames: int, flip_pairs, min_movement, max_movement, asymmetry_threshold, fps) -> Dict:
+    rate = 1.0 if fps is None else float(fps)
+    joints = []
+    for k in range(st.shape[0]):
+        amp, steps = float(st[k, 5]), float(st[k, 7])
+        joints.append({"joint": k, "amplitude": amp, "path_length": float(st[k, 6]),
+                       "mean_speed": float(st[k, 6]) / steps * rate if steps > 0 else 0.0, "max_speed": float(st[k, 8]) * rate,
+                       "valid_fraction": float(st[k, 0]) / n_frames if n_frames > 0 else 0.0,
+                       "flag": "low" if amp < min_movement else ("high" if amp > max_movement else None)})
+    pairs = []
+    for left, right in flip_pairs:
+        a, b = float(st[int(left), 5]), float(st[int(right), 5])
+        ratio = abs(a - b) / max(a, b) if max(a, b) > 0 else 0.0
+        pairs.append({"left": int(left), "right": int(right), "ratio": ratio, "asymmetric": bool(ratio > asymmetry_threshold)})
+    return {"num_frames": n_frames, "fps": None if fps is None else float(fps), "speed_unit": "px/frame" if fps is None else "px/s",
+            "temporal_consistency": _consistency(st), "joints": joints, "pairs": pairs}
+
+
+def movement_heatmap(keypoints_sequence, image_shape, bin_size: int = 10, confidence=None, min_confidence: float = 0.3):
+    """How often each joint was seen where: (K, H // bin_size, W // bin_size) int32 counts of the valid frames of a (T,K,2) trajectory,
+    `image_shape` = (H, W).  Bins as plot_movement_heatmap of the reference takes them (visualization.py:248-252: np.histogram2d over
+    [0, W] x [0, H] with W // 10 x H // 10 bins), rows = y.  `draw_heatmaps(img, counts.float())` overlays the result."""
+    from .. import hipops
+    H, W = int(image_shape[0]), int(image_shape[1])
+    nbx, nby = W // int(bin_size), H // int(bin_size)
+    if int(bin_size) < 1 or nbx < 1 or nby < 1:
+        raise ValueError(f"movement_heatmap: bin_size {bin_size} leaves no bin in an image of {H} x {W}")
+    coords, conf, as_numpy = _sequence_in(keypoints_sequence, confidence)
+    counts = hipops.position_histogram(coords, np.linspace(0, W, nbx + 1), np.linspace(0, H, nby + 1), conf, min_confidence)[0]
+    return counts.cpu().numpy() if as_numpy else counts
+
+
+class PCKAccumulator:
+    """PCK over any number of batches: the share of keypoints within threshold x normaliser of their ground truth.  Holds the three
+    device accumulators of pk_pck; `update` only launches, `compute` is the one synchronising call (one device->host copy)."""
+
+    def __init__(self, num_keypoints: int, thresholds=(0.2,)):
+        from .. import hipops
+        thr = np.asarray(list(thresholds), np.float32).reshape(-1)
+        if not 1 <= thr.size <= hipops.PCK_MAX_THRESHOLDS:
+            raise ValueError(f"PCK: {thr.size} thresholds (1 to {hipops.PCK_MAX_THRESHOLDS})")
+        self.num_keypoints, self.thresholds = int(num_keypoints), tuple(float(t) for t in thresholds)
+        self._thr_host, self._thr, self._buf = thr, None, None
+
+    def reset(self):
+        self._buf = None
+
+    def update(self, pred, gt, visible, normalizer):
+        """pred, gt (N,K,2) in the same space, visible (N,K) (> 0 counts), normalizer (N,) lengths (> 0 counts): numpy or device tensors."""
+        import torch
+        from .. import hipops
+        pred, gt = _device_f32(pred, "pred")[0], _device_f32(gt, "gt")[0]
+        vis, norm = _device_f32(visible, "visible")[0], _device_f32(normalizer, "normalizer")[0]
+        if pred.dim() != 3 or pred.shape[1] != self.num_keypoints:
+            raise ValueError(f"pred: expected (N, {self.num_keypoints}, 2), got {tuple(pred.shape)}")
+        if self._buf is None:
+            self._thr = torch.from_numpy(self._thr_host).to(pred.device)
+            self._buf = hipops.pck_buffers(self.num_keypoints, len(self.thresholds), pred.device)
+        hipops.pck_accumulate(pred, gt, vis.to(pred.device), norm.to(pred.device), self._thr, *self._buf)
+
+    def counts(self):
+        """-> correct (n_thr,K) int64, valid (K,) int64, err_sum (K,) float64 as numpy arrays (zeros before the first update)."""
+        n_thr, K = len(self.thresholds), self.num_keypoints
+        if self._buf is None:
+            return np.zeros((n_thr, K), np.int64), np.zeros(K, np.int64), np.zeros(K, np.float64)
+        import torch
+        flat = torch.cat([self._buf[0].reshape(-1).double(), self._buf[1].double(), self._buf[2]]).cpu().numpy()      # counts < 2^53: exact
+        return flat[:n_thr * K].reshape(n_thr, K).astype(np.int64), flat[n_thr * K:(n_thr + 1) * K].astype(np.int64), flat[(n_thr + 1) * K:]
+
+    def compute(self) -> Dict:
+        """{'PCK@<thr>': mean over the joints with a counted pair of correct / valid, ..., 'per_joint': (n_thr,K) array (NaN for a joint
+        without one), 'mean_error': mean normalised distance over all counted pairs}."""
+        correct, valid, err = self.counts()
+        seen = valid > 0
+        per_joint = np.where(seen[None], correct / np.maximum(valid, 1)[None], np.nan)
+        out = {f"PCK@{t:g}": float(per_joint[j, seen].mean()) if seen.any() else 0.0 for j, t in enumerate(self.thresholds)}
+        out["per_joint"] = per_joint
+        out["mean_error"] = float(err.sum() / valid.sum()) if seen.any() else 0.0
+        return out
+
+
+def calculate_pck(pred, gt, visible, normalizer, thresholds=(0.2,)) -> Dict:
+    """PCK of one set of predictions: `PCKAccumulator(K, thresholds)` with one update."""
+    acc = PCKAccumulator(int(pred.shape[1]), thresholds)
+    acc.update(pred, gt, visible, normalizer)
+    return acc.compute()

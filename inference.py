@@ -8,6 +8,8 @@ as restated in oracle/warp.py), the model's flip-test inference and decode follo
 mapping of inference.py:142-175 is one kernel (pk_affine_coords).  `predict_batch` really batches (the reference loops over predict).
 With `scales` (`--scales 0.8 1.0 1.2`, or the config's `test_scales`) every person is cropped once per scale -- all crops of a call in ONE
 cropper launch, each image uploaded once -- and the passes are merged on the device (PoseEstimator.inference_multiscale).
+`predict_sequence` / `--sequence` take the frames of a video (a directory of images) for one person and keep the trajectory on the device
+for the movement analysis of utils/metrics.py (temporal smoothing, `movement_report`, `movement_heatmap`).
 Visualisation is on the device too: `visualize` / `visualize_batch` draw through utils/visualization.py (pk_draw_shapes,
 pk_heatmap_overlay, pk_heatmap_overlay_patches: this project's own integer rasterisation rule, not OpenCV's pixels) and files are written
 with Pillow.
@@ -27,8 +29,9 @@ from infantposeestimation_gaussianbias_amd.configs import get_config  # noqa: E4
 from infantposeestimation_gaussianbias_amd.configs.config import check_test_scales  # noqa: E402
 from infantposeestimation_gaussianbias_amd.datasets.transforms import DeviceCropper, get_affine_matrix, multiscale_matrices  # noqa: E402
 from infantposeestimation_gaussianbias_amd.models import build_model  # noqa: E402
-from infantposeestimation_gaussianbias_amd.utils.postprocess import heatmap_to_image_coords  # noqa: E402
-from infantposeestimation_gaussianbias_amd.utils.visualization import COCO_SKELETON, draw_poses, draw_skeleton, write_image  # noqa: E402
+from infantposeestimation_gaussianbias_amd.utils.metrics import movement_heatmap, movement_report  # noqa: E402
+from infantposeestimation_gaussianbias_amd.utils.postprocess import heatmap_to_image_coords, temporal_smoothing  # noqa: E402
+from infantposeestimation_gaussianbias_amd.utils.visualization import COCO_SKELETON, draw_heatmaps, draw_poses, draw_skeleton, write_image  # noqa: E402
 
 
 class PoseInference:
@@ -97,6 +100,40 @@ class PoseInference:
         s = torch.as_tensor(np.asarray(scale, np.float32).reshape(-1, 2), device=self.device)
         out = heatmap_to_image_coords(kp, c, s, self.input_size, self.cfg.data.heatmap_size).cpu().numpy()
         return (out[0] if single else out), scores
+
+    def _image_coords(self, keypoints, center, scale):
+        """heat-px keypoints (B,K,2) on the device -> original image coordinates, still on the device (one kernel)."""
+        c = torch.as_tensor(np.asarray(center, np.float32).reshape(-1, 2), device=self.device)
+        s = torch.as_tensor(np.asarray(scale, np.float32).reshape(-1, 2), device=self.device)
+        return heatmap_to_image_coords(keypoints, c, s, self.input_size, self.cfg.data.heatmap_size)
+
+    @torch.no_grad()
+    def predict_sequence(self, frames, bbox: Optional[np.ndarray] = None, batch_size: int = 16):
+        """One person over the frames of a video: frames = list of (H,W,3) BGR uint8 arrays (or one (T,H,W,3) array), `bbox` one
+        (x1, y1, x2, y2) for all of them or None for the whole image -> keypoints (T,K,2) in image pixels and scores (T,K), DEVICE tensors:
+        what `temporal_smoothing`, `movement_report` and `movement_heatmap` take.  The frames go through crop -> inference -> image
+        coordinates in batches of `batch_size`, each computed exactly as `predict_batch` computes it (same numbers, no host round trip)."""
+        frames = list(frames)
+        if not frames:
+            raise ValueError("predict_sequence: no frames")
+        if int(batch_size) < 1:
+            raise ValueError(f"predict_sequence: batch_size {batch_size}")
+        kps, scs = [], []
+        for i in range(0, len(frames), int(batch_size)):
+            part = frames[i:i + int(batch_size)]
+            x, centers, scales = self._crops(part, [bbox] * len(part))
+            kp, sc = self._infer(x)
+            kps.append(self._image_coords(kp, centers, scales))
+            scs.append(sc)
+        return torch.cat(kps), torch.cat(scs)
+
+    def _crops(self, imgs, bboxes):
+        """The network input of `predict_batch` for these images: crops (B,3,H,W), or (S,B,3,H,W) with scales, and the centers and scales
+        (B,2) of the (scale-1.0) crops."""
+        if self.scales is None:
+            return self.preprocess_batch(imgs, bboxes)
+        cs = [self._center_scale(im, bboxes[i] if bboxes else None) for i, im in enumerate(imgs)]
+        return self._crops_multiscale(imgs, cs, range(len(imgs))), np.stack([c for c, _ in cs]), np.stack([s for _, s in cs])
 
     @torch.no_grad()
     def predict_batch(self, imgs: List[np.ndarray], bboxes: Optional[List[np.ndarray]] = None) -> List[Tuple[np.ndarray, np.ndarray]]:
@@ -184,9 +221,57 @@ def detect_persons(img: np.ndarray) -> List[np.ndarray]:
     return [np.array([0, 0, w, h])]
 
 
+_FRAME_SUFFIXES = (".png", ".jpg", ".jpeg", ".bmp")
+
+
+def sequence_report(pose: PoseInference, frames, bbox=None, smooth: Optional[int] = None, fps: Optional[float] = None, batch_size: int = 16):
+    """Movement analysis of one person over `frames` (BGR arrays of one size): `predict_sequence`, temporal smoothing when `smooth` (an odd
+    window, 'gaussian') or the config's `temporal` asks for it, then `movement_report` with the config's visibility and CLINICAL
+    thresholds.  -> (report dict, keypoints (T,K,2) and scores (T,K) on the device, the keypoints as analysed)."""
+    cfg = pose.cfg
+    kp, sc = pose.predict_sequence(frames, bbox, batch_size=batch_size)
+    temporal = (int(smooth), "gaussian") if smooth else getattr(cfg, "temporal", None)
+    if temporal:
+        kp = temporal_smoothing(kp, window_size=temporal[0], method=temporal[1])
+    clinical = getattr(cfg, "clinical", None) or {}
+    report = movement_report(kp, sc, flip_pairs=cfg.data.flip_pairs, min_confidence=cfg.min_keypoint_visibility,
+                             min_movement=clinical.get("min_movement", 5.0), max_movement=clinical.get("max_movement", 200.0), fps=fps)
+    report["smoothing"] = list(temporal) if temporal else None
+    return report, kp, sc
+
+
+def main_sequence(args, pose):
+    """--sequence: --input is a directory of frames (sorted by name), one --bbox for all of them or the whole image."""
+    import json
+    from PIL import Image
+    names = sorted(n for n in os.listdir(args.input) if n.lower().endswith(_FRAME_SUFFIXES))
+    if not names:
+        raise SystemExit(f"--sequence: no image files {_FRAME_SUFFIXES} in {args.input}")
+    frames = [np.asarray(Image.open(os.path.join(args.input, n)).convert("RGB"))[:, :, ::-1].copy() for n in names]
+    if len({f.shape for f in frames}) != 1:
+        raise SystemExit("--sequence: the frames differ in size")
+    bbox = np.array(args.bbox) if args.bbox else None
+    report, kp, sc = sequence_report(pose, frames, bbox, smooth=args.smooth, fps=args.fps)
+    report["frames"] = names
+    text = json.dumps(report, indent=2)
+    if args.report:
+        with open(args.report, "w") as f:
+            f.write(text + "\n")
+        print(f'Movement report saved to: {args.report}')
+    else:
+        print(text)
+    if args.output:
+        counts = movement_heatmap(kp, frames[0].shape[:2], confidence=sc, min_confidence=pose.cfg.min_keypoint_visibility)
+        write_image(draw_heatmaps(frames[0], counts.float()), args.output)
+        print(f'Result saved to: {args.output}')
+    return report
+
+
 def main(args):
     from PIL import Image
     pose = PoseInference(checkpoint=args.checkpoint, device=args.device, flip_test=not args.no_flip, config=args.config, scales=args.scales)
+    if getattr(args, "sequence", False):
+        return main_sequence(args, pose)
     rgb = np.asarray(Image.open(args.input).convert("RGB"))
     img = rgb[:, :, ::-1].copy()                          # the reference hands BGR (cv2.imread) to PoseInference
     bboxes = [np.array(args.bbox)] if args.bbox else detect_persons(img)
@@ -227,4 +312,12 @@ if __name__ == '__main__':
     p.add_argument('--draw_heatmaps', action='store_true',
                    help='also overlay the predicted heatmaps (alpha 0.3) into --output: each person\'s map where that person\'s crop lies in '
                         'the image; for a single whole-image box the map is stretched over the image, as the reference does')
+    p.add_argument('--sequence', action='store_true',
+                   help='--input is a directory of video frames (image files, sorted by name) of one person: predict every frame, then '
+                        'print the movement report (amplitude, path length, speeds, asymmetry, temporal consistency); --output gets the '
+                        'first frame with the movement heat map over it')
+    p.add_argument('--smooth', type=int, default=None, help='--sequence: smooth the trajectory with an odd gaussian window of this many '
+                                                             'frames before the analysis (default: the config\'s TEMPORAL block)')
+    p.add_argument('--fps', type=float, default=None, help='--sequence: frame rate, turns the speeds into pixels per second')
+    p.add_argument('--report', type=str, default=None, help='--sequence: write the movement report (JSON) here instead of printing it')
     main(p.parse_args())

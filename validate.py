@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Validation script (drop-in for the reference's validate.py: --checkpoint --data_root --batch_size --no_flip; plus --scales for the
-multi-scale test: predictions from `PoseEstimator.inference_multiscale` over the loader's `img_scales`, the loss still on `img`).
+multi-scale test: predictions from `PoseEstimator.inference_multiscale` over the loader's `img_scales`, the loss still on `img`; plus
+--pck [THR ...] for PCK next to AP: the share of keypoints within THR x the longer box side of their ground truth, counted on the device).
 
 Flip-test inference + decode run entirely on the GPU (`PoseEstimator.inference`: two forwards, one flip-merge kernel, one
 decode kernel); the heat-px -> image transform of validate.py:100-117 is one kernel (`heatmap_to_image_coords`) instead of a
@@ -26,13 +27,18 @@ from infantposeestimation_gaussianbias_amd.utils.postprocess import heatmap_to_i
 
 
 @torch.no_grad()
-def validate(model, loader, device, cfg, logger, flip_test=True, scales=None):
+def validate(model, loader, device, cfg, logger, flip_test=True, scales=None, pck_thresholds=None):
     """train.py:231-325 == validate.py:39-140 of the reference: loss + decode + image-space transform + COCOEvaluator.update per batch,
     then AP.  Decode, flip merge, the heat-px -> image transform and the evaluator's record arrays are kernels (no B x K Python loops, one
     device->host copy per batch).  AP / AR come from COCOKeypointEval when the loader's dataset has an annotation file; otherwise AP is the
     reference's own OKS matching against the batch's ground truth mapped to image space (synthetic loaders carry no annotation file).
-    `scales`: multi-scale test over `batch["img_scales"]` (the loader must have been built with the same `test_scales`)."""
+    `scales`: multi-scale test over `batch["img_scales"]` (the loader must have been built with the same `test_scales`).
+    `pck_thresholds`: None (nothing added), or thresholds for PCK in image space with the longer side of `meta["bbox"]` (x1 y1 x2 y2 in both
+    loaders) as the normalising length: adds `PCK@<thr>` per threshold and `PCK_mean_error` (mean distance / normaliser) to the metrics.
+    The counts accumulate on the device (`PCKAccumulator`): one device->host copy after the last batch."""
     from infantposeestimation_gaussianbias_amd.utils import COCOEvaluator
+    from infantposeestimation_gaussianbias_amd.utils import metrics as metrics_mod
+    pck = metrics_mod.PCKAccumulator(cfg.data.num_keypoints, pck_thresholds) if pck_thresholds is not None else None
     model.eval()
     loss_meter = AverageMeter("Loss", ":.4f")
     ann = getattr(getattr(loader, "dataset", None), "ann_file", None)
@@ -56,9 +62,18 @@ def validate(model, loader, device, cfg, logger, flip_test=True, scales=None):
         center, scale = meta["center"].to(device).float(), meta["scale"].to(device).float()
         img_kp = heatmap_to_image_coords(kp, center, scale, cfg.data.input_size, cfg.data.heatmap_size)
         evaluator.update(img_kp, sc, meta["image_id"], meta["ann_id"], center, scale, meta["area"], meta["bbox"])
+        if pck is not None and gt_kp is None:
+            raise RuntimeError("validate: PCK needs a loader that yields batch['keypoints'] and batch['keypoints_visible']; this one does not")
+        # ground truth in image space: the same inverse crop transform, applied to the input-pixel keypoints (heatmap size == input size)
+        gimg_dev = None
+        if gt_kp is not None and (pck is not None or ann is None):
+            gimg_dev = heatmap_to_image_coords(gt_kp.float(), center, scale, cfg.data.input_size, cfg.data.input_size)
+        if pck is not None:
+            bb = torch.as_tensor(meta["bbox"]).float().reshape(-1, 4).cpu()
+            norm = torch.maximum(bb[:, 2] - bb[:, 0], bb[:, 3] - bb[:, 1])          # host arithmetic on the loader's metadata, then one upload
+            pck.update(img_kp, gimg_dev, batch["keypoints_visible"].to(device).float(), norm.to(device))
         if ann is None and gt_kp is not None:
-            # ground truth in image space: the same inverse crop transform, applied to the input-pixel keypoints (heatmap size == input size)
-            gimg = heatmap_to_image_coords(gt_kp.float(), center, scale, cfg.data.input_size, cfg.data.input_size).cpu().numpy()
+            gimg = gimg_dev.cpu().numpy()
             vis = batch["keypoints_visible"].cpu().numpy()
             for b in range(gimg.shape[0]):
                 k3 = [[float(gimg[b, k, 0]), float(gimg[b, k, 1]), float(vis[b, k])] for k in range(gimg.shape[1])]
@@ -67,6 +82,10 @@ def validate(model, loader, device, cfg, logger, flip_test=True, scales=None):
             logger.info(f"  [{i}/{len(loader)}] Loss: {loss_meter.avg:.4f}")
     metrics = dict(evaluator.evaluate(gt_annotations=None if ann else gts))
     metrics["loss"] = loss_meter.avg
+    if pck is not None:
+        res = pck.compute()
+        metrics.update({k: v for k, v in res.items() if k.startswith("PCK@")})
+        metrics["PCK_mean_error"] = res["mean_error"]
     logger.info(f"Validation Loss: {loss_meter.avg:.4f}  " + "  ".join(f"{k}: {v:.4f}" for k, v in metrics.items() if k != "loss")
                 + ("" if ann else "  (reference OKS matching against the loader's ground truth: the loader has no annotation file)"))
     return metrics, evaluator.predictions
@@ -88,7 +107,13 @@ def main(args):
     ckpt = torch.load(args.checkpoint, map_location="cpu", weights_only=True)
     model.load_state_dict(ckpt["model_state_dict"])
     logger.info(f"Loaded checkpoint from epoch {ckpt.get('epoch', 'unknown')}")
-    metrics, _ = validate(model, loader, device, cfg, logger, flip_test=not args.no_flip, scales=cfg.test_scales)
+    # --pck alone: the config's pck_threshold; --pck THR ...: those; no flag: PCK only when the config's yaml names it among EVAL.METRICS
+    pck_thresholds = None
+    if getattr(args, "pck", None) is not None:
+        pck_thresholds = tuple(args.pck) or (cfg.pck_threshold,)
+    elif "PCK" in cfg.eval_metrics:
+        pck_thresholds = (cfg.pck_threshold,)
+    metrics, _ = validate(model, loader, device, cfg, logger, flip_test=not args.no_flip, scales=cfg.test_scales, pck_thresholds=pck_thresholds)
     logger.info(f"Loss: {metrics['loss']:.4f}")
     return metrics
 
@@ -102,4 +127,7 @@ if __name__ == "__main__":
     p.add_argument("--config", type=str, default=None)
     p.add_argument("--scales", type=float, nargs="+", default=None,
                    help="multi-scale test: box-scale factors of the crops per sample, exactly one of them 1.0 (default: the config's test_scales)")
+    p.add_argument("--pck", type=float, nargs="*", default=None,
+                   help="also report PCK at these thresholds (fractions of the longer box side; no value: the config's pck_threshold, 0.2); "
+                        "default: only when the config's yaml names 'PCK' in EVAL.METRICS")
     main(p.parse_args())
