@@ -99,6 +99,29 @@ int pk_coco_kpt_eval(const double* oks, const int64_t* oks_off, const int32_t* g
                      const double* iou_thrs, const double* rec_thrs, int32_t* dt_match, uint8_t* dt_ignore, int32_t* npig, int32_t* order,
                      void* ws, double* precision, double* recall, int n_img, int n_gt, int n_cap, int A, int T, int R, void* stream);
 
+/* ---- f1: validation on detector boxes: pose rescoring and OKS-NMS per image (this project's own specification, DESIGN.md "Detector boxes
+ * and OKS-NMS": the reference's yaml says TEST.USE_GT_BBOX: false and its code has neither step).  Everything fp64; no atomics, fixed
+ * orders: two launches give identical bytes.  Poses of all images in CSR form: off (n_img + 1) int32 offsets, kpt (N,K,3) rows
+ * [x, y, keypoint score], area (N), score (N); vars = (2 sigma)^2 (K).  1 <= K <= 64 (else PK_ERR_INVALID).
+ * pk_pose_rescore: score_out[i] = box_score[i] * mean{ s_k : s_k > in_vis_thr }, the sum over k ascending, then one divide and one
+ *   multiply; 0 when no joint qualifies; box_score == NULL means 1.  in_vis_thr may be -inf (every non-NaN score counts), not NaN.
+ * pk_oks_nms: one workgroup per image.  Pose-pair OKS: joint k counts when both poses have a keypoint score > in_vis_thr;
+ *   e_k = (dx^2 + dy^2) / vars_k / ((area_a + area_b) / 2 + 2.220446049250313e-16) / 2; oks = sum_k exp(-e_k) / count over k ascending, 0
+ *   when no joint counts.
+ *   soft == 0: poses are visited by descending score (ties to the lower index, NaN last: pk_coco_kpt_oks's rule); a visited pose that is
+ *     still alive is kept and removes every later alive pose with oks > thr (strict).  max_dets is not read.
+ *   soft != 0 (thr > 0, max_dets > 0): until max_dets poses are kept or none remains, the remaining pose with the highest current score
+ *     (same ordering rule) is selected and every remaining score is multiplied by exp(-oks^2 / thr), oks taken to the selected pose.
+ *   Outputs, every element of an image with poses written: keep (N) uint8; n_keep (n_img) int32; order (N) int32: per image its kept
+ *   local indices in selection order, then -1; out_score (N): the input score (soft == 0) or the score at selection, 0 where not kept.
+ *   At most 1024 poses per image.  The offsets are device memory, so the entry cannot read them: the caller checks them (hipops.oks_nms
+ *   raises with PK_ERR_UNSUPPORTED, naming the image and its count, before anything is launched); a workgroup that meets more writes only
+ *   n_keep = -1 for its image.  A non-finite thr, a NaN in_vis_thr and soft mode with thr <= 0 or max_dets <= 0 are PK_ERR_INVALID.      */
+int pk_pose_rescore(const double* kpt, const double* box_score, double* score_out, int N, int K, double in_vis_thr, void* stream);
+int pk_oks_nms(const double* kpt, const double* area, const double* score, const int32_t* off, const double* vars, uint8_t* keep,
+               int32_t* n_keep, int32_t* order, double* out_score, int n_img, int K, double thr, double in_vis_thr, int soft, int max_dets,
+               void* stream);
+
 /* ---- f2: input pipeline (datasets/transforms.py:42-47,128-131,212-217; datasets/coco_dataset.py:156-163; inference.py:83-110):
  * affine crop (OpenCV 8-bit warpAffine INTER_LINEAR / BORDER_CONSTANT 0 integer algorithm, see oracle/warp.py; parity unpinned vs cv2
  * itself) + optional column mirror + optional BGR->RGB + ((v/255) - mean)/std, whole batch, one launch.  src_u8: device buffer holding the

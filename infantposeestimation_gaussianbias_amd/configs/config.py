@@ -9,8 +9,11 @@ identically.  Extension over the reference: `get_config(path_or_name)` also acce
     missing sub-key reads as 0, and a block that is empty or all zero leaves jitter off), and `ADVANCED.MULTI_SCALE_TEST` /
     `ADVANCED.SCALE_LIST` onto `cfg.test_scales` (multi-scale test; off unless MULTI_SCALE_TEST is true), `EVAL.{METRICS, PCK_THRESHOLD,
     MIN_KEYPOINT_VISIBILITY}` onto `cfg.eval_metrics` / `pck_threshold` / `min_keypoint_visibility`, `TEMPORAL.*` onto `cfg.temporal` and
-    `CLINICAL.*` onto `cfg.clinical` (movement analysis: utils/metrics.py, `validate.py --pck`, `inference.py --sequence`).
+    `CLINICAL.*` onto `cfg.clinical` (movement analysis: utils/metrics.py, `validate.py --pck`, `inference.py --sequence`), and
+    `TEST.{COCO_BBOX_FILE, IMAGE_THRE, OKS_THRE, IN_VIS_THRE, SOFT_NMS}` onto `cfg.bbox_file` / `det_score_thr` / `oks_nms_thr` /
+    `in_vis_thr` / `soft_nms` (validation on detector boxes; `TEST.USE_GT_BBOX: false` without a box file changes nothing and says so).
 """
+import logging
 import math
 import os
 from dataclasses import dataclass, field
@@ -103,6 +106,15 @@ class Config:
     min_keypoint_visibility = 0.3
     temporal = None
     clinical = None
+    # Validation on detector boxes (legacy yaml TEST block, `validate.py --bbox_file / --oks_nms`), plain class attributes as well.
+    # bbox_file: None (crops from the ground-truth boxes) or a COCO-style person-detection file, relative to data_root; det_score_thr: boxes
+    # scored below it are dropped; oks_nms_thr: None (every pose is evaluated) or the OKS threshold of the per-image pose NMS, which then
+    # also rescores every pose as box score x mean keypoint score above in_vis_thr; soft_nms: the soft variant.
+    bbox_file = None
+    det_score_thr = 0.0
+    oks_nms_thr = None
+    in_vis_thr = 0.2
+    soft_nms = False
 
 
 _PRESETS = {
@@ -195,6 +207,18 @@ def _apply_legacy_yaml(cfg: Config, path: str) -> Config:
         cfg.pck_threshold = float(ev['PCK_THRESHOLD'])
     if 'MIN_KEYPOINT_VISIBILITY' in ev:
         cfg.min_keypoint_visibility = float(ev['MIN_KEYPOINT_VISIBILITY'])
+    # TEST block: detector boxes.  (EVAL.OKS_THRESHOLD is the match threshold of an AP, not an NMS threshold: not mapped.)
+    te = y.get('TEST', {}) or {}
+    if te.get('COCO_BBOX_FILE'):
+        cfg.bbox_file = str(te['COCO_BBOX_FILE'])
+    for src, dst in (('IMAGE_THRE', 'det_score_thr'), ('OKS_THRE', 'oks_nms_thr'), ('IN_VIS_THRE', 'in_vis_thr')):
+        if te.get(src) is not None:
+            setattr(cfg, dst, float(te[src]))
+    if 'SOFT_NMS' in te:
+        cfg.soft_nms = bool(te['SOFT_NMS'])
+    if te.get('USE_GT_BBOX') is False and cfg.bbox_file is None:
+        logging.getLogger(__name__).warning(f"{path}: TEST.USE_GT_BBOX is false but no TEST.COCO_BBOX_FILE is given: validation keeps "
+                                            "cropping from the ground-truth boxes")
     tp = y.get('TEMPORAL', {}) or {}
     if tp.get('ENABLED'):
         window = int(tp.get('WINDOW_SIZE', 5))

@@ -20,7 +20,13 @@ from .transforms import Compose, DeviceCropper, get_train_transforms, get_val_tr
 
 class COCOPoseDataset(torch.utils.data.Dataset):
     def __init__(self, data_root: str, ann_file: str, img_prefix: str, input_size=(192, 256), heatmap_size=(48, 64), sigma: float = 2.0,
-                 num_keypoints: int = 17, transforms: Optional[Compose] = None, is_train: bool = True, flip_pairs=None):
+                 num_keypoints: int = 17, transforms: Optional[Compose] = None, is_train: bool = True, flip_pairs=None,
+                 bbox_file: Optional[str] = None, det_score_thr: float = 0.0):
+        """bbox_file (validation only): a COCO-style person-detection file; the records then come from its boxes (`_load_detections`)
+        instead of the ground-truth annotations, and carry no ground truth."""
+        if bbox_file is not None and is_train:
+            raise ValueError("COCOPoseDataset: bbox_file is for validation (detector boxes carry no ground truth to train on)")
+        self.bbox_file, self.det_score_thr = bbox_file, float(det_score_thr)
         self.data_root = data_root
         self.ann_file = os.path.join(data_root, ann_file)
         self.img_prefix = os.path.join(data_root, img_prefix)
@@ -29,8 +35,12 @@ class COCOPoseDataset(torch.utils.data.Dataset):
         self.flip_pairs = flip_pairs or [(1, 2), (3, 4), (5, 6), (7, 8), (9, 10), (11, 12), (13, 14), (15, 16)]
         with open(self.ann_file) as f:
             self.coco = json.load(f)
-        self.db = self._load_annotations()
-        print(f"Loaded {len(self.db)} samples from {self.ann_file}")
+        if bbox_file is not None:
+            self.bbox_file = os.path.join(data_root, bbox_file)        # like ann_file: relative to data_root unless absolute
+            self.db = self._load_detections()
+        else:
+            self.db = self._load_annotations()
+        print(f"Loaded {len(self.db)} samples from {self.bbox_file or self.ann_file}")
 
     def _load_annotations(self) -> List[Dict]:
         """coco_dataset.py:64-115: one record per person annotation with keypoints, bbox clipped to the image, scale x 1.25."""
@@ -55,6 +65,41 @@ class COCOPoseDataset(torch.utils.data.Dataset):
                            "scale": np.array([x2 - x1, y2 - y1], dtype=np.float32) * 1.25,
                            "bbox": np.array([x1, y1, x2, y2], dtype=np.float32), "keypoints": kp[:, :2].astype(np.float32),
                            "keypoints_visible": kp[:, 2].astype(np.float32), "area": ann.get("area", w * h)})
+        return db
+
+    def _load_detections(self) -> List[Dict]:
+        """One record per box of a COCO-style detection list [{image_id, category_id, bbox [x, y, w, h], score}, ...], in the file's
+        order: category 1 (person) with score >= det_score_thr on an image of the annotation file; the box is clipped and degenerate
+        boxes are dropped exactly as `_load_annotations` does; area = w h of the clipped box; no ground truth (ann_id -1, keypoints and
+        visibility zero); `box_score` = the detector's score."""
+        try:
+            with open(self.bbox_file) as f:
+                dets = json.load(f)
+        except (OSError, ValueError) as e:
+            raise ValueError(f"{self.bbox_file}: cannot read the detection file ({e})") from None
+        if not isinstance(dets, list):
+            raise ValueError(f"{self.bbox_file}: expected a list of detections {{image_id, category_id, bbox, score}}, got {type(dets).__name__}")
+        info_of = {info["id"]: info for info in self.coco.get("images", [])}
+        K, db = self.num_keypoints, []
+        for n, det in enumerate(dets):
+            try:
+                image_id, cat, score = det["image_id"], int(det["category_id"]), float(det["score"])
+                x, y, w, h = (float(v) for v in det["bbox"])
+            except (KeyError, TypeError, ValueError) as e:
+                raise ValueError(f"{self.bbox_file}: detection {n} is malformed ({type(e).__name__}: {e})") from None
+            info = info_of.get(image_id)
+            if cat != 1 or not score >= self.det_score_thr or info is None:
+                continue
+            if w <= 0 or h <= 0:
+                continue
+            x1, y1, x2, y2 = max(0, x), max(0, y), min(info["width"], x + w), min(info["height"], y + h)
+            if x2 <= x1 or y2 <= y1:
+                continue
+            db.append({"image_file": os.path.join(self.img_prefix, info["file_name"]), "image_id": info["id"], "ann_id": -1,
+                       "center": np.array([(x1 + x2) / 2, (y1 + y2) / 2], dtype=np.float32),
+                       "scale": np.array([x2 - x1, y2 - y1], dtype=np.float32) * 1.25,
+                       "bbox": np.array([x1, y1, x2, y2], dtype=np.float32), "keypoints": np.zeros((K, 2), np.float32),
+                       "keypoints_visible": np.zeros(K, np.float32), "area": float((x2 - x1) * (y2 - y1)), "box_score": score})
         return db
 
     def __len__(self) -> int:
@@ -141,10 +186,12 @@ class DeviceBatcher:
         target, weight = generate_target(kp, vis, d.input_size, d.heatmap_size, d.sigma)
         f32 = lambda k: torch.from_numpy(np.stack([np.asarray(s[k], np.float32) for s in samples]))
         batch = {} if img_scales is None else {"img_scales": img_scales}
+        # detector boxes (COCOPoseDataset(bbox_file=...)): the box scores ride along, and mark the batch as one without ground truth
+        box = {"box_score": torch.tensor([float(s["box_score"]) for s in samples], dtype=torch.float64)} if "box_score" in samples[0] else {}
         return {**batch, "img": img32, "img_nhwc8": img16, "target": target, "target_weight": weight, "keypoints": kp, "keypoints_visible": vis,
                 "meta": {"image_id": torch.tensor([int(s["image_id"]) for s in samples]), "ann_id": torch.tensor([int(s["ann_id"]) for s in samples]),
                          "center": f32("center"), "scale": f32("scale"), "bbox": f32("bbox"),
-                         "area": torch.tensor([float(s["area"]) for s in samples])}}
+                         "area": torch.tensor([float(s["area"]) for s in samples]), **box}}
 
     def _prepare(self, samples):
         """Enqueue the device work of one batch on the side stream -> (batch, event that marks it ready)."""
@@ -184,7 +231,8 @@ def build_coco_dataloader(cfg, is_train: bool = True, device="cuda"):
     tf = (get_train_transforms(d.input_size, t.flip_prob, t.rotation_factor, t.scale_factor, color_jitter=t.color_jitter,
                                color_jitter_prob=t.color_jitter_prob) if is_train else get_val_transforms(d.input_size))
     ds = COCOPoseDataset(d.data_root, d.train_ann if is_train else d.val_ann, d.train_img_prefix if is_train else d.val_img_prefix, d.input_size,
-                         d.heatmap_size, d.sigma, d.num_keypoints, tf, is_train, d.flip_pairs)
+                         d.heatmap_size, d.sigma, d.num_keypoints, tf, is_train, d.flip_pairs,
+                         bbox_file=None if is_train else getattr(cfg, "bbox_file", None), det_score_thr=getattr(cfg, "det_score_thr", 0.0))
     loader = torch.utils.data.DataLoader(ds, batch_size=t.batch_size, shuffle=is_train, num_workers=t.num_workers, collate_fn=collate_records,
                                          drop_last=is_train, persistent_workers=t.num_workers > 0)
     return DeviceBatcher(loader, cfg, device, test_scales=None if is_train else getattr(cfg, "test_scales", None))

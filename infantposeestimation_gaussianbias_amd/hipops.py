@@ -171,6 +171,65 @@ def coco_kpt_eval(oks, oks_off, gt_off, gt_area, gt_flags, cap_off, cap_idx, dt_
     return out
 
 
+OKS_NMS_MAX_POSES = 1024      # poses per image pk_oks_nms holds in LDS
+OKS_NMS_MAX_K = 64
+
+
+def pose_rescore(kpt, box_score=None, in_vis_thr=0.2):
+    """(N,K,3) fp64 rows [x, y, keypoint score] (+ (N,) fp64 box scores or None = 1) -> (N,) fp64: box score x mean of the keypoint scores
+    above `in_vis_thr`, 0 without one (pk_pose_rescore)."""
+    if kpt.dim() != 3 or kpt.shape[-1] != 3:
+        raise ValueError(f"kpt: expected (N, K, 3), got {tuple(kpt.shape)}")
+    N, K = int(kpt.shape[0]), int(kpt.shape[1])
+    if not 1 <= K <= OKS_NMS_MAX_K:
+        raise ValueError(f"kpt: {K} keypoints (1 to {OKS_NMS_MAX_K})")
+    if box_score is not None and tuple(box_score.shape) != (N,):
+        raise ValueError(f"box_score: expected {(N,)}, got {tuple(box_score.shape)}")
+    kp = _chk(kpt, F64, "kpt")
+    bs = None if box_score is None else _chk(box_score, F64, "box_score")
+    out = torch.empty(N, dtype=F64, device=kp.device)
+    _call_if(N, "pk_pose_rescore", kp, bs, out, N, K, float(in_vis_thr), stream_ptr())
+    return out
+
+
+def oks_nms(kpt, area, score, off, vars_, thr, in_vis_thr=0.2, soft=False, max_dets=20):
+    """OKS-NMS of the poses of every image (pk_oks_nms, one workgroup per image).  kpt (N,K,3), area (N,), score (N,), vars_ (K,) = (2 sigma)^2:
+    fp64 device tensors; off: the n_img + 1 int32 CSR offsets, a host array / CPU tensor (uploaded here) or a device tensor (copied back
+    once: the per-image limit is checked on the host, before the launch).  -> keep (N,) uint8, n_keep (n_img,) int32, order (N,) int32 (per
+    image: kept local indices in selection order, then -1), out_score (N,) fp64 (0 where not kept)."""
+    if kpt.dim() != 3 or kpt.shape[-1] != 3:
+        raise ValueError(f"kpt: expected (N, K, 3), got {tuple(kpt.shape)}")
+    N, K = int(kpt.shape[0]), int(kpt.shape[1])
+    if not 1 <= K <= OKS_NMS_MAX_K:
+        raise ValueError(f"kpt: {K} keypoints (1 to {OKS_NMS_MAX_K})")
+    for t, name, shape in ((area, "area", (N,)), (score, "score", (N,)), (vars_, "vars", (K,))):
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name}: expected {shape}, got {tuple(t.shape)}")
+    off_dev = off if isinstance(off, torch.Tensor) and off.is_cuda else None
+    off_host = np.asarray(off.cpu() if isinstance(off, torch.Tensor) else off)
+    if off_host.ndim != 1 or off_host.size < 2 or off_host.dtype != np.int32:
+        raise ValueError(f"off: expected n_img + 1 int32 offsets in one dimension, got {off_host.dtype} {off_host.shape}")
+    counts = np.diff(off_host.astype(np.int64))
+    if off_host[0] != 0 or off_host[-1] != N or (counts < 0).any():
+        raise ValueError(f"off: offsets must ascend from 0 to N = {N}")
+    if not math.isfinite(thr) or (soft and not (thr > 0 and int(max_dets) > 0)):
+        raise ValueError(f"oks_nms: thr must be finite, and soft mode needs thr > 0 and max_dets > 0 (got thr {thr}, max_dets {max_dets})")
+    if counts.max() > OKS_NMS_MAX_POSES:
+        i = int(counts.argmax())
+        raise _lib.PoseKernelError(f"pk_oks_nms failed (code -2, PK_ERR_UNSUPPORTED): image {i} holds {int(counts[i])} poses; the kernel is "
+                                   f"built for at most {OKS_NMS_MAX_POSES} per image")
+    kp, ar, sc, va = _chk(kpt, F64, "kpt"), _chk(area, F64, "area"), _chk(score, F64, "score"), _chk(vars_, F64, "vars")
+    dev, n_img = kp.device, int(off_host.size) - 1
+    od = _chk(off_dev, I32, "off") if off_dev is not None else torch.from_numpy(np.ascontiguousarray(off_host)).to(dev)
+    keep = torch.empty(N, dtype=torch.uint8, device=dev)
+    n_keep = torch.zeros(n_img, dtype=I32, device=dev)
+    order = torch.empty(N, dtype=I32, device=dev)
+    out_score = torch.empty(N, dtype=F64, device=dev)
+    _call_if(N, "pk_oks_nms", kp, ar, sc, od, va, keep, n_keep, order, out_score, n_img, K, float(thr), float(in_vis_thr), int(bool(soft)),
+             int(max_dets), stream_ptr())
+    return keep, n_keep, order, out_score
+
+
 def flip_merge(hm, hm_from_flipped, partner):
     a, b = _chk(hm), _chk(hm_from_flipped)
     B, K, H, W = a.shape

@@ -4,7 +4,8 @@
 per-instance scores come from one kernel (pk_pose_records) and ONE device->host copy per batch; numpy inputs (the reference's
 calling convention) are accepted as they are -- the evaluator itself is host bookkeeping (a list of record dicts).
 With an annotation file `evaluate()` reports COCO keypoint AP / AR (utils/coco_eval.py: COCOeval's arithmetic on the device, no
-pycocotools); without one, the precision of greedy OKS matching against `gt_annotations=` (array form)."""
+pycocotools); without one, the precision of greedy OKS matching against `gt_annotations=` (array form).  With `oks_nms_thr=` the records
+are first rescored and thinned per image by OKS-NMS on the device (pk_pose_rescore, pk_oks_nms): the detector-box protocol."""
 from collections import defaultdict
 from typing import Dict, List, Optional
 
@@ -15,19 +16,27 @@ class COCOEvaluator:
     DEFAULT_OKS_SIGMAS = np.array([0.026, 0.025, 0.025, 0.035, 0.035, 0.079, 0.079, 0.072, 0.072, 0.062, 0.062, 0.107, 0.107, 0.087,
                                    0.087, 0.089, 0.089])
 
-    def __init__(self, ann_file: Optional[str] = None, oks_sigmas: Optional[np.ndarray] = None, num_keypoints: int = 17):
+    def __init__(self, ann_file: Optional[str] = None, oks_sigmas: Optional[np.ndarray] = None, num_keypoints: int = 17,
+                 oks_nms_thr: Optional[float] = None, in_vis_thr: float = 0.2, soft_nms: bool = False, nms_max_dets: int = 20):
+        """oks_nms_thr: None (every record is evaluated as it is), or the OKS threshold of the detector-box protocol: `evaluate()` then
+        rescores every record (box score x mean of the keypoint scores above `in_vis_thr`) and removes duplicate poses per image with
+        OKS-NMS -- hard, or soft (`soft_nms`, at most `nms_max_dets` poses per image) -- on the device before it computes AP."""
         self.ann_file = ann_file
         self.oks_sigmas = oks_sigmas if oks_sigmas is not None else self.DEFAULT_OKS_SIGMAS
         self.num_keypoints = num_keypoints
         self.oks_thresholds = np.linspace(0.5, 0.95, 10)
+        self.oks_nms_thr, self.in_vis_thr, self.soft_nms, self.nms_max_dets = oks_nms_thr, float(in_vis_thr), bool(soft_nms), int(nms_max_dets)
         self.predictions: List[Dict] = []
+        self.kept: List[Dict] = []
 
     def reset(self):
         self.predictions = []
+        self.kept = []
 
-    def update(self, pred_keypoints, pred_scores, image_ids, ann_ids, centers=None, scales=None, areas=None, bboxes=None):
+    def update(self, pred_keypoints, pred_scores, image_ids, ann_ids, centers=None, scales=None, areas=None, bboxes=None, box_scores=None):
         """pred_keypoints (B,K,2) in image space, pred_scores (B,K): device tensors or numpy arrays; ids / areas / bboxes: sequences,
-        arrays or tensors (utils/metrics.py:61-106: centers and scales are accepted and unused there too)."""
+        arrays or tensors (utils/metrics.py:61-106: centers and scales are accepted and unused there too).  box_scores (B,): the detector's
+        score of each box, stored as the record's `box_score` (None: ground-truth boxes, no such key)."""
         import torch
         if torch.is_tensor(pred_keypoints) and pred_keypoints.is_cuda:
             from .. import hipops
@@ -41,9 +50,46 @@ class COCOEvaluator:
         to_list = lambda v: v.tolist() if hasattr(v, "tolist") else list(v)
         image_ids, ann_ids, areas = to_list(image_ids), to_list(ann_ids), to_list(areas)
         bboxes = bboxes.cpu().numpy() if torch.is_tensor(bboxes) else np.asarray(bboxes)
+        box_scores = None if box_scores is None else to_list(box_scores)
         for i in range(rec.shape[0]):
             self.predictions.append({'image_id': int(image_ids[i]), 'ann_id': int(ann_ids[i]), 'keypoints': rec[i].flatten().tolist(),
                                      'score': float(inst[i]), 'area': float(areas[i]), 'bbox': bboxes[i].tolist()})
+            if box_scores is not None:
+                self.predictions[-1]['box_score'] = float(box_scores[i])
+
+    def suppress(self) -> List[Dict]:
+        """Rescoring + OKS-NMS of `self.predictions` (left untouched) -> the surviving records, copies with the updated `score`: images in
+        the order of their first record, inside an image in selection order.  Two kernels over all images (pk_pose_rescore, pk_oks_nms),
+        one device->host copy; the OKS uses each record's `area` and this evaluator's sigmas."""
+        import torch
+        from .. import _lib, hipops
+        if not torch.cuda.is_available():
+            raise _lib.PoseKernelError("COCOEvaluator: OKS-NMS runs on a CUDA(HIP) device; the kernels have no CPU implementation")
+        recs = self.predictions
+        pos_of: Dict[int, int] = {}
+        pos = np.array([pos_of.setdefault(int(r['image_id']), len(pos_of)) for r in recs], np.int64)
+        idx = np.argsort(pos, kind='stable')                                   # grouped by image, record order inside an image
+        off = np.searchsorted(pos[idx], np.arange(len(pos_of) + 1)).astype(np.int32)
+        dev = torch.device('cuda', torch.cuda.current_device())
+        f64 = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float64)).to(dev)
+        kp = f64(np.array([recs[i]['keypoints'] for i in idx], np.float64).reshape(len(idx), -1, 3))
+        has_box = ['box_score' in recs[i] for i in idx]
+        if any(has_box) and not all(has_box):
+            raise ValueError("COCOEvaluator: some records carry a box_score and some do not")
+        box = f64(np.array([recs[i]['box_score'] for i in idx])) if all(has_box) and len(idx) else None
+        score = hipops.pose_rescore(kp, box, self.in_vis_thr)
+        sig = np.asarray(self.oks_sigmas, np.float64).reshape(-1)
+        _, _, order, out_score = hipops.oks_nms(kp, f64(np.array([recs[i]['area'] for i in idx])), score, off, f64((sig * 2) ** 2),
+                                                float(self.oks_nms_thr), self.in_vis_thr, self.soft_nms, self.nms_max_dets)
+        both = torch.stack([order.double(), out_score]).cpu().numpy()          # local indices < 1024: exact in float64
+        order_h, score_h = both[0].astype(np.int64), both[1]
+        kept = []
+        for i in range(len(pos_of)):
+            for p in order_h[off[i]:off[i + 1]]:
+                if p < 0:
+                    break
+                kept.append(dict(recs[idx[off[i] + p]], score=float(score_h[off[i] + p])))
+        return kept
 
     def compute_oks(self, pred_kpts: np.ndarray, gt_kpts: np.ndarray, gt_vis: np.ndarray, area: float) -> float:
         """Object keypoint similarity of one prediction / ground-truth pair (utils/metrics.py:108-142): mean over the visible joints
@@ -65,12 +111,15 @@ class COCOEvaluator:
         carry no file."""
         if not self.predictions:
             return {'AP': 0.0, 'AP50': 0.0, 'AP75': 0.0}
+        records = self.predictions
+        if self.oks_nms_thr is not None:       # detector-box protocol: rescore, OKS-NMS per image, then AP of what survives (`self.kept`)
+            records = self.kept = self.suppress()
         if self.ann_file is not None:
             from .coco_eval import COCOKeypointEval
-            return COCOKeypointEval(self.ann_file, self.oks_sigmas).evaluate(self.predictions)
+            return COCOKeypointEval(self.ann_file, self.oks_sigmas).evaluate(records)
         if gt_annotations is None:
             raise ValueError("Either ann_file or gt_annotations must be provided")
-        return oks_precision(self.predictions, gt_annotations, self.oks_sigmas, self.oks_thresholds)
+        return oks_precision(records, gt_annotations, self.oks_sigmas, self.oks_thresholds)
 
 
 def oks_precision(records, gts, sigmas, thresholds):

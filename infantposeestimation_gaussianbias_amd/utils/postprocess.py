@@ -59,6 +59,59 @@ def nms_pose(preds, maxvals, distance_threshold=5.0):
     return hipops.nms_pose(preds, maxvals, distance_threshold)
 
 
+def _oks_nms(kpts, scores, areas, thr, sigmas, in_vis_thr, offsets, soft, max_dets):
+    """Shared body of `oks_nms` / `soft_oks_nms`: numpy arrays are uploaded (and numpy comes back), device tensors are used as they are.
+    -> kept global indices (int64; images in order, selection order inside an image), their scores."""
+    import numpy as np
+    as_numpy = not torch.is_tensor(kpts)
+    if as_numpy and not torch.cuda.is_available():
+        from .. import _lib
+        raise _lib.PoseKernelError("oks_nms: expected a CUDA(HIP) device; the kernels have no CPU implementation")
+    dev = kpts.device if not as_numpy else torch.device("cuda", torch.cuda.current_device())
+    f64 = lambda v: (v.to(torch.float64) if torch.is_tensor(v) else torch.from_numpy(np.ascontiguousarray(v, np.float64)).to(dev))
+    kp = f64(kpts)
+    if kp.dim() != 3 or kp.shape[-1] != 3:
+        raise ValueError(f"kpts: expected (N, K, 3) rows [x, y, score], got {tuple(kp.shape)}")
+    N, K = int(kp.shape[0]), int(kp.shape[1])
+    if sigmas is None:
+        from .metrics import COCOEvaluator
+        sigmas = COCOEvaluator.DEFAULT_OKS_SIGMAS
+        if K != len(sigmas):
+            raise ValueError(f"oks_nms: pass one OKS sigma per keypoint (the default holds the {len(sigmas)} COCO sigmas, got K = {K})")
+    sig = np.asarray(sigmas.cpu() if torch.is_tensor(sigmas) else sigmas, np.float64).reshape(-1)
+    if sig.size != K:
+        raise ValueError(f"oks_nms: {sig.size} OKS sigmas for {K} keypoints")
+    if offsets is None:
+        off = np.array([0, N], np.int32)
+    else:
+        off = np.asarray(offsets.cpu() if torch.is_tensor(offsets) else offsets)
+        if off.ndim != 1 or off.size < 2 or (off != off.astype(np.int32)).any():
+            raise ValueError("offsets: expected n_img + 1 integer CSR offsets")
+        off = off.astype(np.int32)
+    _, n_keep, order, out_score = hipops.oks_nms(kp, f64(areas).reshape(-1), f64(scores).reshape(-1), off, f64((sig * 2) ** 2), thr,
+                                                 in_vis_thr, soft, max_dets)
+    base = torch.repeat_interleave(torch.from_numpy(off[:-1].astype(np.int64)), torch.from_numpy(np.diff(off).astype(np.int64))).to(dev)
+    sel = order >= 0                                   # per image the kept slots come first, so masking preserves the selection order
+    idx = (order.to(torch.int64) + base)[sel]
+    sc = out_score[idx]
+    return (idx.cpu().numpy(), sc.cpu().numpy()) if as_numpy else (idx, sc)
+
+
+def oks_nms(kpts, scores, areas, thr=0.9, sigmas=None, in_vis_thr=0.2, offsets=None):
+    """Hard OKS-NMS of the poses of one image, or of a CSR batch of images (`offsets`: n_img + 1 ascending offsets into the N poses), on
+    the device (pk_oks_nms).  kpts (N,K,3) rows [x, y, keypoint score], scores (N,), areas (N,); sigmas: the K OKS sigmas (default: COCO's 17).
+    Per image the poses are visited by descending score (ties to the lower index); a visited pose that is still alive is kept and removes
+    every later pose whose OKS to it exceeds `thr`; a joint counts in the OKS when both keypoint scores exceed `in_vis_thr`.
+    -> the kept indices (int64), image by image, in selection order.  At most 1024 poses per image."""
+    return _oks_nms(kpts, scores, areas, thr, sigmas, in_vis_thr, offsets, False, 0)[0]
+
+
+def soft_oks_nms(kpts, scores, areas, thr=0.9, sigmas=None, in_vis_thr=0.2, offsets=None, max_dets=20):
+    """Soft OKS-NMS: per image, until `max_dets` poses are kept, the remaining pose with the highest current score is selected and every
+    remaining score is multiplied by exp(-oks^2 / thr).  -> (kept indices, their scores at selection)."""
+    return _oks_nms(kpts, scores, areas, thr, sigmas, in_vis_thr, offsets, True, max_dets)
+
+
 def transform_preds(coords, center, scale, output_size, input_size=[256, 256]):
     return hipops.affine_coords(coords.float(), center.float().to(coords.device), scale.float().to(coords.device),
                                 1.0 / input_size[0], 1.0 / input_size[1])

@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Validation script (drop-in for the reference's validate.py: --checkpoint --data_root --batch_size --no_flip; plus --scales for the
 multi-scale test: predictions from `PoseEstimator.inference_multiscale` over the loader's `img_scales`, the loss still on `img`; plus
---pck [THR ...] for PCK next to AP: the share of keypoints within THR x the longer box side of their ground truth, counted on the device).
+--pck [THR ...] for PCK next to AP: the share of keypoints within THR x the longer box side of their ground truth, counted on the device;
+plus --bbox_file / --det_score_thr / --oks_nms THR / --soft_nms / --in_vis_thr for the detector-box protocol: crops from a person-detection
+file instead of the ground-truth boxes, every pose rescored as box score x mean confident keypoint score, duplicate poses removed per image
+by OKS-NMS on the device, then AP).
 
 Flip-test inference + decode run entirely on the GPU (`PoseEstimator.inference`: two forwards, one flip-merge kernel, one
 decode kernel); the heat-px -> image transform of validate.py:100-117 is one kernel (`heatmap_to_image_coords`) instead of a
@@ -27,7 +30,7 @@ from infantposeestimation_gaussianbias_amd.utils.postprocess import heatmap_to_i
 
 
 @torch.no_grad()
-def validate(model, loader, device, cfg, logger, flip_test=True, scales=None, pck_thresholds=None):
+def validate(model, loader, device, cfg, logger, flip_test=True, scales=None, pck_thresholds=None, evaluator=None):
     """train.py:231-325 == validate.py:39-140 of the reference: loss + decode + image-space transform + COCOEvaluator.update per batch,
     then AP.  Decode, flip merge, the heat-px -> image transform and the evaluator's record arrays are kernels (no B x K Python loops, one
     device->host copy per batch).  AP / AR come from COCOKeypointEval when the loader's dataset has an annotation file; otherwise AP is the
@@ -35,16 +38,23 @@ def validate(model, loader, device, cfg, logger, flip_test=True, scales=None, pc
     `scales`: multi-scale test over `batch["img_scales"]` (the loader must have been built with the same `test_scales`).
     `pck_thresholds`: None (nothing added), or thresholds for PCK in image space with the longer side of `meta["bbox"]` (x1 y1 x2 y2 in both
     loaders) as the normalising length: adds `PCK@<thr>` per threshold and `PCK_mean_error` (mean distance / normaliser) to the metrics.
-    The counts accumulate on the device (`PCKAccumulator`): one device->host copy after the last batch."""
+    The counts accumulate on the device (`PCKAccumulator`): one device->host copy after the last batch.
+    Detector boxes: a batch whose meta carries `box_score` (a COCO loader built with `cfg.bbox_file`) has no ground truth -- the loss forward
+    is skipped (`metrics["loss"]` is NaN), PCK raises, and the box scores go to the evaluator, which with `cfg.oks_nms_thr` rescores the poses
+    and removes duplicates per image by OKS-NMS on the device before AP (`COCOEvaluator.kept`).  `evaluator`: the COCOEvaluator to fill
+    (default: one built from the loader's annotation file and the config's NMS settings)."""
     from infantposeestimation_gaussianbias_amd.utils import COCOEvaluator
     from infantposeestimation_gaussianbias_amd.utils import metrics as metrics_mod
     pck = metrics_mod.PCKAccumulator(cfg.data.num_keypoints, pck_thresholds) if pck_thresholds is not None else None
     model.eval()
     loss_meter = AverageMeter("Loss", ":.4f")
     ann = getattr(getattr(loader, "dataset", None), "ann_file", None)
-    evaluator = COCOEvaluator(ann_file=ann, num_keypoints=cfg.data.num_keypoints)
+    if evaluator is None:
+        evaluator = COCOEvaluator(ann_file=ann, num_keypoints=cfg.data.num_keypoints, oks_nms_thr=getattr(cfg, "oks_nms_thr", None),
+                                  in_vis_thr=getattr(cfg, "in_vis_thr", 0.2), soft_nms=getattr(cfg, "soft_nms", False))
     flip_pairs = cfg.data.flip_pairs if flip_test else None
     gts = []
+    no_gt = False
     for i, batch in enumerate(loader):
         imgs = batch["img"].to(device)
         if scales is None:
@@ -55,13 +65,22 @@ def validate(model, loader, device, cfg, logger, flip_test=True, scales=None, pc
                                    "slice per scale (the COCO loader built from a config with the same test_scales); this loader does not, "
                                    "and there is no single-scale fallback")
             kp, sc = model.inference_multiscale(batch["img_scales"].to(device), scales, flip=bool(flip_test and flip_pairs), flip_pairs=flip_pairs)
-        gt_kp = batch["keypoints"].to(device) if batch.get("keypoints") is not None else None
-        out = model(imgs, batch["target"].to(device), batch["target_weight"].to(device), gt_keypoints=gt_kp, input_size=cfg.data.input_size)
-        loss_meter.update(float(out["loss"]), imgs.size(0))
         meta = batch["meta"]
+        box_scores = meta.get("box_score")
+        if box_scores is not None:          # detector boxes: the batch's keypoints and targets are placeholders, not ground truth
+            if pck is not None:
+                raise RuntimeError("validate: PCK needs ground-truth keypoints; a loader of detector boxes (bbox_file) carries none")
+            no_gt, gt_kp = True, None
+        else:
+            gt_kp = batch["keypoints"].to(device) if batch.get("keypoints") is not None else None
+            out = model(imgs, batch["target"].to(device), batch["target_weight"].to(device), gt_keypoints=gt_kp, input_size=cfg.data.input_size)
+            loss_meter.update(float(out["loss"]), imgs.size(0))
         center, scale = meta["center"].to(device).float(), meta["scale"].to(device).float()
         img_kp = heatmap_to_image_coords(kp, center, scale, cfg.data.input_size, cfg.data.heatmap_size)
-        evaluator.update(img_kp, sc, meta["image_id"], meta["ann_id"], center, scale, meta["area"], meta["bbox"])
+        if box_scores is not None:
+            evaluator.update(img_kp, sc, meta["image_id"], meta["ann_id"], center, scale, meta["area"], meta["bbox"], box_scores=box_scores)
+        else:
+            evaluator.update(img_kp, sc, meta["image_id"], meta["ann_id"], center, scale, meta["area"], meta["bbox"])
         if pck is not None and gt_kp is None:
             raise RuntimeError("validate: PCK needs a loader that yields batch['keypoints'] and batch['keypoints_visible']; this one does not")
         # ground truth in image space: the same inverse crop transform, applied to the input-pixel keypoints (heatmap size == input size)
@@ -81,7 +100,7 @@ def validate(model, loader, device, cfg, logger, flip_test=True, scales=None, pc
         if i % 50 == 0:
             logger.info(f"  [{i}/{len(loader)}] Loss: {loss_meter.avg:.4f}")
     metrics = dict(evaluator.evaluate(gt_annotations=None if ann else gts))
-    metrics["loss"] = loss_meter.avg
+    metrics["loss"] = float("nan") if no_gt else loss_meter.avg
     if pck is not None:
         res = pck.compute()
         metrics.update({k: v for k, v in res.items() if k.startswith("PCK@")})
@@ -101,6 +120,7 @@ def main(args):
         cfg.train.batch_size = args.batch_size
     if args.scales:
         cfg.test_scales = check_test_scales(args.scales)
+    apply_detector_box_args(cfg, args)
     device = torch.device("cuda")
     loader = build_dataloader(cfg, is_train=False)
     model = build_model(cfg).to(device)
@@ -111,14 +131,31 @@ def main(args):
     pck_thresholds = None
     if getattr(args, "pck", None) is not None:
         pck_thresholds = tuple(args.pck) or (cfg.pck_threshold,)
-    elif "PCK" in cfg.eval_metrics:
+    elif "PCK" in cfg.eval_metrics and cfg.bbox_file is None:      # detector boxes carry no ground truth: only an explicit --pck insists
         pck_thresholds = (cfg.pck_threshold,)
     metrics, _ = validate(model, loader, device, cfg, logger, flip_test=not args.no_flip, scales=cfg.test_scales, pck_thresholds=pck_thresholds)
     logger.info(f"Loss: {metrics['loss']:.4f}")
     return metrics
 
 
-if __name__ == "__main__":
+def apply_detector_box_args(cfg, args):
+    """--bbox_file / --det_score_thr / --oks_nms / --soft_nms / --in_vis_thr onto the config (a flag that is not given leaves the yaml's value)."""
+    if getattr(args, "bbox_file", None):
+        cfg.bbox_file = args.bbox_file
+    if getattr(args, "det_score_thr", None) is not None:
+        cfg.det_score_thr = float(args.det_score_thr)
+    if getattr(args, "oks_nms", None) is not None:
+        cfg.oks_nms_thr = float(args.oks_nms)
+    if getattr(args, "soft_nms", False):
+        cfg.soft_nms = True
+    if getattr(args, "in_vis_thr", None) is not None:
+        cfg.in_vis_thr = float(args.in_vis_thr)
+    if cfg.soft_nms and cfg.oks_nms_thr is None:
+        raise ValueError("--soft_nms needs an OKS threshold: give --oks_nms THR (or TEST.OKS_THRE in the yaml)")
+    return cfg
+
+
+def build_parser():
     p = argparse.ArgumentParser(description="Validate Pose Estimation Model")
     p.add_argument("--checkpoint", type=str, required=True)
     p.add_argument("--data_root", type=str, default=None)
@@ -130,4 +167,18 @@ if __name__ == "__main__":
     p.add_argument("--pck", type=float, nargs="*", default=None,
                    help="also report PCK at these thresholds (fractions of the longer box side; no value: the config's pck_threshold, 0.2); "
                         "default: only when the config's yaml names 'PCK' in EVAL.METRICS")
-    main(p.parse_args())
+    p.add_argument("--bbox_file", type=str, default=None,
+                   help="validate on detector boxes: a COCO-style person-detection file [{image_id, category_id, bbox, score}], relative to "
+                        "data_root (default: the config's bbox_file; none: crops from the ground-truth boxes)")
+    p.add_argument("--det_score_thr", type=float, default=None, help="drop detector boxes scored below this (default: the config's, 0.0)")
+    p.add_argument("--oks_nms", type=float, default=None, metavar="THR",
+                   help="rescore every pose (box score x mean confident keypoint score) and remove duplicate poses per image with OKS-NMS at "
+                        "this threshold before AP (default: the config's oks_nms_thr; none: every pose is evaluated)")
+    p.add_argument("--soft_nms", action="store_true", help="soft OKS-NMS (scores decay by exp(-oks^2 / THR)) instead of hard suppression")
+    p.add_argument("--in_vis_thr", type=float, default=None,
+                   help="keypoint score above which a joint counts in the rescoring and in the NMS's OKS (default: the config's, 0.2)")
+    return p
+
+
+if __name__ == "__main__":
+    main(build_parser().parse_args())
