@@ -23,11 +23,6 @@
 // the kernel, no float atomics).
 #include "pk_common.h"
 
-typedef __attribute__((ext_vector_type(8))) short bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-
 #define AT_N 49
 #define AT_WS 7
 // row pitch (bf16) of the [64][32*DK] row-major LDS tiles: 32*DK + 8 (40 for head_dim <= 32, 72 for head_dim <= 64)
@@ -39,8 +34,6 @@ __device__ __forceinline__ bf16x8 lds_frag(const uint16_t* base, int row, int pi
 // All global reads are branch-free `buffer_load_dwordx4` with the out-of-range offset trick (offset >= num_records returns
 // zeros): rows >= 49 and channels >= d cost no branch, so the compiler issues every load of a window back to back and
 // waits once, instead of serialising one HBM latency per conditional load (that was ~25 us per window).
-#define OOB_OFF 0x80000000u
-#define MAKE_RSRC(ptr) __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(ptr), 0, 0x7ffffff0, 0x00020000)
 // Row fragment straight from global memory: token row `row`, channels 8g .. 8g+7 (zeros outside the 49 x d slice).
 #define GLB_FRAG(rsrc, ld, d, row, c0) \
     __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rsrc, ((row) < AT_N && (c0) < (d)) ? (unsigned)(((row) * (ld) + (c0)) * 2) : OOB_OFF, 0, 0))

@@ -25,14 +25,6 @@
 // have a fixed order (deterministic, no float atomics).
 #include "pk_common.h"
 
-typedef __attribute__((ext_vector_type(8))) short bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-
-#define OOB_OFF 0x80000000u
-#define MAKE_RSRC(ptr) __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(ptr), 0, 0x7ffffff0, 0x00020000)
 #define LOG2E_F 1.44269504088896340736f
 #define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0)
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, b, c, 0, 0, 0)
@@ -99,7 +91,7 @@ __device__ __forceinline__ int opaque_lane(int lane) {
 }
 
 // LayerNorm of one token row spread over the 4 lanes {j, j+16, j+32, j+48}: lane g holds channels 32k + 8g .. + 7 of K-step k
-// (natural order = the B-operand fragment).  Two-pass statistics as k_ln_fwd (pk_norm.hip).
+// (natural order = the B-operand fragment).  Two-pass statistics as k_ln_fwd (pk_ln.hip).
 template <int NK>
 __device__ __forceinline__ void ln_row(const u32x4 (&xr)[NK], const float (&gam)[NK][8], const float (&bet)[NK][8], float inv_c, float eps,
                                        bf16x8 (&vf)[NK], float& mean, float& rstd) {

@@ -16,7 +16,17 @@
 typedef __attribute__((ext_vector_type(8))) short bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
+typedef __attribute__((ext_vector_type(4))) short s16x4;
+typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 #define OOB_OFF 0x80000000u      // buffer-load offset beyond num_records: the hardware returns zeros
+// buffer descriptor over a bf16 tensor: no stride, the largest num_records, 16-bit elements
+#define MAKE_RSRC(ptr) __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(ptr), 0, 0x7ffffff0, 0x00020000)
+
+// Declares `i`, the member of a grouped launch that owns workgroup L: first[i] <= L < first[i + 1] (workgroup-uniform, i.e. scalar,
+// search over <= PK_GROUP_MAX entries of a table in the kernel arguments; a macro, so that the table is never addressed through a pointer)
+#define PK_GROUP_MEMBER(i, first, n, L) \
+    int i = 0;                          \
+    while (i + 1 < (n) && (L) >= (first)[i + 1]) ++i
 
 void pk_set_error(const char* fmt, ...);
 

@@ -262,7 +262,7 @@ extern "C" int pk_draw_shapes(void* images_u8, int N, int H, int W, const float*
 
 // ================================================================================================ heatmap overlay
 // draw_heatmaps of the reference (utils/visualization.py:93-127) for a batch: m = max over the K maps; m resized bilinearly to (H, W)
-// with the exchange units' half-pixel rule (bil_taps of pk_norm.hip restated); per-image min / max of the RESIZED plane (per-workgroup
+// with the exchange units' half-pixel rule (bil_taps of pk_exchange.hip restated); per-image min / max of the RESIZED plane (per-workgroup
 // partials, fixed-order finish: no atomics); v = (m - min) / (max - min + 1e-8); idx = floor(255 v); colour = LUT[idx];
 // out = (img (256 - a) + colour a + 128) >> 8 with a = clamp(rint(256 alpha), 0, 256).  The resize is evaluated twice (statistics pass
 // and blend pass) by the same function, so both passes see the same bits; the resized plane is never stored.

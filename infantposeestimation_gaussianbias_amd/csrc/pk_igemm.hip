@@ -246,8 +246,8 @@ __device__ __forceinline__ void igemm2_body(const IgemmArgs& p_in, const int bid
     constexpr bool DMA = (BN >= 128);
     const int kcg = DMA ? (kc ^ swz<BK>(row0)) : kc;   // chunk index on the global side (swz depends on row bit 3 only: same for row0 + 64 i)
 
-    const auto rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.x), 0, 0x7ffffff0, 0x00020000);
-    const auto rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.w), 0, 0x7ffffff0, 0x00020000);
+    const auto rx = MAKE_RSRC(p.x);
+    const auto rw = MAKE_RSRC(p.w);
 
     // Stride-2 data gradient (dilated gather): only the taps whose parity matches the output pixel's contribute -- 1, 2, 2 or 4 of the 9,
     // by parity class (oy & 1, ox & 1).  With p.dil_group the GEMM rows enumerate the output pixels class by class (class-major, then
@@ -706,8 +706,7 @@ struct IgemmGroup {
 template <int BM, int BN, int WM, int WN, int BK, int LEAN>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) k_igemm2g(IgemmGroup g) {
     const int L = (int)blockIdx.x;
-    int i = 0;
-    while (i + 1 < g.n && L >= g.first[i + 1]) ++i;          // workgroup-uniform (scalar) search over <= 12 entries
+    PK_GROUP_MEMBER(i, g.first, g.n, L);
     const int local = L - g.first[i], gy = g.gy[i], gx = (g.first[i + 1] - g.first[i]) / gy;
     igemm2_body<BM, BN, WM, WN, BK, LEAN>(g.a[i], local % gx, local / gx, gx, gy);
 }
@@ -773,8 +772,8 @@ __global__ void __launch_bounds__(512, 2) k_conv8p(IgemmArgs p) {
         nt = tile - mt * ntiles;
     }
     const int m0 = mt * 256, n0 = nt * 256;
-    const auto rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.x), 0, 0x7ffffff0, 0x00020000);
-    const auto rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.w), 0, 0x7ffffff0, 0x00020000);
+    const auto rx = MAKE_RSRC(p.x);
+    const auto rw = MAKE_RSRC(p.w);
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)c8_smem;
 
     // ---- DMA geometry: a 1 KiB piece = 16 rows x 64 bytes; in the pixel tile and in the weight tile this wave moves pieces wave and
@@ -965,7 +964,6 @@ __global__ void __launch_bounds__(512, 2) k_conv8p(IgemmArgs p) {
         if (m < p.M) *reinterpret_cast<u32x4*>(out + (size_t)m * p.ldo + n0 + wn * 64 + ch * 8) = v;
     }
 }
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 // ================================================================================================ halo kernel (small-channel 3x3 convs)
 // 3x3 stride-1 convolutions with 32 / 64 input and output channels on large maps (layer1, transitions and exchange units of HRFormer,
 // every BasicBlock of HRNet's high-resolution branches) are HBM-bound by arithmetic (64 -> 64 @64x48: 50 MB, 14.5 GFLOP) but ran at
@@ -1033,9 +1031,9 @@ __global__ void __launch_bounds__(256, 2) k_conv3h(IgemmArgs p, int pieces_per_w
             for (int i = tid; i < 4 * COUT; i += 256) p.stats[(size_t)blockIdx.x * 4 * COUT + i] = 0.f;
         return;
     }
-    const auto rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.x), 0, 0x7ffffff0, 0x00020000);
-    const auto ro = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<uint16_t*>(p.out), 0, 0x7ffffff0, 0x00020000);
-    const auto rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.res ? p.res : p.x), 0, 0x7ffffff0, 0x00020000);
+    const auto rx = MAKE_RSRC(p.x);
+    const auto ro = MAKE_RSRC((uint16_t*)p.out);
+    const auto rr = MAKE_RSRC(p.res ? p.res : p.x);
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)h3_smem;
 
     // ---- per-tap fragment base addresses (bytes from the start of a buffer): LDS row halo + 64 wm + (lane & 15) + tap offset, chunk lane >> 4

@@ -28,8 +28,6 @@ struct WgradArgs {
 };
 
 #define WG_MK 32
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-
 __device__ __forceinline__ bf16x8 tr_frag(const uint16_t* tile, int pitch, int col0, int lane) {
     // fragment for MFMA lane (col = col0 + lane&15, k-group g = lane>>4): elements k = 8g .. 8g+7 of that column
     const int g = lane >> 4, i = lane & 15, q = i >> 2, pq = i & 3;
@@ -66,8 +64,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TN == 
     const int m_end = min(p.M, m_begin + p.m_per_slice);
     const bool linear = (p.Ho == 0);
     const int hw = p.Ho * p.Wo;
-    const auto rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.x), 0, 0x7ffffff0, 0x00020000);
-    const auto rg = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.g), 0, 0x7ffffff0, 0x00020000);
+    const auto rx = MAKE_RSRC(p.x);
+    const auto rg = MAKE_RSRC(p.g);
 
     // fixed (row-in-step, chunk) assignment
     int g_row[G_PT], g_col[G_PT], x_row[X_PT], x_col[X_PT];
@@ -249,8 +247,8 @@ __global__ void __launch_bounds__(512, 2) k_wgrad3(WgradArgs p) {
     const int m_end = min(p.M, m_begin + p.m_per_slice);
     const int nsteps = (max(m_end - m_begin, 0) + W3_ROWS - 1) / W3_ROWS;
     const int hw = p.Ho * p.Wo;
-    const auto rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.x), 0, 0x7ffffff0, 0x00020000);
-    const auto rg = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.g), 0, 0x7ffffff0, 0x00020000);
+    const auto rx = MAKE_RSRC(p.x);
+    const auto rg = MAKE_RSRC(p.g);
     // this wave's DMA pieces: tile rows (4 wave + 2 j, + 1), j = 0, 1; lane -> (row within the pair, physical chunk).  The pixel
     // coordinates of the lane's row are carried from step to step (+32 rows with carries): the first version recomputed them with two
     // integer divisions per piece and step, ~200 VALU instructions per wave and step -- more issue time than the step's 32 MFMAs.
@@ -420,8 +418,8 @@ __device__ __forceinline__ void wgrad4_body(const WgradArgs& p, const int bid) {
     const int m_begin = zslice * p.m_per_slice;
     const int m_end = min(p.M, m_begin + p.m_per_slice);
     const int nsteps = (max(m_end - m_begin, 0) + 31) / 32;
-    const auto rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.x), 0, 0x7ffffff0, 0x00020000);
-    const auto rg = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.g), 0, 0x7ffffff0, 0x00020000);
+    const auto rx = MAKE_RSRC(p.x);
+    const auto rg = MAKE_RSRC(p.g);
     // this wave's pieces: G pieces wave + 4 j (j < PG), X pieces wave + 4 j (j < PX); lane -> (row in piece, physical chunk)
     const int ncols = COLS ? 9 * p.Cin : p.Cin;                      // columns of the X operand = row length of one output row
     int gm[PG], xm[PX];
@@ -562,8 +560,7 @@ struct WgradGroup {
 template <int TN, int TC, bool COLS>
 __global__ void __launch_bounds__(256, 2) k_wgrad4g(WgradGroup g) {
     const int L = (int)blockIdx.x;
-    int i = 0;
-    while (i + 1 < g.n && L >= g.first[i + 1]) ++i;
+    PK_GROUP_MEMBER(i, g.first, g.n, L);
     wgrad4_body<TN, TC, COLS>(g.a[i], L - g.first[i]);
 }
 
@@ -639,8 +636,8 @@ __global__ void __launch_bounds__(256, 2) k_wgrad4w(WgradArgs p) {
     const bool gwin = MODE == 0 ? p.g_rowmap != nullptr : MODE == 2, xwin = MODE == 0 ? p.a_rowmap != nullptr : MODE == 1,
                scaled = MODE == 0 ? p.g_scale != nullptr : MODE >= 2;     // workgroup-uniform; compile-time in the specialised instantiations
     const int nw = (p.Ws + 6) / 7, nh = (p.Hs + 6) / 7;
-    const auto rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.x), 0, 0x7ffffff0, 0x00020000);
-    const auto rg = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.g), 0, 0x7ffffff0, 0x00020000);
+    const auto rx = MAKE_RSRC(p.x);
+    const auto rg = MAKE_RSRC(p.g);
     const auto rs = __builtin_amdgcn_make_buffer_rsrc(scaled ? const_cast<float*>(p.g_scale) : (float*)const_cast<uint16_t*>(p.g), 0, 0x7ffffff0, 0x00020000);
     int gm[PG], xm[PX], gsb[PG], gsr[PG];
     unsigned gcb[PG], xcb[PX];                      // byte offset of the lane's chunk inside a source row
@@ -801,8 +798,8 @@ __global__ void __launch_bounds__(256, 2) k_wgrad4_3x3(WgradArgs p) {
     const int p_begin = zslice * p.m_per_slice;                              // multiple of 32
     const int p_end = min(MP, p_begin + p.m_per_slice);
     const int nsteps = (max(p_end - p_begin, 0) + 31) / 32;
-    const auto rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.x), 0, 0x7ffffff0, 0x00020000);
-    const auto rg = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.g), 0, 0x7ffffff0, 0x00020000);
+    const auto rx = MAKE_RSRC(p.x);
+    const auto rg = MAKE_RSRC(p.g);
     // DMA roles: 8 rows per 1 KiB piece, piece `wave` of every 32-row block; lane -> (row in piece, physical chunk).  The padded pixel
     // of the lane's row is carried as (b, py, px) and advanced by 32 per block.
     const int prow = 8 * wave + (lane >> 3);

@@ -8,102 +8,46 @@
 // tests/golden/launch_routes.txt.xz line for line: which kernel, tile and grid a shape gets is part of the library's behaviour.
 //
 // Build: hipcc --offload-host-only -O1 -std=c++17 tests/launch_recorder.hip -o launch_recorder
-#include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
+#include "launch_recorder.h"
 
-static char g_line[1 << 16];
-static size_t g_len = 0;
-static char g_err[1024];
-static void emit(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    const int n = vsnprintf(g_line + g_len, sizeof(g_line) - g_len, fmt, ap);
-    va_end(ap);
-    if (n > 0) g_len += (size_t)n < sizeof(g_line) - g_len ? (size_t)n : sizeof(g_line) - g_len - 1;
-}
-static void flush_line() {
-    fwrite(g_line, 1, g_len, stdout);
-    fputc('\n', stdout);
-    g_len = 0;
-}
-
-// launcher-set fields, one overload per argument-block type (the class overloads follow the units: found by argument-dependent lookup)
-static void rec_args(...) {}
-static void rec_args(const float* part, float* const&, int S, int, int, int, int layout, const float* bias_part, float* const&, int n_bias, int w_blocks) {
+// launcher-set fields, one overload per argument-block type
+static void rec_args(Rec, const float* part, float* const&, int S, int, int, int, int layout, const float* bias_part, float* const&, int n_bias, int w_blocks) {
     emit(" S=%d layout=%d bias_off=%ld n_bias=%d w_blocks=%d", S, layout, bias_part ? (long)(bias_part - part) : -1L, n_bias, w_blocks);
 }
-template <class... A>
-static void rec_launch(const char* kern, dim3 grid, dim3 block, size_t lds, const A&... a) {
-    emit(" | ");
-    for (const char* c = kern; *c; ++c)                      // the instantiation as the launch site spells it, without blanks and brackets
-        if (*c != ' ' && *c != '(' && *c != ')') emit("%c", *c);
-    emit(" g=%u,%u,%u b=%u l=%zu", grid.x, grid.y, grid.z, block.x, lds);
-    rec_args(a...);
-}
-#undef hipLaunchKernelGGL
-#define hipLaunchKernelGGL(kern, grid, block, lds, stream, ...) rec_launch(#kern, grid, block, lds, __VA_ARGS__)
-#define hipFuncSetAttribute(...) hipSuccess
-#define hipGetLastError() hipSuccess
-#define hipGetDevice(p) hipErrorNoDevice
-// kernels become plain device functions: the host side gets no launch stubs and needs no device code object to register
-#undef __global__
-#define __global__ __device__
-#undef __launch_bounds__
-#define __launch_bounds__(...)
-#define amdgpu_waves_per_eu(...)
 
 #include "../infantposeestimation_gaussianbias_amd/csrc/pk_igemm.hip"
 #include "../infantposeestimation_gaussianbias_amd/csrc/pk_wgrad.hip"
 
-void pk_set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-
-static void rec_args(const IgemmArgs& a) { emit(" v8=%d xr=%d cm=%d dg=%d", a.vec8, a.xcd_remap, a.chunk_major, a.dil_group); }
-static void rec_args(const IgemmArgs& a, const int& pieces_per_wave) {
-    rec_args(a);
+static void rec_args(Rec, const IgemmArgs& a) { emit(" v8=%d xr=%d cm=%d dg=%d", a.vec8, a.xcd_remap, a.chunk_major, a.dil_group); }
+static void rec_args(Rec, const IgemmArgs& a, const int& pieces_per_wave) {
+    rec_args(Rec{}, a);
     emit(" pp=%d", pieces_per_wave);
 }
-static void rec_args(const IgemmGroup& g) {
+static void rec_args(Rec, const IgemmGroup& g) {
     emit(" n=%d", g.n);
     for (int i = 0; i < g.n; ++i) {
         emit(" [%d gy=%d", g.first[i], g.gy[i]);
-        rec_args(g.a[i]);
+        rec_args(Rec{}, g.a[i]);
         emit("]");
     }
     emit(" end=%d", g.first[g.n]);
 }
-static void rec_args(const WgradArgs& a) {
+static void rec_args(Rec, const WgradArgs& a) {
     emit(" ct=%d nt3=%d ns3=%d mps=%d bias_off=%ld", a.ctiles, a.ntiles3, a.nslices3, a.m_per_slice, a.bias_part ? (long)(a.bias_part - a.part) : -1L);
 }
-static void rec_args(const WgradGroup& g) {
+static void rec_args(Rec, const WgradGroup& g) {
     emit(" n=%d", g.n);
     for (int i = 0; i < g.n; ++i) {
         emit(" [%d", g.first[i]);
-        rec_args(g.a[i]);
+        rec_args(Rec{}, g.a[i]);
         emit("]");
     }
     emit(" end=%d", g.first[g.n]);
 }
 
-static void finish(int rc) {
-    emit(" | rc=%d", rc);
-    if (rc) emit(" err=\"%s\"", g_err);
-    g_err[0] = 0;
-}
-
 // made-up addresses: 16-byte aligned unless an offset is added
-template <class T> static T* fake(uintptr_t base, uintptr_t off = 0) { return reinterpret_cast<T*>(base + off); }
 enum : uintptr_t { X_ = 0x10000000, W_ = 0x18000000, OUT_ = 0x20000000, STATS_ = 0x28000000, BIAS_ = 0x30000000, SCALE_ = 0x31000000,
                    RES_ = 0x38000000, MAP_ = 0x40000000, PRE_ = 0x48000000, WS_ = 0x50000000, DW_ = 0x58000000, DB_ = 0x5c000000 };
-static void* const STREAM = nullptr;
 
 static void set_switches(int sw) {        // 0: defaults, 1: both thresholds at one tile, 2: both specialised kernels off
     unsetenv("PK_CONV8P"); unsetenv("PK_CONV8P_MIN_TILES"); unsetenv("PK_CONV3H"); unsetenv("PK_CONV3H_MIN_TILES");

@@ -1,4 +1,4 @@
-"""GPU tests (`-m gpu`) of the normalisation and partial-sum kernels of csrc/pk_norm.hip at the row counts training runs.
+"""GPU tests (`-m gpu`) of the normalisation and partial-sum kernels of csrc/pk_bn.hip and csrc/pk_ln.hip at the row counts training runs.
 
 The library picks its code path from the tensor size (release builds have no run-time switch), so every case here is chosen by size:
 the fused one-launch BatchNorm paths (tiles <= 128 and rows <= 32768 forward, rows <= 32768 backward), the multi-launch paths behind
