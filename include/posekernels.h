@@ -8,9 +8,10 @@
  * Conventions (all entries):
  *   - extern "C", plain pointers and sizes; no C++/torch types.
  *   - every pointer is a BORROWED DEVICE pointer (caller allocates inputs, outputs and workspaces);
- *     the library allocates nothing and keeps no state besides a thread-local error string.  It reads four environment
- *     switches, per call, that route convolutions to / away from the two specialised kernels (PK_CONV8P, PK_CONV8P_MIN_TILES,
- *     PK_CONV3H, PK_CONV3H_MIN_TILES: used by the parity tests to push small shapes through them) and nothing else.
+ *     the library allocates nothing and keeps no state besides a thread-local error string.  It reads seven environment
+ *     switches, per call, that route convolutions to / away from the specialised kernels (PK_CONV8P, PK_CONV8P_MIN_TILES,
+ *     PK_CONV3H, PK_CONV3H_MIN_TILES, PK_CONV1X1_BN, PK_CONV1X1_BN_MIN_ROWS, PK_CONV1X1_BN_MAX_GRID: used by the parity tests to push
+ *     small shapes through them) and nothing else.
  *   - asynchronous on `stream` (a hipStream_t passed as void*); no internal synchronisation; graph-capturable.
  *   - returns 0 on success, a negative PK_ERR_* on argument validation failure (nothing launched),
  *     or a positive hipError_t from the launch.  Never throws, never aborts.
@@ -396,6 +397,34 @@ int pk_bn_bwd(const void* dy, const void* y_act, const void* raw, const float* s
               const float* gamma, float* partial, float* sums, float* dgamma, float* dbeta, void* dx, void* dresidual,
               int64_t rows, int C, int relu, const uint8_t* relu_mask, void* stream);
 int pk_relu_bwd(const void* dy, const void* y, void* dx, int64_t numel, void* stream);
+
+/* ---- 1x1 convolution 64 -> 256 + BatchNorm with the pre-normalisation tensor recomputed, never stored (pk_conv1x1_bn.hip): layer1's
+ * conv3 + bn3 and downsample branch (models/_blocks.py).  x: [rows][64] bf16, w: the packed forward weight [256][1][64] bf16; every
+ * 256-channel tensor [rows][256] bf16; all of them 16-byte aligned.  bf16(x w^T) is bit for bit what pk_conv2d_nhwc stores.
+ * pk_conv1x1_bn_supported: 1 for Cin = 64, Cout = 256, rows >= 32 768 (where pk_bn_train_fwd / pk_bn_bwd take their large-tensor form).
+ *   Per-call environment switches: PK_CONV1X1_BN=0 (route off), PK_CONV1X1_BN_MIN_ROWS (row threshold), PK_CONV1X1_BN_MAX_GRID (at most
+ *   this many workgroups per launch).
+ * pk_conv1x1_stats: the statistics-only pass: stats_partial [pk_conv1x1_stats_rows(rows)][2][Cout] sums / sums of squares of the fp32
+ *   accumulators per 128 rows, what pk_bn_finalize reads.
+ * pk_conv1x1_bn_act: y = relu?(bf16(conv) * scale + shift (+ residual)) and the ReLU bit mask, as pk_bn_act computes them from a stored raw.
+ * pk_conv1x1_bn_bwd: pk_bn_bwd (training mode; relu needs relu_mask) with (x, w) in place of raw: _bwd_reduce writes partial
+ *   [pk_conv1x1_bn_bwd_rows(rows)][2][Cout] (= pk_bn_bwd_blocks(rows): pk_bn_bwd's own partial rows, bit for bit), their fixed-order sum
+ *   goes to sums [2][Cout] and dbeta / dgamma, _bwd_apply writes draw and the optional dresidual; above 32 768 rows every output equals
+ *   pk_bn_bwd's on the stored raw bit for bit.                                                                                                          */
+int pk_conv1x1_bn_supported(int64_t rows, int Cin, int Cout);
+int pk_conv1x1_stats_rows(int64_t rows);
+int pk_conv1x1_bn_bwd_rows(int64_t rows);
+int pk_conv1x1_stats(const void* x, const void* w, float* stats_partial, int64_t rows, int Cin, int Cout, void* stream);
+int pk_conv1x1_bn_act(const void* x, const void* w, const float* scale, const float* shift, const void* residual, void* y, int relu,
+                      uint8_t* relu_mask, int64_t rows, int Cin, int Cout, void* stream);
+int pk_conv1x1_bn_bwd_reduce(const void* dy, const void* x, const void* w, const float* save_mean, const float* save_rstd, float* partial,
+                             int64_t rows, int Cin, int Cout, int relu, const uint8_t* relu_mask, void* stream);
+int pk_conv1x1_bn_bwd_apply(const void* dy, const void* x, const void* w, const float* save_mean, const float* save_rstd, const float* gamma,
+                            const float* sums, float inv_count, void* draw, void* dresidual, int64_t rows, int Cin, int Cout, int relu,
+                            const uint8_t* relu_mask, void* stream);
+int pk_conv1x1_bn_bwd(const void* dy, const void* x, const void* w, const float* save_mean, const float* save_rstd, const float* gamma,
+                      float* partial, float* sums, float* dgamma, float* dbeta, void* draw, void* dresidual, int64_t rows, int Cin, int Cout,
+                      int relu, const uint8_t* relu_mask, void* stream);
 /* nn.LayerNorm(C, eps 1e-5) over the channel dim of NHWC rows (hrformer.py:240,252,273,288).  C = row width (multiple of 8,
  * <= 1024); C_real (0 = C) = number of real channels when the rows carry zero padding: statistics over the real channels,
  * padded outputs / input gradients are zero.  gamma/beta (and dgamma/dbeta) have C entries, 16-byte aligned; the padded

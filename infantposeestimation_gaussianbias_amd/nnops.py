@@ -492,6 +492,20 @@ def _bn_backward(dy, y, mask, raw, mean, rstd, gamma, g_param, b_param, relu, tr
     return draw, dres, dgamma.grad(), dbeta.grad()
 
 
+def _conv1x1_bn_backward(dy, x, wf, mask, mean, rstd, gamma, g_param, b_param, relu, has_res, out_shape):
+    """_bn_backward (training mode) of the recomputing route: the pre-normalisation tensor comes from (x, wf) again instead of memory."""
+    C = out_shape[-1]
+    M, dev = x.numel() // x.shape[-1], x.device
+    nb = _lib.lib.pk_conv1x1_bn_bwd_rows(M)
+    part, sums = _e((nb, 2, C), F32, dev), _e((2 * C,), F32, dev)
+    dgamma, dbeta = _Dest(g_param), _Dest(b_param)
+    draw = _e(out_shape, BF16, dev)
+    dres = _e(out_shape, BF16, dev) if has_res else None
+    call("pk_conv1x1_bn_bwd", dy, x, wf, mean, rstd, gamma, part, sums, dgamma.t, dbeta.t, draw, dres, M, x.shape[-1], C, 1 if relu else 0, mask,
+         stream_ptr())
+    return draw, dres, dgamma.grad(), dbeta.grad()
+
+
 class _ConvBnAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, gamma, beta, residual, bn, stride, relu, training, skip_out=None, skip_in=None, infer=False):
@@ -512,23 +526,43 @@ class _ConvBnAct(torch.autograd.Function):
             y = _e((B, Ho, Wo, Cout), BF16, dev)
             call("pk_conv2d_affine_nhwc", x, wf, y, scale, shift, res, 1 if relu else 0, B, Hs, Ws, Cin, Cout, ksize, stride, Ho, Wo, stream_ptr())
             return y
-        raw, part = _conv_raw(x, wf, Cout, ksize, stride, training)
-        # ReLU mask as one bit per element (a byte per 16-byte chunk): BatchNorm backward reads it instead of y (1/16 of the bytes)
-        mask = _e((M * Cout // 8,), torch.uint8, dev) if (relu and not infer) else None
-        y, mean, rstd = _bn_forward(raw, part, gamma, beta, bn, res, relu, training, mask)
-        ctx.save_for_backward(x, raw, y if mask is None else mask, mean, rstd, gamma, wd)
+        # shallow 1x1 conv into a wide tensor (layer1's 64 -> 256 at >= 32 768 rows; the library is asked directly, as for pk_wgrad_slices):
+        # the pre-normalisation tensor is never stored, every BatchNorm pass recomputes its tile from x (pk_conv1x1_bn.hip)
+        ctx.recompute = bool(training and not infer and ksize == 1 and stride == 1 and _lib.lib.pk_conv1x1_bn_supported(M, Cin, Cout))
+        if ctx.recompute:
+            # statistics pass, finalize, apply pass; backward likewise from (x, wf).  Saved: no tensor of the output's size but the bit mask.
+            wc.bn_eval.pop(id(bn), None)
+            part = _e((_lib.lib.pk_conv1x1_stats_rows(M), 2, Cout), F32, dev)
+            call("pk_conv1x1_stats", x, wf, part, M, Cin, Cout, stream_ptr())
+            mask = _e((M * Cout // 8,), torch.uint8, dev) if relu else None
+            y = _e((B, Ho, Wo, Cout), BF16, dev)
+            scale, shift, mean, rstd = (_e((Cout,), F32, dev) for _ in range(4))
+            call("pk_bn_finalize", part, part.shape[0], Cout, M, gamma, beta, bn.running_mean, bn.running_var, bn.num_batches_tracked, 0.1, 1e-5,
+                 scale, shift, mean, rstd, stream_ptr())
+            call("pk_conv1x1_bn_act", x, wf, scale, shift, res, y, 1 if relu else 0, mask, M, Cin, Cout, stream_ptr())
+            ctx.save_for_backward(x, wf, x.new_empty(0) if mask is None else mask, mean, rstd, gamma, wd)
+        else:
+            raw, part = _conv_raw(x, wf, Cout, ksize, stride, training)
+            # ReLU mask as one bit per element (a byte per 16-byte chunk): BatchNorm backward reads it instead of y (1/16 of the bytes)
+            mask = _e((M * Cout // 8,), torch.uint8, dev) if (relu and not infer) else None
+            y, mean, rstd = _bn_forward(raw, part, gamma, beta, bn, res, relu, training, mask)
+            ctx.save_for_backward(x, raw, y if mask is None else mask, mean, rstd, gamma, wd)
         ctx.has_mask = mask is not None
-        ctx.meta = (stride, relu, training, residual is not None, Cin_real, ksize, (B, Hs, Ws, Ho, Wo))
+        ctx.meta = (stride, relu, training, residual is not None, Cin_real, ksize, (B, Hs, Ws, Ho, Wo), Cout)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, raw, y, mean, rstd, gamma, wd = ctx.saved_tensors
-        stride, relu, training, has_res, Cin_real, ksize, (B, Hs, Ws, Ho, Wo) = ctx.meta
-        Cout, Cin = raw.shape[-1], x.shape[-1]
+        stride, relu, training, has_res, Cin_real, ksize, (B, Hs, Ws, Ho, Wo), Cout = ctx.meta
+        Cin = x.shape[-1]
         w_p, g_p, b_p = ctx.params
-        draw, dres, dgamma, dbeta = _bn_backward(dy.contiguous(), None if ctx.has_mask else y, y if ctx.has_mask else None, raw, mean, rstd,
-                                                 gamma, g_p, b_p, relu, training, has_res)
+        if ctx.recompute:
+            draw, dres, dgamma, dbeta = _conv1x1_bn_backward(dy.contiguous(), x, raw, y if ctx.has_mask else None, mean, rstd, gamma, g_p, b_p,
+                                                             relu, has_res, (B, Ho, Wo, Cout))
+        else:
+            draw, dres, dgamma, dbeta = _bn_backward(dy.contiguous(), None if ctx.has_mask else y, y if ctx.has_mask else None, raw, mean, rstd,
+                                                     gamma, g_p, b_p, relu, training, has_res)
         addend = None
         if ctx.skip_in is not None:
             addend, ctx.skip_in.g = ctx.skip_in.g, None
