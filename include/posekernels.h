@@ -251,6 +251,24 @@ int pk_spatial_stats_bwd(const float* heatmaps, const float* mean, const float* 
 int pk_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const uint8_t* decay_mask,
                   uint16_t* param_bf16, int64_t n, const float* lr_dev, const int32_t* step_dev,
                   float beta1, float beta2, float eps, float weight_decay, float grad_scale, void* stream);
+/* Guarded step (opt-in; what GradScaler.step + clip_grad_norm_ do around optimizer.step in the reference's train.py:182-184): three
+ * launches on one stream, no atomics, no host read, every sum in a fixed order.
+ * pk_grad_sumsq: fp64 sum of grad^2 over the elements whose flag has bit1 set (the ones pk_adamw_step updates; everything else is
+ *   ignored whatever it holds).  partials: 2 doubles per workgroup {sum, 1.0 if an element had all exponent bits set else 0.0};
+ *   n_partials must be pk_grad_sumsq_partials(n), the grid size (a function of n only).
+ * pk_grad_guard_finalize: norm = grad_scale*sqrt(total); c = max_norm/(norm+1e-6); coef = (max_norm>0 && finite && c<1) ? c : 1
+ *   (torch.nn.utils.clip_grad_norm_); skip = any non-finite flag.  guard_state: 4 words {float norm, float coef, int32 skipped_last,
+ *   int32 skipped_total (+1 on skip)}.  step_dev[0] += 1 only when the step is NOT skipped (it counts applied updates).
+ * pk_adamw_step_guarded: pk_adamw_step with gradient factor grad_scale*coef; touches nothing when skipped_last is set.  With
+ *   coef == 1 the result is bitwise pk_adamw_step's.                                                                            */
+int pk_grad_sumsq_partials(int64_t n);
+int pk_grad_sumsq(const float* grad, const uint8_t* flags, int64_t n, double* partials, int n_partials, void* stream);
+int pk_grad_guard_finalize(const double* partials, int n_partials, float grad_scale, float max_norm, int32_t* guard_state,
+                           int32_t* step_dev, void* stream);
+int pk_adamw_step_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const uint8_t* decay_mask,
+                          uint16_t* param_bf16, int64_t n, const float* lr_dev, const int32_t* step_dev,
+                          float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                          const int32_t* guard_state, void* stream);
 
 
 /* ======================= network contractions (bf16 MFMA, fp32 accumulate; NHWC activations) =======================

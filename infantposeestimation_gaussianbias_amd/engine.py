@@ -42,9 +42,17 @@ class FlatAdamW:
 
     ALIGN = 4            # elements: every tensor starts 16-byte aligned inside the flat buffers
 
-    def __init__(self, model: torch.nn.Module, lr=5e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, direct_grads=False):
+    def __init__(self, model: torch.nn.Module, lr=5e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, direct_grads=False,
+                 clip_grad_norm=0.0, skip_nonfinite=False):
+        """`clip_grad_norm` > 0 (torch.nn.utils.clip_grad_norm_'s max_norm) or `skip_nonfinite` select the guarded step: the global
+        gradient norm is reduced on the device, the update is scaled by the clip coefficient and dropped as a whole when a gradient is
+        inf / NaN (what GradScaler.step does in the reference).  A non-finite norm cannot clip anything, so clipping implies skipping."""
+        if not (math.isfinite(clip_grad_norm) and clip_grad_norm >= 0):
+            raise ValueError(f"clip_grad_norm must be finite and >= 0 (0 = off), got {clip_grad_norm}")
         self.model = model
         self.direct_grads = direct_grads
+        self.clip_grad_norm = float(clip_grad_norm)
+        self.guarded = self.clip_grad_norm > 0 or bool(skip_nonfinite)
         named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
         if not named:
             raise ValueError("model has no trainable parameters")
@@ -72,7 +80,11 @@ class FlatAdamW:
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         self.lr_dev = torch.full((1,), lr, dtype=torch.float32, device=dev)
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.step_count = 0
+        self.step_count = 0          # steps taken; guarded mode: steps ATTEMPTED (step_dev counts the applied ones)
+        if self.guarded:
+            # static buffers (a captured graph holds their addresses): per-workgroup partial sums, and the record the update reads
+            self.guard_partials = torch.zeros(hipops.grad_sumsq_partials(off), 2, dtype=torch.float64, device=dev)
+            self.guard_state = torch.zeros(hipops.GUARD_STATE_WORDS, dtype=torch.int32, device=dev)
 
     # -- gradient storage ---------------------------------------------------------------------------------
     def grad_view(self, i):
@@ -132,15 +144,31 @@ class FlatAdamW:
                     self.grad_view(i).zero_()
         self._sinks_armed = self.direct_grads
         self.step_count += 1
-        self.step_dev.add_(1)
-        hipops.adamw_step(self.flat, self.grad, self.exp_avg, self.exp_avg_sq, self.flags, None, self.lr_dev, self.step_dev,
-                          self.betas[0], self.betas[1], self.eps, self.weight_decay, grad_scale)
+        if self.guarded:
+            # the finalize kernel advances step_dev, and only when the update is applied
+            hipops.grad_sumsq(self.grad, self.flags, self.guard_partials)
+            hipops.grad_guard_finalize(self.guard_partials, grad_scale, self.clip_grad_norm, self.guard_state, self.step_dev)
+            hipops.adamw_step_guarded(self.flat, self.grad, self.exp_avg, self.exp_avg_sq, self.flags, None, self.lr_dev, self.step_dev,
+                                      self.betas[0], self.betas[1], self.eps, self.weight_decay, self.guard_state, grad_scale)
+        else:
+            self.step_dev.add_(1)
+            hipops.adamw_step(self.flat, self.grad, self.exp_avg, self.exp_avg_sq, self.flags, None, self.lr_dev, self.step_dev,
+                              self.betas[0], self.betas[1], self.eps, self.weight_decay, grad_scale)
         wc = getattr(self.model, "_pk_weight_cache", None)
         if wc is not None:
             wc.mark_dirty()          # the kernel rewrote the fp32 masters behind torch's back: bf16 copies are stale
         tw = getattr(self.model, "_pk_twin", None)
         if tw:
             tw.mark_dirty()          # ... and so is the padded twin's embedded copy
+
+    def guard_stats(self):
+        """Last step's gradient norm (after grad_scale, before clipping), clip coefficient, whether it was skipped, and the number of
+        skipped steps so far.  One device read: for the log interval, never for the step path."""
+        if not self.guarded:
+            raise RuntimeError("guard_stats: the guarded step is off (clip_grad_norm=0, skip_nonfinite=False)")
+        st = self.guard_state.cpu()
+        norm, coef = st[:2].view(torch.float32).tolist()
+        return {"grad_norm": norm, "clip_coef": coef, "skipped_last": int(st[2]), "skipped_steps": int(st[3])}
 
     # -- checkpoint format of the reference (train.py:351-357): per-parameter state keyed by index ---------------
     def state_dict(self):
@@ -149,11 +177,13 @@ class FlatAdamW:
         order = decay + nodecay
         remap = {old: new for new, old in enumerate(order)}
         state = {}
+        # guarded mode: "step" is the number of APPLIED updates (the bias correction's t), which only the device knows
+        steps = int(self.step_dev) if self.guarded else self.step_count
         for i, p in enumerate(self.params):
-            if not self.active[i] or self.step_count == 0:
+            if not self.active[i] or steps == 0:
                 continue
             o, n = self.offsets[i], p.numel()
-            state[remap[i]] = {"step": torch.tensor(float(self.step_count)),
+            state[remap[i]] = {"step": torch.tensor(float(steps)),
                                "exp_avg": self.exp_avg[o:o + n].view_as(p).clone(),
                                "exp_avg_sq": self.exp_avg_sq[o:o + n].view_as(p).clone()}
         common = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "amsgrad": False, "maximize": False,
@@ -341,7 +371,7 @@ class Trainer:
     each replay, so the per-iteration schedule advances normally.  Batches are copied into static input buffers."""
 
     def __init__(self, model, cfg, iters_per_epoch: int, bucket_mb: float = 8.0, use_graph: bool = False, graph_warmup: int = 3,
-                 overlap_comm: bool = True, graph_streams: bool = False):
+                 overlap_comm: bool = True, graph_streams: bool = False, clip_grad_norm: float = 0.0, skip_nonfinite: bool = False):
         self.model, self.cfg = model, cfg
         self.overlap_comm = overlap_comm
         # concurrent branch streams: on for eager steps; inside a captured graph only on request (fork/join capture across
@@ -352,7 +382,11 @@ class Trainer:
         if t.optimizer != "AdamW":
             raise ValueError(f"Unknown optimizer: {t.optimizer}")   # the fused kernel implements the reference default only
         # gradients are stored directly by the backward kernels (gradient sinks); the exchange is driven by backward milestones
-        self.opt = FlatAdamW(model, t.lr, tuple(t.betas), 1e-8, t.weight_decay, direct_grads=True)
+        # clip_grad_norm / skip_nonfinite: the guarded step lives inside opt.step, so eager steps, the captured whole step and the
+        # optimiser between forward+backward-only replays all take it; the LR schedule advances on skipped steps too (as the
+        # reference's scheduler.step() does)
+        self.opt = FlatAdamW(model, t.lr, tuple(t.betas), 1e-8, t.weight_decay, direct_grads=True, clip_grad_norm=clip_grad_norm,
+                             skip_nonfinite=skip_nonfinite)
         self.sched = WarmupMultiStepLR(self.opt, t, iters_per_epoch)
         self.comm = GradientExchange(self.opt, bucket_mb, overlap=overlap_comm)
         self.comm.broadcast_initial_state()
@@ -471,7 +505,9 @@ class Trainer:
             v.copy_(batch[k], non_blocking=True)
         self._graph.replay()
         if self._graph_has_opt:
-            self.opt.step_count += 1          # the captured pk_adamw_step already advanced the device-side counter
+            # the captured optimiser launches already advanced the device-side counter (guarded mode: unless they skipped the
+            # update; step_count then counts attempted steps)
+            self.opt.step_count += 1
             # ... and rewrote the fp32 masters behind torch's back: the bf16 compute copies (and a padded twin's embedded
             # parameters) are one step behind until the next forward repacks them
             wc = getattr(self.model, "_pk_weight_cache", None)

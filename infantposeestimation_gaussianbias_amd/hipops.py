@@ -701,3 +701,50 @@ def heatmap_overlay_patches(images, heatmaps, image_index, matrices, alpha, lut,
 def adamw_step(param, grad, exp_avg, exp_avg_sq, flags, param_bf16, lr_dev, step_dev, beta1, beta2, eps, weight_decay, grad_scale=1.0):
     call("pk_adamw_step", param, grad, exp_avg, exp_avg_sq, flags, param_bf16, param.numel(), lr_dev, step_dev, float(beta1), float(beta2),
          float(eps), float(weight_decay), float(grad_scale), stream_ptr())
+
+
+# Guarded step: grad_sumsq -> grad_guard_finalize -> adamw_step_guarded on the current stream.  The norm and the skip decision are
+# written to `guard_state` on the device and read there by the update; nothing here reads them back.
+GUARD_STATE_WORDS = 4          # {float norm, float coef, int32 skipped_last, int32 skipped_total}
+
+
+def grad_sumsq_partials(n):
+    """Workgroups pk_grad_sumsq launches for n elements (a function of n only): `partials` is a (that many, 2) float64 tensor."""
+    k = _lib.lib.pk_grad_sumsq_partials(int(n))
+    if k <= 0:
+        raise _lib.PoseKernelError(f"pk_grad_sumsq_partials failed: {_lib.lib.pk_last_error_string().decode()}")
+    return k
+
+
+def _chk_guard_state(guard_state):
+    if _chk(guard_state, I32, "guard_state").numel() != GUARD_STATE_WORDS:
+        raise _lib.PoseKernelError(f"guard_state: expected {GUARD_STATE_WORDS} int32 words, got {guard_state.numel()}")
+
+
+def _chk_partials(partials):
+    if not (isinstance(partials, torch.Tensor) and partials.is_cuda and partials.dtype == torch.float64 and partials.dim() == 2
+            and partials.shape[1] == 2 and partials.is_contiguous()):
+        raise _lib.PoseKernelError("partials: expected a contiguous (n_partials, 2) float64 CUDA(HIP) tensor")
+
+
+def grad_sumsq(grad, flags, partials):
+    """partials[b] = {fp64 sum of grad^2 over workgroup b's share of the elements with flag bit1, 1.0 if one of them is inf/NaN else 0.0}."""
+    _chk_partials(partials)
+    if _chk(flags, torch.uint8, "flags").numel() != _chk(grad, name="grad").numel():
+        raise _lib.PoseKernelError(f"grad_sumsq: {grad.numel()} gradients but {flags.numel()} flags")
+    call("pk_grad_sumsq", grad, flags, grad.numel(), partials, partials.shape[0], stream_ptr())
+    return partials
+
+
+def grad_guard_finalize(partials, grad_scale, max_norm, guard_state, step_dev):
+    _chk_partials(partials)
+    _chk_guard_state(guard_state)
+    call("pk_grad_guard_finalize", partials, partials.shape[0], float(grad_scale), float(max_norm), guard_state,
+         _chk(step_dev, I32, "step_dev"), stream_ptr())
+
+
+def adamw_step_guarded(param, grad, exp_avg, exp_avg_sq, flags, param_bf16, lr_dev, step_dev, beta1, beta2, eps, weight_decay, guard_state,
+                       grad_scale=1.0):
+    _chk_guard_state(guard_state)
+    call("pk_adamw_step_guarded", param, grad, exp_avg, exp_avg_sq, flags, param_bf16, param.numel(), lr_dev, step_dev, float(beta1),
+         float(beta2), float(eps), float(weight_decay), float(grad_scale), guard_state, stream_ptr())

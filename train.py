@@ -6,8 +6,9 @@
 
 Differences from the reference loop (train.py:131-228): no per-step `loss.item()` host sync (losses are read back only at the
 log interval), bf16 instead of fp16+GradScaler, fused AdamW over a flat parameter buffer, optional hipGraph replay
-(`--graph`), colour jitter on the device (`--color_jitter B C S`, or DATA.COLOR_JITTER of a legacy yaml).  With POSE_SYNTHETIC=1 the
-loader yields device-resident synthetic batches (no COCO on disk needed; they are not jittered).
+(`--graph`), GradScaler's "drop the step when a gradient is inf/NaN" and gradient-norm clipping as an opt-in device-side guard
+(`--skip_nonfinite`, `--clip_grad_norm X`), colour jitter on the device (`--color_jitter B C S`, or DATA.COLOR_JITTER of a legacy
+yaml).  With POSE_SYNTHETIC=1 the loader yields device-resident synthetic batches (no COCO on disk needed; they are not jittered).
 """
 import argparse
 import copy
@@ -66,6 +67,9 @@ def train_one_epoch(trainer, loader, epoch, cfg, logger, rank):
                        f"LR: {trainer.opt.lr:.6f} Time: {batch_time.val:.3f}s")
                 if "losses" in out:
                     msg += " | " + ", ".join(f"{k}: {float(v.detach()):.4f}" for k, v in out["losses"].items() if k != "total_loss")
+                if trainer.opt.guarded:
+                    gs = trainer.opt.guard_stats()
+                    msg += f" | grad_norm: {gs['grad_norm']:.4g} clip_coef: {gs['clip_coef']:.4g} skipped_steps: {gs['skipped_steps']}"
                 logger.info(msg)
     return loss_meter.avg
 
@@ -94,7 +98,8 @@ def main(args):
     out_dir = os.path.join(cfg.train.checkpoint_dir, f"{cfg.exp_name}_{datetime.now().strftime('%Y%m%d_%H%M%S')}")
     loader = build_dataloader(cfg, is_train=True)
     model = build_model(cfg).to(torch.device("cuda", local))
-    trainer = engine.Trainer(model, cfg, iters_per_epoch=len(loader), use_graph=args.graph, graph_streams=args.graph)
+    trainer = engine.Trainer(model, cfg, iters_per_epoch=len(loader), use_graph=args.graph, graph_streams=args.graph,
+                             clip_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite)
     start_epoch, best_ap = 0, 0.0
     if args.resume and os.path.isfile(args.resume):
         ckpt = torch.load(args.resume, map_location="cpu", weights_only=True)
@@ -132,7 +137,7 @@ def main(args):
         dist.destroy_process_group()
 
 
-if __name__ == "__main__":
+def build_parser():
     p = argparse.ArgumentParser(description="Train Pose Estimation Model")
     p.add_argument("--data_root", type=str, default=None)
     p.add_argument("--batch_size", type=int, default=None)
@@ -144,4 +149,12 @@ if __name__ == "__main__":
     p.add_argument("--color_jitter", type=float, nargs=3, default=None, metavar=("B", "C", "S"),
                    help="brightness / contrast / saturation ranges of the colour jitter applied to training crops on the device")
     p.add_argument("--color_jitter_prob", type=float, default=None, help="share of the samples that are jittered (default 0.5)")
-    main(p.parse_args())
+    p.add_argument("--clip_grad_norm", type=float, default=0.0, metavar="X",
+                   help="clip the global gradient norm to X on the device (torch.nn.utils.clip_grad_norm_; 0 = off); implies --skip_nonfinite")
+    p.add_argument("--skip_nonfinite", action="store_true",
+                   help="drop the whole optimiser step when a gradient is inf or NaN (what GradScaler.step does in the reference)")
+    return p
+
+
+if __name__ == "__main__":
+    main(build_parser().parse_args())
