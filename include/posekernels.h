@@ -56,6 +56,26 @@ int pk_dense_target(const float* keypoints, const float* visible, float* heatmap
 int pk_argmax_decode(const float* heatmaps, int32_t* index, float* maxval, float* coords,
                      int BK, int H, int W, int mode, void* stream);
 
+/* ---- Unbiased (distribution-aware, "DARK") decode: this project's own specification (DESIGN.md "Unbiased decoding"; the reference names
+ * TEST.POST_PROCESS in its yamls and implements nothing beyond modes 1 and 2 above).  One workgroup per map; NaN counts as the maximum and
+ * ties go to the lowest flat index, as in pk_argmax_decode.  taps_host: HOST pointer to ksize floats (odd, 3 .. 31), read before the call
+ * returns and carried in the kernel's arguments (no device table, no allocation: graph-capturable).  index (BK) int32, maxval (BK) and
+ * refined (BK) uint8 may be NULL; coords (BK,2) may not.  The published form blurs the whole map and rescales it to the raw maximum
+ * before the logarithm; that rescale adds a constant to the log map and cancels in every difference below, so it is dropped, and only
+ * the 13 stencil points need the blur: every heatmap element is read from global memory once (the argmax), then a (ksize + 4) x 5 patch is
+ * blurred.  All float32, one rounding per operation, in this order, with c = (ksize-1)/2 and m = 0 outside the map (zero padding):
+ *   (px, py) = first maximum of m;  maxval = m[py][px];  index = py W + px;
+ *   R[y][x] = sum_t g[t] m[y][x+t-c]:  acc = 0.0f, then acc = fmaf(g[t], v, acc) for t = 0 .. ksize-1;   B[y][x] = sum_t g[t] R[y+t-c][x], alike;
+ *   L = logf(fmaxf(B, 1e-10f));   with L(j, i) = L[py+j][px+i]:
+ *   dx = 0.5f (L(0,1) - L(0,-1));  dy = 0.5f (L(1,0) - L(-1,0));  dxx = 0.25f (L(0,2) - 2 L(0,0) + L(0,-2));  dyy = 0.25f (L(2,0) - 2 L(0,0) + L(-2,0));
+ *   dxy = 0.25f (L(1,1) - L(-1,1) - L(1,-1) + L(-1,-1));   det = dxx dyy - dxy dxy;   ox = -(dyy dx - dxy dy) / det;   oy = -(dxx dy - dxy dx) / det.
+ * The step is taken iff 2 <= px <= W-3 and 2 <= py <= H-3, dxx < 0 and det > 0 (a maximum), |ox| <= 2 and |oy| <= 2 (the reach of the
+ * stencil) -- positive comparisons, which a NaN fails.  Then refined = 1 and coords = (px + ox, py + oy); otherwise refined = 0 and coords =
+ * (px, py), exactly the integers (constant, all-zero and non-positive maps, NaN / inf maps, border peaks).  Two launches: identical bytes.
+ * PK_ERR_INVALID, before any launch: null heatmaps / coords / taps_host, a ksize that is even or outside 3 .. 31, a bad shape.          */
+int pk_unbiased_decode(const float* heatmaps, const float* taps_host, int ksize, int32_t* index, float* maxval, float* coords,
+                       uint8_t* refined, int BK, int H, int W, void* stream);
+
 /* ---- D1: HeatmapRegressionHead.decode (models/fusion_head.py:309-365) = SoftArgmax2D (:24-71) +
  * LocalGaussianRefinement (:74-128) + alpha blend (:169-170) + offset sampling.  alpha/fusion_weight are the
  * RAW parameters (sigmoid applied inside), read from device memory.  offsets may be NULL (apply_offset=False). */

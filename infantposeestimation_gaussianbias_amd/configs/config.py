@@ -11,7 +11,10 @@ identically.  Extension over the reference: `get_config(path_or_name)` also acce
     MIN_KEYPOINT_VISIBILITY}` onto `cfg.eval_metrics` / `pck_threshold` / `min_keypoint_visibility`, `TEMPORAL.*` onto `cfg.temporal` and
     `CLINICAL.*` onto `cfg.clinical` (movement analysis: utils/metrics.py, `validate.py --pck`, `inference.py --sequence`), and
     `TEST.{COCO_BBOX_FILE, IMAGE_THRE, OKS_THRE, IN_VIS_THRE, SOFT_NMS}` onto `cfg.bbox_file` / `det_score_thr` / `oks_nms_thr` /
-    `in_vis_thr` / `soft_nms` (validation on detector boxes; `TEST.USE_GT_BBOX: false` without a box file changes nothing and says so).
+    `in_vis_thr` / `soft_nms` (validation on detector boxes; `TEST.USE_GT_BBOX: false` without a box file changes nothing and says so),
+    and `TEST.DECODE: 'shift' | 'unbiased'` / `TEST.MODULATE_KERNEL` onto `cfg.decode` / `cfg.modulate_kernel` (the heatmap decode of the
+    heatmap-head models; a bad value raises and names the key).  `TEST.POST_PROCESS` and `TEST.SHIFT_HEATMAP` are deliberately NOT mapped:
+    both shipped yamls set them true, and mapping them would change what those configurations do today.
 """
 import logging
 import math
@@ -115,6 +118,11 @@ class Config:
     oks_nms_thr = None
     in_vis_thr = 0.2
     soft_nms = False
+    # Heatmap decode of the heatmap-head models (legacy yaml TEST.DECODE / TEST.MODULATE_KERNEL, `--decode / --modulate_kernel`), plain class
+    # attributes as well.  decode: None or 'shift' (argmax + quarter-pixel shift) or 'unbiased' (distribution-aware: one Newton step on the
+    # log of the map smoothed with `modulate_kernel` Gaussian taps, an odd size from 3 to 31).
+    decode = None
+    modulate_kernel = 11
 
 
 _PRESETS = {
@@ -144,6 +152,21 @@ def check_test_scales(scales) -> Tuple[float, ...]:
     if sc.count(1.0) != 1:
         raise ValueError(f"test scales need exactly one 1.0 (the base crop), got {sc}")
     return sc
+
+
+def check_decode(decode, modulate_kernel=11, what=("decode", "modulate_kernel")):
+    """The decode choice and its smoothing size as (None | 'shift' | 'unbiased', int): ValueError naming `what` (the key or flag the value
+    came from) for any other choice, or a size that is not an odd integer from 3 to 31."""
+    if decode is not None and decode not in ("shift", "unbiased"):
+        raise ValueError(f"{what[0]} must be 'shift' or 'unbiased', got {decode!r}")
+    try:
+        k = int(modulate_kernel)
+        ok = not isinstance(modulate_kernel, bool) and k == modulate_kernel and 3 <= k <= 31 and k % 2 == 1
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"{what[1]} must be an odd integer from 3 to 31, got {modulate_kernel!r}")
+    return decode, k
 
 
 def _apply_preset(cfg: Config, name: str) -> Config:
@@ -216,6 +239,11 @@ def _apply_legacy_yaml(cfg: Config, path: str) -> Config:
             setattr(cfg, dst, float(te[src]))
     if 'SOFT_NMS' in te:
         cfg.soft_nms = bool(te['SOFT_NMS'])
+    # TEST.DECODE / TEST.MODULATE_KERNEL choose the heatmap decode.  TEST.POST_PROCESS and TEST.SHIFT_HEATMAP are NOT mapped: both shipped
+    # yamls set them true, so mapping them would change what those configurations compute today.
+    if te.get('DECODE') is not None or te.get('MODULATE_KERNEL') is not None:
+        cfg.decode, cfg.modulate_kernel = check_decode(te.get('DECODE'), te.get('MODULATE_KERNEL', Config.modulate_kernel),
+                                                       ('TEST.DECODE', 'TEST.MODULATE_KERNEL'))
     if te.get('USE_GT_BBOX') is False and cfg.bbox_file is None:
         logging.getLogger(__name__).warning(f"{path}: TEST.USE_GT_BBOX is false but no TEST.COCO_BBOX_FILE is given: validation keeps "
                                             "cropping from the ground-truth boxes")

@@ -216,6 +216,120 @@ extern "C" int pk_argmax_decode(const float* heatmaps, int32_t* index, float* ma
     return pk_launch_status("pk_argmax_decode");
 }
 
+// ================================================================================================ unbiased (DARK) decode
+// Distribution-aware decoding: argmax, then one Newton step of the quadratic fitted to the logarithm of the Gaussian-smoothed map
+// (include/posekernels.h states every operation; tests/unbiased_np.py restates it over the whole map).  The published form blurs the
+// whole map and rescales it to the raw maximum before the logarithm; the rescale adds one constant to the log map, which cancels in every
+// difference the step is made of, so it is dropped -- and without it only the 13 stencil points around the argmax need the blur.  Each
+// heatmap element is therefore read from global memory ONCE, by am_block; the workgroup then blurs a (ksize + 4) x 5 patch: the row pass
+// into LDS (one thread per entry, its ksize taps come back out of L2), the column pass at the 5 x 5 points, and lane 0 takes the step.
+// Both passes fetch their operands UB_CHUNK at a time from addresses that are always valid (clamped; what lies outside is replaced by 0
+// afterwards), so a chunk's loads are in flight together and only the fmaf chain is serial: this tail is latency, not bandwidth.
+// The taps ride in the kernel arguments (no device table); every operation is rounded once, in a fixed order: the same bits on every run.
+#define UB_MAX_K 31
+#define UB_CHUNK 16
+struct UbTaps {
+    float v[UB_MAX_K];
+};
+__global__ void __launch_bounds__(256) k_unbiased_decode(const float* __restrict__ hm, UbTaps taps, int ksize, int32_t* __restrict__ index,
+                                                         float* __restrict__ maxval, float* __restrict__ coords,
+                                                         uint8_t* __restrict__ refined, int H, int W) {
+    __shared__ float sv[4];
+    __shared__ int si[4];
+    __shared__ float sg[2 * UB_CHUNK];
+    __shared__ float sR[(UB_MAX_K + 4) * 5];
+    __shared__ float sL[25];
+    const int map = blockIdx.x, tid = threadIdx.x;
+    if (tid == 0) {      // static indices into the argument struct; am_block's barrier publishes sg
+#pragma unroll
+        for (int t = 0; t < 2 * UB_CHUNK; ++t) sg[t] = t < UB_MAX_K ? taps.v[t] : 0.0f;
+    }
+    const float* m = hm + (size_t)map * H * W;
+    const ArgMax r = am_block(m, H * W, sv, si);
+    const int px = r.i % W, py = r.i / W;
+    if (tid == 0) {
+        if (index) index[map] = r.i;
+        if (maxval) maxval[map] = r.v;
+    }
+    if (!(px >= 2 && px <= W - 3 && py >= 2 && py <= H - 3)) {      // uniform over the workgroup: no stencil, no step
+        if (tid == 0) {
+            coords[2 * map] = (float)px;
+            coords[2 * map + 1] = (float)py;
+            if (refined) refined[map] = 0;
+        }
+        return;
+    }
+    const int c = (ksize - 1) / 2, rows = ksize + 4;
+    // row pass: R[y][x] for y = py-2-c .. py+2+c, x = px-2 .. px+2; m counts as 0 outside the map (the tap is still multiplied in)
+    for (int e = tid; e < rows * 5; e += blockDim.x) {
+        const int rr = e / 5, y = py - 2 - c + rr, x0 = px - 2 + (e - rr * 5) - c;
+        const bool row_in = y >= 0 && y < H;
+        const float* mrow = m + min(max(y, 0), H - 1) * W;
+        float acc = 0.0f;
+        for (int t0 = 0; t0 < ksize; t0 += UB_CHUNK) {
+            float v[UB_CHUNK], g[UB_CHUNK];
+#pragma unroll
+            for (int j = 0; j < UB_CHUNK; ++j) {
+                const int x = x0 + t0 + j;
+                g[j] = sg[t0 + j];
+                const float raw = mrow[min(max(x, 0), W - 1)];
+                // a bit mask, not a select: a select lets the compiler sink the load into a branch of its own and wait for each one
+                const unsigned keep = 0u - (unsigned)(row_in & (x >= 0) & (x < W));
+                v[j] = __uint_as_float(__float_as_uint(raw) & keep);
+            }
+#pragma unroll
+            for (int j = 0; j < UB_CHUNK; ++j)
+                if (t0 + j < ksize) acc = fmaf(g[j], v[j], acc);
+        }
+        sR[e] = acc;
+    }
+    __syncthreads();
+    if (tid < 25) {      // column pass and logarithm at (py + tid/5 - 2, px + tid%5 - 2)
+        const int ry = tid / 5, cx = tid - ry * 5;
+        float acc = 0.0f;
+        for (int t0 = 0; t0 < ksize; t0 += UB_CHUNK) {
+            float v[UB_CHUNK], g[UB_CHUNK];
+#pragma unroll
+            for (int j = 0; j < UB_CHUNK; ++j) {
+                g[j] = sg[t0 + j];
+                v[j] = sR[(ry + min(t0 + j, ksize - 1)) * 5 + cx];
+            }
+#pragma unroll
+            for (int j = 0; j < UB_CHUNK; ++j)
+                if (t0 + j < ksize) acc = fmaf(g[j], v[j], acc);
+        }
+        sL[tid] = logf(fmaxf(acc, 1e-10f));
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    auto L = [&](int dy, int dx) { return sL[(dy + 2) * 5 + dx + 2]; };
+    const float two_l0 = __fmul_rn(2.0f, L(0, 0));
+    const float dx = __fmul_rn(0.5f, __fsub_rn(L(0, 1), L(0, -1))), dy = __fmul_rn(0.5f, __fsub_rn(L(1, 0), L(-1, 0)));
+    const float dxx = __fmul_rn(0.25f, __fadd_rn(__fsub_rn(L(0, 2), two_l0), L(0, -2)));
+    const float dyy = __fmul_rn(0.25f, __fadd_rn(__fsub_rn(L(2, 0), two_l0), L(-2, 0)));
+    const float dxy = __fmul_rn(0.25f, __fadd_rn(__fsub_rn(__fsub_rn(L(1, 1), L(-1, 1)), L(1, -1)), L(-1, -1)));
+    const float det = __fsub_rn(__fmul_rn(dxx, dyy), __fmul_rn(dxy, dxy));
+    const float ox = -__fdiv_rn(__fsub_rn(__fmul_rn(dyy, dx), __fmul_rn(dxy, dy)), det);
+    const float oy = -__fdiv_rn(__fsub_rn(__fmul_rn(dxx, dy), __fmul_rn(dxy, dx)), det);
+    // positive comparisons: a NaN anywhere fails them and the integers stand
+    const bool step = dxx < 0.0f && det > 0.0f && fabsf(ox) <= 2.0f && fabsf(oy) <= 2.0f;
+    coords[2 * map] = step ? __fadd_rn((float)px, ox) : (float)px;
+    coords[2 * map + 1] = step ? __fadd_rn((float)py, oy) : (float)py;
+    if (refined) refined[map] = step ? 1 : 0;
+}
+
+extern "C" int pk_unbiased_decode(const float* heatmaps, const float* taps_host, int ksize, int32_t* index, float* maxval, float* coords,
+                                  uint8_t* refined, int BK, int H, int W, void* stream) {
+    PK_REQUIRE(heatmaps && coords && taps_host, "pk_unbiased_decode: null pointer (heatmaps, coords and taps_host are required)");
+    PK_REQUIRE(ksize >= 3 && ksize <= UB_MAX_K && (ksize & 1) == 1, "pk_unbiased_decode: ksize %d (odd, 3 to %d)", ksize, UB_MAX_K);
+    PK_REQUIRE(BK > 0 && H > 0 && W > 0 && (int64_t)H * W < 0x7fffffff, "pk_unbiased_decode: bad shape BK=%d H=%d W=%d", BK, H, W);
+    UbTaps taps = {};
+    for (int t = 0; t < ksize; ++t) taps.v[t] = taps_host[t];
+    hipLaunchKernelGGL(k_unbiased_decode, dim3(BK), dim3(256), 0, (hipStream_t)stream, heatmaps, taps, ksize, index, maxval, coords, refined,
+                       H, W);
+    return pk_launch_status("pk_unbiased_decode");
+}
+
 // ================================================================================================ D1
 __device__ __forceinline__ float bilinear_border(const float* __restrict__ p, int H, int W, float x, float y) {
     x = fminf(fmaxf(x, 0.f), (float)(W - 1));

@@ -88,6 +88,42 @@ def argmax_decode(heatmaps, mode=0):
     return idx, mv, co
 
 
+_TAPS_CACHE = {}
+
+
+def unbiased_taps(kernel=11):
+    """The `kernel` float32 taps of the unbiased decode's smoothing, cached per size: a Gaussian derived from the size alone by OpenCV's
+    rule, sigma = 0.3 ((k - 1) 0.5 - 1) + 0.8, g_i = exp(-(i - c)^2 / (2 sigma^2)) in float64, divided by its float64 sum, then rounded to
+    float32.  (OpenCV's fixed tables for k <= 7 are deliberately not imitated: one formula for every size.)"""
+    k = int(kernel)
+    if k != kernel or k < 3 or k > 31 or k % 2 == 0:
+        raise _lib.PoseKernelError(f"unbiased_decode: kernel {kernel!r} (an odd size from 3 to 31)")
+    if k not in _TAPS_CACHE:
+        sigma = 0.3 * ((k - 1) * 0.5 - 1) + 0.8
+        g = np.exp(-(np.arange(k, dtype=np.float64) - (k - 1) // 2) ** 2 / (2 * sigma ** 2))
+        taps = (g / g.sum()).astype(np.float32)
+        taps.setflags(write=False)
+        _TAPS_CACHE[k] = taps
+    return _TAPS_CACHE[k]
+
+
+def unbiased_decode(heatmaps, kernel=11):
+    """Unbiased (DARK) decode, pk_unbiased_decode: (B,K,H,W) -> index (B,K) int32, maxval (B,K), coords (B,K,2), refined (B,K) uint8 (1 where
+    the Newton step on the log of the smoothed map was taken, 0 where coords are the integer argmax).  The taps ride in the launch: no
+    host synchronisation, no host-to-device copy, no allocation but the outputs."""
+    taps = unbiased_taps(kernel)
+    hm = _chk(heatmaps, name="heatmaps")
+    if hm.dim() != 4:
+        raise _lib.PoseKernelError(f"unbiased_decode: heatmaps {tuple(hm.shape)} are not (B, K, H, W)")
+    B, K, H, W = hm.shape
+    idx = torch.empty(B, K, dtype=I32, device=hm.device)
+    mv = torch.empty(B, K, dtype=F32, device=hm.device)
+    co = torch.empty(B, K, 2, dtype=F32, device=hm.device)
+    ref = torch.empty(B, K, dtype=torch.uint8, device=hm.device)
+    _call_if(B * K, "pk_unbiased_decode", hm, taps.ctypes.data, taps.size, idx, mv, co, ref, B * K, H, W, stream_ptr())
+    return idx, mv, co, ref
+
+
 def softargmax_refine_decode(heatmaps, offsets, alpha_param, fusion_weight_param, radius=2):
     hm = _chk(heatmaps, name="heatmaps")
     B, K, H, W = hm.shape

@@ -122,8 +122,11 @@ class PoseEstimator(nn.Module):
         return output
 
     @torch.no_grad()
-    def inference(self, x, flip: bool = True, flip_pairs: Optional[list] = None):
-        """-> keypoints (B,K,2) heat-px, scores (B,K); flip test as pose_estimator.py:275-329 (offsets of the un-flipped pass)."""
+    def inference(self, x, flip: bool = True, flip_pairs: Optional[list] = None, decode: Optional[str] = None, modulate_kernel: int = 11):
+        """-> keypoints (B,K,2) heat-px, scores (B,K); flip test as pose_estimator.py:275-329 (offsets of the un-flipped pass).
+        `decode` (heatmap heads): None or 'shift' = the quarter-pixel shift of `decode_heatmaps`; 'unbiased' = the distribution-aware
+        decode with a `modulate_kernel`-tap smoothing (pk_unbiased_decode).  The fusion head refuses 'unbiased'."""
+        unbiased = self._decode_choice(decode)
         if flip and flip_pairs is not None and not self.training and os.environ.get("POSE_FLIP_BATCHED", "1") != "0":
             # eval mode: every sample is independent of the rest of its batch (running BatchNorm statistics, per-sample windows), so the two
             # passes of the flip test are ONE forward over [x ; flip(x)] -- same numbers per sample, half the launches, twice the rows per launch
@@ -141,15 +144,18 @@ class PoseEstimator(nn.Module):
             o = dict(out)
             o["heatmaps"] = hm
             return self.head.decode(o, apply_offset=True)
-        return self.decode_heatmaps(hm)
+        return self.decode_heatmaps(hm, unbiased=unbiased, kernel=modulate_kernel)
 
     @torch.no_grad()
-    def inference_multiscale(self, xs, scales, flip: bool = True, flip_pairs: Optional[list] = None):
+    def inference_multiscale(self, xs, scales, flip: bool = True, flip_pairs: Optional[list] = None, decode: Optional[str] = None,
+                             modulate_kernel: int = 11):
         """Multi-scale (flip) test -> keypoints (B,K,2) heat-px of the scale-1.0 crop, scores (B,K).  `xs`: (S,B,3,H,W) or a list of S
         (B,3,H,W) crops of the same centres with box scale `scales[s] * scale`, in the order of `scales` (exactly one entry 1.0).  Eval mode
         only: the S * F passes are ONE forward over S*F*B samples, pass s*F + f in rows [(s*F + f) B, (s*F + f + 1) B), f = 1 the mirrored
         crop -- batch statistics would couple them.  The heatmaps are merged in the base crop's frame (pk_multiscale_merge); the fusion
-        head's offsets, variances and fusion_weight are those of the scale-1.0 un-flipped pass (the reference's flip-test rule, extended)."""
+        head's offsets, variances and fusion_weight are those of the scale-1.0 un-flipped pass (the reference's flip-test rule, extended).
+        `decode` / `modulate_kernel`: as in `inference`, applied to the merged heatmaps."""
+        unbiased = self._decode_choice(decode)
         if self.training:
             raise RuntimeError("inference_multiscale needs eval mode: in training mode batch statistics would couple the passes")
         sc = check_test_scales(scales)
@@ -169,7 +175,7 @@ class PoseEstimator(nn.Module):
             o = dict(out)
             o["heatmaps"] = hm
             return self.head.decode(o, apply_offset=True)
-        return self.decode_heatmaps(hm)
+        return self.decode_heatmaps(hm, unbiased=unbiased, kernel=modulate_kernel)
 
     def _flip_partner(self, flip_pairs, device):
         """int32 (K,) left/right partner of every keypoint, cached on the device (no host->device copy per call: inference is
@@ -183,9 +189,23 @@ class PoseEstimator(nn.Module):
             cache[key] = partner.to(device)
         return cache[key]
 
+    def _decode_choice(self, decode) -> bool:
+        """`decode` of `inference` / `inference_multiscale` -> whether the heatmaps go through the unbiased decode."""
+        if decode not in (None, "shift", "unbiased"):
+            raise ValueError(f"decode must be None, 'shift' or 'unbiased', got {decode!r}")
+        if decode == "unbiased" and self.head_type == "fusion":
+            raise ValueError("decode='unbiased' is for heatmap heads: the fusion head decodes through its own learned soft-argmax, "
+                             "refinement and offset blend (HeatmapRegressionHead.decode)")
+        return decode == "unbiased"
+
     @staticmethod
     @torch.no_grad()
-    def decode_heatmaps(heatmaps, shift: bool = True):
+    def decode_heatmaps(heatmaps, shift: bool = True, unbiased: bool = False, kernel: int = 11):
+        """-> coords (B,K,2) heat-px, maxvals (B,K).  Integer argmax plus a quarter-pixel shift toward the larger neighbour (`shift`), or,
+        with `unbiased`, plus one Newton step on the log of the map smoothed with a `kernel`-tap Gaussian (pk_unbiased_decode)."""
+        if unbiased:
+            _, mv, co, _ = hipops.unbiased_decode(heatmaps.float(), kernel)
+            return co, mv
         _, mv, co = hipops.argmax_decode(heatmaps.float(), 1 if shift else 0)
         return co, mv
 

@@ -17,6 +17,13 @@ def get_max_preds_with_subpixel(batch_heatmaps):
     return co, mv.unsqueeze(-1)
 
 
+def get_max_preds_unbiased(batch_heatmaps, kernel=11):
+    """Argmax + the unbiased (distribution-aware) step: one Newton step on the logarithm of the map smoothed with a `kernel`-tap Gaussian
+    (pk_unbiased_decode; where the step is not taken the integer argmax stands).  -> preds (B,K,2), maxvals (B,K,1) like its siblings."""
+    _, mv, co, _ = hipops.unbiased_decode(batch_heatmaps.float(), kernel)
+    return co, mv.unsqueeze(-1)
+
+
 def fused_decode(heatmaps, regression_coords=None, centers=None, scales=None, alpha=0.5):
     """postprocess.py:78-135 incl. its quirks (hard-coded 256 image size; the alpha blend is overwritten by the
     confidence-adaptive blend, so `alpha` has no effect — kept for signature parity)."""

@@ -8,6 +8,8 @@ as restated in oracle/warp.py), the model's flip-test inference and decode follo
 mapping of inference.py:142-175 is one kernel (pk_affine_coords).  `predict_batch` really batches (the reference loops over predict).
 With `scales` (`--scales 0.8 1.0 1.2`, or the config's `test_scales`) every person is cropped once per scale -- all crops of a call in ONE
 cropper launch, each image uploaded once -- and the passes are merged on the device (PoseEstimator.inference_multiscale).
+With `decode='unbiased'` (`--decode unbiased [--modulate_kernel K]`, or the config's `decode`) a heatmap-head model's maps are decoded by the
+unbiased, distribution-aware step (pk_unbiased_decode) instead of the quarter-pixel shift -- single images, `--scales` and `--sequence` alike.
 `predict_sequence` / `--sequence` take the frames of a video (a directory of images) for one person and keep the trajectory on the device
 for the movement analysis of utils/metrics.py (temporal smoothing, `movement_report`, `movement_heatmap`).
 Visualisation is on the device too: `visualize` / `visualize_batch` draw through utils/visualization.py (pk_draw_shapes,
@@ -26,7 +28,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from infantposeestimation_gaussianbias_amd.configs import get_config  # noqa: E402
-from infantposeestimation_gaussianbias_amd.configs.config import check_test_scales  # noqa: E402
+from infantposeestimation_gaussianbias_amd.configs.config import check_decode, check_test_scales  # noqa: E402
 from infantposeestimation_gaussianbias_amd.datasets.transforms import DeviceCropper, get_affine_matrix, multiscale_matrices  # noqa: E402
 from infantposeestimation_gaussianbias_amd.models import build_model  # noqa: E402
 from infantposeestimation_gaussianbias_amd.utils.metrics import movement_heatmap, movement_report  # noqa: E402
@@ -36,9 +38,11 @@ from infantposeestimation_gaussianbias_amd.utils.visualization import COCO_SKELE
 
 class PoseInference:
     scales = None       # multi-scale test off unless __init__ is given (or finds in the config) a scale list
+    decode = None       # the model's default decode unless __init__ is given (or finds in the config) another
+    modulate_kernel = 11
 
     def __init__(self, checkpoint: Optional[str] = None, device: str = 'cuda', flip_test: bool = True, config: Optional[str] = None,
-                 scales=None):
+                 scales=None, decode: Optional[str] = None, modulate_kernel: Optional[int] = None):
         if not torch.cuda.is_available():
             raise RuntimeError("PoseInference needs an MI355X: the hot path has no CPU implementation")
         self.device = torch.device(device)
@@ -46,6 +50,8 @@ class PoseInference:
         self.cfg = get_config(config) if config else get_config()
         scales = scales if scales is not None else getattr(self.cfg, "test_scales", None)
         self.scales = check_test_scales(scales) if scales is not None else None          # None: one crop per person
+        self.decode, self.modulate_kernel = check_decode(decode if decode is not None else getattr(self.cfg, "decode", None),
+                                                         modulate_kernel if modulate_kernel is not None else getattr(self.cfg, "modulate_kernel", 11))
         self.model = build_model(self.cfg).to(self.device).eval()
         if checkpoint and os.path.isfile(checkpoint):
             ckpt = torch.load(checkpoint, map_location="cpu", weights_only=True)
@@ -83,8 +89,9 @@ class PoseInference:
         """Crops (P,3,H,W), or (S,P,3,H,W) with scales -> heat-px keypoints and scores of the model's (multi-scale) flip-test inference."""
         pairs = self.flip_pairs if self.flip_test else None
         if self.scales is not None:
-            return self.model.inference_multiscale(x, self.scales, flip=self.flip_test, flip_pairs=pairs)
-        return self.model.inference(x, flip=self.flip_test, flip_pairs=pairs)
+            return self.model.inference_multiscale(x, self.scales, flip=self.flip_test, flip_pairs=pairs, decode=self.decode,
+                                                   modulate_kernel=self.modulate_kernel)
+        return self.model.inference(x, flip=self.flip_test, flip_pairs=pairs, decode=self.decode, modulate_kernel=self.modulate_kernel)
 
     def preprocess(self, img: np.ndarray, bbox: Optional[np.ndarray] = None):
         x, c, s = self.preprocess_batch([img], [bbox])
@@ -269,7 +276,8 @@ def main_sequence(args, pose):
 
 def main(args):
     from PIL import Image
-    pose = PoseInference(checkpoint=args.checkpoint, device=args.device, flip_test=not args.no_flip, config=args.config, scales=args.scales)
+    pose = PoseInference(checkpoint=args.checkpoint, device=args.device, flip_test=not args.no_flip, config=args.config, scales=args.scales,
+                         decode=args.decode, modulate_kernel=args.modulate_kernel)
     if getattr(args, "sequence", False):
         return main_sequence(args, pose)
     rgb = np.asarray(Image.open(args.input).convert("RGB"))
@@ -295,7 +303,7 @@ def main(args):
         print(f'Result saved to: {args.output}')
 
 
-if __name__ == '__main__':
+def build_parser():
     p = argparse.ArgumentParser(description='Pose Estimation Inference')
     p.add_argument('--checkpoint', type=str, default=None)
     p.add_argument('--input', type=str, required=True)
@@ -320,4 +328,14 @@ if __name__ == '__main__':
                                                              'frames before the analysis (default: the config\'s TEMPORAL block)')
     p.add_argument('--fps', type=float, default=None, help='--sequence: frame rate, turns the speeds into pixels per second')
     p.add_argument('--report', type=str, default=None, help='--sequence: write the movement report (JSON) here instead of printing it')
-    main(p.parse_args())
+    p.add_argument('--decode', type=str, choices=('shift', 'unbiased'), default=None,
+                   help='heatmap decode of a heatmap-head model, for single images, --scales and --sequence alike: shift = argmax + '
+                        'quarter-pixel shift, unbiased = argmax + one Newton step on the log of the smoothed map (default: the config\'s '
+                        'decode; none: shift)')
+    p.add_argument('--modulate_kernel', type=int, default=None, metavar='K',
+                   help='--decode unbiased: taps of the Gaussian smoothing, odd, 3 to 31 (default: the config\'s modulate_kernel, 11)')
+    return p
+
+
+if __name__ == '__main__':
+    main(build_parser().parse_args())

@@ -118,6 +118,7 @@ def main(args):
                 val_cfg = copy.copy(cfg)
                 val_cfg.test_scales = None           # this monitor stays single-scale and un-flipped; validate.py runs the multi-scale test
                 val_loader = build_dataloader(val_cfg, is_train=False)
+            # the heatmap decode follows the config (cfg.decode / cfg.modulate_kernel); a config that names none keeps the quarter-pixel shift
             metrics, _ = validate(model, val_loader, torch.device("cuda", local), cfg, logger, flip_test=False)
             model.train()
             is_best = metrics["AP"] > best_ap

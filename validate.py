@@ -4,7 +4,8 @@ multi-scale test: predictions from `PoseEstimator.inference_multiscale` over the
 --pck [THR ...] for PCK next to AP: the share of keypoints within THR x the longer box side of their ground truth, counted on the device;
 plus --bbox_file / --det_score_thr / --oks_nms THR / --soft_nms / --in_vis_thr for the detector-box protocol: crops from a person-detection
 file instead of the ground-truth boxes, every pose rescored as box score x mean confident keypoint score, duplicate poses removed per image
-by OKS-NMS on the device, then AP).
+by OKS-NMS on the device, then AP; plus --decode {shift,unbiased} / --modulate_kernel K for the heatmap decode of the heatmap-head models:
+the quarter-pixel shift (the default) or the unbiased, distribution-aware step on the log of the smoothed map).
 
 Flip-test inference + decode run entirely on the GPU (`PoseEstimator.inference`: two forwards, one flip-merge kernel, one
 decode kernel); the heat-px -> image transform of validate.py:100-117 is one kernel (`heatmap_to_image_coords`) instead of a
@@ -22,7 +23,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from infantposeestimation_gaussianbias_amd.configs import get_config  # noqa: E402
-from infantposeestimation_gaussianbias_amd.configs.config import check_test_scales  # noqa: E402
+from infantposeestimation_gaussianbias_amd.configs.config import check_decode, check_test_scales  # noqa: E402
 from infantposeestimation_gaussianbias_amd.datasets import build_dataloader  # noqa: E402
 from infantposeestimation_gaussianbias_amd.models import build_model  # noqa: E402
 from infantposeestimation_gaussianbias_amd.utils import AverageMeter  # noqa: E402
@@ -30,7 +31,8 @@ from infantposeestimation_gaussianbias_amd.utils.postprocess import heatmap_to_i
 
 
 @torch.no_grad()
-def validate(model, loader, device, cfg, logger, flip_test=True, scales=None, pck_thresholds=None, evaluator=None):
+def validate(model, loader, device, cfg, logger, flip_test=True, scales=None, pck_thresholds=None, evaluator=None, decode=None,
+             modulate_kernel=None):
     """train.py:231-325 == validate.py:39-140 of the reference: loss + decode + image-space transform + COCOEvaluator.update per batch,
     then AP.  Decode, flip merge, the heat-px -> image transform and the evaluator's record arrays are kernels (no B x K Python loops, one
     device->host copy per batch).  AP / AR come from COCOKeypointEval when the loader's dataset has an annotation file; otherwise AP is the
@@ -42,10 +44,14 @@ def validate(model, loader, device, cfg, logger, flip_test=True, scales=None, pc
     Detector boxes: a batch whose meta carries `box_score` (a COCO loader built with `cfg.bbox_file`) has no ground truth -- the loss forward
     is skipped (`metrics["loss"]` is NaN), PCK raises, and the box scores go to the evaluator, which with `cfg.oks_nms_thr` rescores the poses
     and removes duplicates per image by OKS-NMS on the device before AP (`COCOEvaluator.kept`).  `evaluator`: the COCOEvaluator to fill
-    (default: one built from the loader's annotation file and the config's NMS settings)."""
+    (default: one built from the loader's annotation file and the config's NMS settings).
+    `decode` / `modulate_kernel`: the heatmap decode ('shift', 'unbiased') and its smoothing size; None takes the config's `decode` /
+    `modulate_kernel`, and a config that names none keeps the quarter-pixel shift."""
     from infantposeestimation_gaussianbias_amd.utils import COCOEvaluator
     from infantposeestimation_gaussianbias_amd.utils import metrics as metrics_mod
     pck = metrics_mod.PCKAccumulator(cfg.data.num_keypoints, pck_thresholds) if pck_thresholds is not None else None
+    decode, modulate_kernel = check_decode(decode if decode is not None else getattr(cfg, "decode", None),
+                                           modulate_kernel if modulate_kernel is not None else getattr(cfg, "modulate_kernel", 11))
     model.eval()
     loss_meter = AverageMeter("Loss", ":.4f")
     ann = getattr(getattr(loader, "dataset", None), "ann_file", None)
@@ -58,13 +64,14 @@ def validate(model, loader, device, cfg, logger, flip_test=True, scales=None, pc
     for i, batch in enumerate(loader):
         imgs = batch["img"].to(device)
         if scales is None:
-            kp, sc = model.inference(imgs, flip=bool(flip_test and flip_pairs), flip_pairs=flip_pairs)
+            kp, sc = model.inference(imgs, flip=bool(flip_test and flip_pairs), flip_pairs=flip_pairs, decode=decode, modulate_kernel=modulate_kernel)
         else:
             if batch.get("img_scales") is None or batch["img_scales"].shape[0] != len(scales):
                 raise RuntimeError(f"validate: multi-scale test over {tuple(scales)} needs a loader that yields batch['img_scales'] with one "
                                    "slice per scale (the COCO loader built from a config with the same test_scales); this loader does not, "
                                    "and there is no single-scale fallback")
-            kp, sc = model.inference_multiscale(batch["img_scales"].to(device), scales, flip=bool(flip_test and flip_pairs), flip_pairs=flip_pairs)
+            kp, sc = model.inference_multiscale(batch["img_scales"].to(device), scales, flip=bool(flip_test and flip_pairs), flip_pairs=flip_pairs,
+                                                decode=decode, modulate_kernel=modulate_kernel)
         meta = batch["meta"]
         box_scores = meta.get("box_score")
         if box_scores is not None:          # detector boxes: the batch's keypoints and targets are placeholders, not ground truth
@@ -121,6 +128,10 @@ def main(args):
     if args.scales:
         cfg.test_scales = check_test_scales(args.scales)
     apply_detector_box_args(cfg, args)
+    if getattr(args, "decode", None) is not None or getattr(args, "modulate_kernel", None) is not None:
+        cfg.decode, cfg.modulate_kernel = check_decode(args.decode if args.decode is not None else cfg.decode,
+                                                       args.modulate_kernel if args.modulate_kernel is not None else cfg.modulate_kernel,
+                                                       ("--decode", "--modulate_kernel"))
     device = torch.device("cuda")
     loader = build_dataloader(cfg, is_train=False)
     model = build_model(cfg).to(device)
@@ -177,6 +188,11 @@ def build_parser():
     p.add_argument("--soft_nms", action="store_true", help="soft OKS-NMS (scores decay by exp(-oks^2 / THR)) instead of hard suppression")
     p.add_argument("--in_vis_thr", type=float, default=None,
                    help="keypoint score above which a joint counts in the rescoring and in the NMS's OKS (default: the config's, 0.2)")
+    p.add_argument("--decode", type=str, choices=("shift", "unbiased"), default=None,
+                   help="heatmap decode of a heatmap-head model: 'shift' = argmax + quarter-pixel shift, 'unbiased' = argmax + one Newton step on "
+                        "the log of the smoothed map (default: the config's decode; none: shift)")
+    p.add_argument("--modulate_kernel", type=int, default=None, metavar="K",
+                   help="--decode unbiased: taps of the Gaussian smoothing, odd, 3 to 31 (default: the config's modulate_kernel, 11)")
     return p
 
 
