@@ -23,8 +23,6 @@
 // the kernel, no float atomics).
 #include "pk_common.h"
 
-#define AT_N 49
-#define AT_WS 7
 // row pitch (bf16) of the [64][32*DK] row-major LDS tiles: 32*DK + 8 (40 for head_dim <= 32, 72 for head_dim <= 64)
 #define RPITCH(DK) (32 * (DK) + 8)
 
@@ -48,7 +46,6 @@ __device__ __forceinline__ bf16x8 tok_frag(const uint16_t* tile, int pitch, int 
     const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a0 + 16 * pitch));
     return (bf16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 }
-__device__ __forceinline__ int rel_a(int t) { return 13 * (t / AT_WS) + t % AT_WS; }   // rel_index(i,j) = rel_a(i) - rel_a(j) + 84
 __device__ __forceinline__ bf16x8 pack_frag(const f32x4 a, const f32x4 b, float m) {
     const u32x4 v = {pack_bf16x2(a[0] * m, a[1] * m), pack_bf16x2(a[2] * m, a[3] * m), pack_bf16x2(b[0] * m, b[1] * m),
                      pack_bf16x2(b[2] * m, b[3] * m)};
@@ -204,7 +201,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DK == 1
     uint16_t *sQ = sTiles, *sK = sTiles + 64 * RP, *sdO = sTiles + 2 * 64 * RP;
     const int lane0 = threadIdx.x;
     const int h = blockIdx.x % heads;
-    // Score arithmetic (as in pk_block.hip's k_attn_bwd): the bias table is kept in units of log2 and the score / dP accumulators START
+    // Score arithmetic (as in pk_block_attn.hip's k_attn_bwd): the bias table is kept in units of log2 and the score / dP accumulators START
     // at -lse / scale and -delta in pass 2 (pass 1 subtracts: no registers to spare), so P = exp2(fma(acc, scale * log2 e, bias')) and
     // dS = P * acc'; the clamps of the bias index exist only on the edge tiles (tiles 0..2 hold only real tokens).
     constexpr float LOG2E = 1.44269504088896340736f;

@@ -56,6 +56,23 @@ static inline int pk_launch_status(const char* what) {
     return PK_OK;
 }
 
+// Workgroups of a grid-stride launch: what the problem needs, at least one, at most `cap`
+static inline int capped_grid(int need, int cap) { return need < cap ? (need < 1 ? 1 : need) : cap; }
+
+// Compute units of the current device (256 where no device answers)
+static inline int pk_cu_count() {
+    static int cus = 0;
+    int dev = 0, n = 0;
+    if (!cus) cus = (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) ? 256 : n;
+    return cus;
+}
+
+// ---- the 7x7 attention window (pk_attn.hip, pk_block_attn.hip)
+#define AT_N 49
+#define AT_WS 7
+// rel_index(i, j) = rel_a(i) - rel_a(j) + 84: the bias-table row of query i and key j, without a division in the inner loop
+__device__ __forceinline__ int rel_a(int t) { return 13 * (t / AT_WS) + t % AT_WS; }
+
 // ---- wave / block reductions (64-lane shuffles) ----------------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -1221,13 +1221,6 @@ __global__ void __launch_bounds__(256, 2) k_conv3h(IgemmArgs p, int pieces_per_w
             }
     }
 }
-static inline int pk_cu_count() {
-    static int cus = 0;
-    int dev = 0, n = 0;
-    if (!cus) cus = (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) ? 256 : n;
-    return cus;
-}
-
 // ================================================================================================ routing
 // Which kernel, tile and grid a call gets is decided in igemm_route and nowhere else: igemm_launch only maps the route to the instantiation,
 // and pk_conv_stats_rows sizes the statistics buffer from the same route.  Every threshold sits here with the measurement behind it.

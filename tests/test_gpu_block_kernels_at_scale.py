@@ -1,4 +1,4 @@
-"""GPU tests (`-m gpu`) of the transformer-block kernels (csrc/pk_block.hip, csrc/pk_attn.hip, the weight-gradient and slab-reduction
+"""GPU tests (`-m gpu`) of the transformer-block kernels (csrc/pk_block_mlp.hip, csrc/pk_block_attn.hip, csrc/pk_attn.hip, the weight-gradient and slab-reduction
 kernels of csrc/pk_wgrad.hip) at the window and row counts training runs.
 
 The block kernels are persistent: the release build caps every grid at a compile-time constant and each wave (or workgroup) walks
