@@ -57,7 +57,7 @@ static inline int pk_launch_status(const char* what) {
 }
 
 // Workgroups of a grid-stride launch: what the problem needs, at least one, at most `cap`
-static inline int capped_grid(int need, int cap) { return need < cap ? (need < 1 ? 1 : need) : cap; }
+static inline int capped_grid(int64_t need, int cap) { return need < cap ? (need < 1 ? 1 : (int)need) : cap; }
 
 // Compute units of the current device (256 where no device answers)
 static inline int pk_cu_count() {

@@ -1,131 +1,9 @@
-// Target generation (T1, T2) and heatmap decoders (D1-D4). All HBM-bound, fp32, one workgroup per map.
-#include <stdarg.h>
-
+// Heatmap decoders (D1-D4): everything that turns heatmaps into coordinates or merges heatmaps.  HBM-bound, fp32.
 #include "pk_common.h"
 
-// ------------------------------------------------------------------------------------------------ errors
-static thread_local char g_err[512] = "";
-void pk_set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-extern "C" const char* pk_last_error_string(void) { return g_err; }
-extern "C" int pk_version(void) { return 100; }
-// Profiling aid: an empty launch whose workgroup count is `id`, so a rocprofv3 kernel trace can be cut into program sections
-// (scripts/trace_sections.py); never launched unless POSE_MARKERS=1.
-__global__ void k_marker() {}
-extern "C" int pk_marker(int id, void* stream) {
-    PK_REQUIRE(id > 0 && id < 65536, "pk_marker: id out of range");
-    hipLaunchKernelGGL(k_marker, dim3(id), dim3(64), 0, (hipStream_t)stream);
-    return pk_launch_status("pk_marker");
-}
-
-// ================================================================================================ T1
-// One 256-thread workgroup per (b,k) map. Each thread redoes the (cheap) float64 index arithmetic, then the
-// block streams the whole map out with 16-byte stores: every element is written exactly once (zeros or LUT).
-__global__ void __launch_bounds__(256) k_gaussian_target(const float* __restrict__ kp, const float* __restrict__ vis,
-                                                         const float* __restrict__ lut, float* __restrict__ target,
-                                                         float* __restrict__ weight, int Hh, int Wh, double sx, double sy,
-                                                         double reach, int pn, int pc) {
-    const int map = blockIdx.x;
-    float w = vis[map];
-    bool draw = !(w < 0.5f);
-    int x_lo = 0, y_lo = 0, x_hi = 0, y_hi = 0;
-    if (draw) {
-        // float32 coordinate / float64 stride, then C truncation toward zero (Python int()).
-        const double mx = (double)kp[2 * map] / sx, my = (double)kp[2 * map + 1] / sy;
-        const double lim = 1.0e9;
-        x_lo = (int)fmin(fmax(mx - reach, -lim), lim);
-        y_lo = (int)fmin(fmax(my - reach, -lim), lim);
-        x_hi = (int)fmin(fmax(mx + reach + 1.0, -lim), lim);
-        y_hi = (int)fmin(fmax(my + reach + 1.0, -lim), lim);
-        if (x_lo >= Wh || y_lo >= Hh || x_hi < 0 || y_hi < 0) {
-            draw = false;
-            w = 0.f;
-        }
-    }
-    if (threadIdx.x == 0) weight[map] = w;
-    const int c0 = max(0, x_lo), c1 = min(x_hi, Wh), r0 = max(0, y_lo), r1 = min(y_hi, Hh);
-    float* out = target + (size_t)map * Hh * Wh;
-    const int n = Hh * Wh;
-    if ((Wh & 3) == 0) {
-        for (int i = threadIdx.x * 4; i < n; i += blockDim.x * 4) {
-            const int y = i / Wh, x = i - y * Wh;
-            float v[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int xx = x + j;
-                float val = 0.f;
-                if (draw && y >= r0 && y < r1 && xx >= c0 && xx < c1) {
-                    const int dx = xx - x_lo - pc, dy = y - y_lo - pc;
-                    val = lut[dx * dx + dy * dy];
-                }
-                v[j] = val;
-            }
-            *reinterpret_cast<float4*>(out + i) = make_float4(v[0], v[1], v[2], v[3]);
-        }
-    } else {
-        for (int i = threadIdx.x; i < n; i += blockDim.x) {
-            const int y = i / Wh, x = i - y * Wh;
-            float val = 0.f;
-            if (draw && y >= r0 && y < r1 && x >= c0 && x < c1) {
-                const int dx = x - x_lo - pc, dy = y - y_lo - pc;
-                val = lut[dx * dx + dy * dy];
-            }
-            out[i] = val;
-        }
-    }
-}
-
-extern "C" int pk_gaussian_target(const float* keypoints, const float* visible, const float* lut, int lut_len, float* target,
-                                  float* weight, int B, int K, int Hh, int Wh, double stride_x, double stride_y,
-                                  double reach, int patch_n, int patch_c, void* stream) {
-    PK_REQUIRE(keypoints && visible && lut && target && weight, "pk_gaussian_target: null pointer");
-    PK_REQUIRE(B > 0 && K > 0 && Hh > 0 && Wh > 0, "pk_gaussian_target: bad shape B=%d K=%d H=%d W=%d", B, K, Hh, Wh);
-    PK_REQUIRE(stride_x > 0 && stride_y > 0 && reach > 0, "pk_gaussian_target: bad stride/reach");
-    const int far = patch_c > patch_n - 1 - patch_c ? patch_c : patch_n - 1 - patch_c;
-    PK_REQUIRE(patch_n > 0 && patch_c >= 0 && patch_c < patch_n && lut_len >= 2 * far * far + 1,
-               "pk_gaussian_target: LUT of %d entries too short for a %d-wide patch centred at %d", lut_len, patch_n, patch_c);
-    PK_REQUIRE((int)(2 * reach + 1) <= patch_n, "pk_gaussian_target: reach %.2f exceeds the %d-wide patch", reach, patch_n);
-    PK_REQUIRE(((uintptr_t)target & 15) == 0, "pk_gaussian_target: target must be 16-byte aligned");
-    hipLaunchKernelGGL(k_gaussian_target, dim3(B * K), dim3(256), 0, (hipStream_t)stream, keypoints, visible, lut, target, weight,
-                       Hh, Wh, stride_x, stride_y, reach, patch_n, patch_c);
-    return pk_launch_status("pk_gaussian_target");
-}
-
-// ================================================================================================ T2
-__global__ void __launch_bounds__(256) k_dense_target(const float* __restrict__ kp, const float* __restrict__ vis,
-                                                      float* __restrict__ hm, float* __restrict__ wts, int Hh, int Wh,
-                                                      float scx, float scy, float sigma) {
-    const int map = blockIdx.x;
-    const float cx = kp[2 * map] * scx, cy = kp[2 * map + 1] * scy;   // float32 multiply, as `scaled_keypoints[:,0] *= scale_w`
-    const bool on = vis[map] > 0.f && cx >= 0.f && cx < (float)Wh && cy >= 0.f && cy < (float)Hh;
-    if (threadIdx.x == 0) wts[map] = on ? 1.f : 0.f;
-    const float denom = 2.f * sigma * sigma;
-    float* out = hm + (size_t)map * Hh * Wh;
-    for (int i = threadIdx.x; i < Hh * Wh; i += blockDim.x) {
-        const int y = i / Wh, x = i - y * Wh;
-        float v = 0.f;
-        if (on) {
-            const float dx = (float)x - cx, dy = (float)y - cy;
-            v = fmaxf(0.f, expf(-(dx * dx + dy * dy) / denom));
-        }
-        out[i] = v;
-    }
-}
-
-extern "C" int pk_dense_target(const float* keypoints, const float* visible, float* heatmaps, float* weights, int B, int K,
-                               int Hh, int Wh, float scale_x, float scale_y, float sigma, void* stream) {
-    PK_REQUIRE(keypoints && visible && heatmaps && weights, "pk_dense_target: null pointer");
-    PK_REQUIRE(B > 0 && K > 0 && Hh > 0 && Wh > 0 && sigma > 0.f, "pk_dense_target: bad shape");
-    hipLaunchKernelGGL(k_dense_target, dim3(B * K), dim3(256), 0, (hipStream_t)stream, keypoints, visible, heatmaps, weights, Hh,
-                       Wh, scale_x, scale_y, sigma);
-    return pk_launch_status("pk_dense_target");
-}
-
 // ================================================================================================ argmax (D2, D3)
+// One workgroup per map with 32-bit indices inside it: what the entries that take an argmax over a map, or gather from one, ask of a shape
+static inline bool map_shape_ok(int maps, int H, int W) { return maps > 0 && H > 0 && W > 0 && (int64_t)H * W < 0x7fffffff; }
 struct ArgMax {
     float v;
     int i;
@@ -210,7 +88,7 @@ __global__ void __launch_bounds__(256) k_argmax_decode(const float* __restrict__
 extern "C" int pk_argmax_decode(const float* heatmaps, int32_t* index, float* maxval, float* coords, int BK, int H, int W,
                                 int mode, void* stream) {
     PK_REQUIRE(heatmaps, "pk_argmax_decode: null heatmaps");
-    PK_REQUIRE(BK > 0 && H > 0 && W > 0 && (int64_t)H * W < 0x7fffffff, "pk_argmax_decode: bad shape");
+    PK_REQUIRE(map_shape_ok(BK, H, W), "pk_argmax_decode: bad shape");
     PK_REQUIRE(mode >= 0 && mode <= 2, "pk_argmax_decode: mode %d", mode);
     hipLaunchKernelGGL(k_argmax_decode, dim3(BK), dim3(256), 0, (hipStream_t)stream, heatmaps, index, maxval, coords, H, W, mode);
     return pk_launch_status("pk_argmax_decode");
@@ -322,7 +200,7 @@ extern "C" int pk_unbiased_decode(const float* heatmaps, const float* taps_host,
                                   uint8_t* refined, int BK, int H, int W, void* stream) {
     PK_REQUIRE(heatmaps && coords && taps_host, "pk_unbiased_decode: null pointer (heatmaps, coords and taps_host are required)");
     PK_REQUIRE(ksize >= 3 && ksize <= UB_MAX_K && (ksize & 1) == 1, "pk_unbiased_decode: ksize %d (odd, 3 to %d)", ksize, UB_MAX_K);
-    PK_REQUIRE(BK > 0 && H > 0 && W > 0 && (int64_t)H * W < 0x7fffffff, "pk_unbiased_decode: bad shape BK=%d H=%d W=%d", BK, H, W);
+    PK_REQUIRE(map_shape_ok(BK, H, W), "pk_unbiased_decode: bad shape BK=%d H=%d W=%d", BK, H, W);
     UbTaps taps = {};
     for (int t = 0; t < ksize; ++t) taps.v[t] = taps_host[t];
     hipLaunchKernelGGL(k_unbiased_decode, dim3(BK), dim3(256), 0, (hipStream_t)stream, heatmaps, taps, ksize, index, maxval, coords, refined,
@@ -470,45 +348,6 @@ extern "C" int pk_softargmax_bwd(const float* heatmaps, const float* coords, con
     hipLaunchKernelGGL(k_softargmax_bwd, dim3(BK), dim3(256), 0, (hipStream_t)stream, heatmaps, coords, scores, grad_coords, grad_scores,
                        d_heatmaps, H, W);
     return pk_launch_status("pk_softargmax_bwd");
-}
-
-// window_partition / window_reverse (hrformer.py:67-114) as row moves through the window row map (window-order token -> pixel row, -1 = one
-// of the zero tokens appended at the bottom / right): gather = partition (pad tokens read as zeros), scatter = reverse (pad tokens dropped).
-// Rows are `row_dwords` 4-byte words of any element type.
-__global__ void k_rows_by_map(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, const int* __restrict__ map, long n_rows,
-                              int row_dwords, int scatter) {
-    const long total = n_rows * row_dwords;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const long r = i / row_dwords;
-        const int c = (int)(i - r * row_dwords), pr = map[r];
-        if (scatter) {
-            if (pr >= 0) dst[(long)pr * row_dwords + c] = src[i];
-        } else {
-            dst[i] = pr >= 0 ? src[(long)pr * row_dwords + c] : 0u;
-        }
-    }
-}
-extern "C" int pk_rows_by_map(const void* src, void* dst, const int* rowmap, int64_t n_rows, int row_bytes, int scatter, void* stream) {
-    PK_REQUIRE(src && dst && rowmap && n_rows > 0 && row_bytes > 0 && row_bytes % 4 == 0, "pk_rows_by_map: bad argument (rows of whole dwords)");
-    const long total = n_rows * (row_bytes / 4);
-    const int nb = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
-    hipLaunchKernelGGL(k_rows_by_map, dim3(nb), dim3(256), 0, (hipStream_t)stream, (const uint32_t*)src, (uint32_t*)dst, rowmap, (long)n_rows,
-                       row_bytes / 4, scatter);
-    return pk_launch_status("pk_rows_by_map");
-}
-
-// drop_path (hrformer.py:15-24): out = (x / keep) * mask[sample], mask in {0, 1}; fp32 elements, `per_sample` of them per sample.
-__global__ void k_drop_path(const float* __restrict__ x, const float* __restrict__ mask, float* __restrict__ out, long total, long per_sample,
-                            float keep) {
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x)
-        out[i] = (x[i] / keep) * mask[i / per_sample];
-}
-extern "C" int pk_drop_path_f32(const float* x, const float* mask, float* out, int64_t batch, int64_t per_sample, float keep_prob, void* stream) {
-    PK_REQUIRE(x && mask && out && batch > 0 && per_sample > 0 && keep_prob > 0.f, "pk_drop_path_f32: bad argument");
-    const long total = batch * per_sample;
-    const int nb = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
-    hipLaunchKernelGGL(k_drop_path, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, mask, out, total, (long)per_sample, keep_prob);
-    return pk_launch_status("pk_drop_path_f32");
 }
 
 // ================================================================================================ D3 tail
@@ -659,8 +498,7 @@ extern "C" int pk_multiscale_merge(const float* stack, const int32_t* partner, c
     PK_REQUIRE(F == 1 || F == 2, "pk_multiscale_merge: F = %d passes per scale (1: plain, 2: plain + mirrored)", F);
     PK_REQUIRE(F == 1 || partner, "pk_multiscale_merge: the mirrored passes need the partner table");
     PK_REQUIRE(S >= 1 && S <= 8, "pk_multiscale_merge: %d scales (1 to 8)", S);
-    PK_REQUIRE(B > 0 && K > 0 && H > 0 && W > 0 && (int64_t)B * K < 0x7fffffff && (int64_t)H * W < 0x7fffffff,
-               "pk_multiscale_merge: bad shape B=%d K=%d H=%d W=%d", B, K, H, W);
+    PK_REQUIRE(K > 0 && (int64_t)B * K < 0x7fffffff && map_shape_ok(B, H, W), "pk_multiscale_merge: bad shape B=%d K=%d H=%d W=%d", B, K, H, W);
     MsInv inv = {};
     for (int s = 0; s < S; ++s) {
         PK_REQUIRE(inv_scales_host[s] > 0.f && inv_scales_host[s] < INFINITY, "pk_multiscale_merge: inverse scale %d is %g (finite, > 0)", s,
@@ -679,284 +517,4 @@ extern "C" int pk_multiscale_merge(const float* stack, const int32_t* partner, c
         default: multiscale_merge_launch<8>(stack, partner, out, inv, F, B, K, H, W, st); break;
     }
     return pk_launch_status("pk_multiscale_merge");
-}
-
-// ================================================================================================ video post-processing
-// utils/postprocess.py::temporal_smoothing (:187-223): per joint coordinate, edge-padded trajectory convolved (np.convolve,
-// i.e. with the kernel FLIPPED) with `w` weights, evaluated in float64 and stored as float32 like the reference's
-// numpy-float64 -> float32 tensor assignment.  coords/out: (T, C) with C = 2K; weights: w doubles; w must be odd (the
-// reference's output has T+1 entries for even windows and its assignment fails).
-__global__ void __launch_bounds__(256) k_temporal_smooth(const float* __restrict__ coords, float* __restrict__ out,
-                                                         const double* __restrict__ weights, int T, int C, int w) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= T * C) return;
-    const int t = i / C, c = i - t * C, half = w / 2;
-    double acc = 0.0;
-    for (int j = 0; j < w; ++j) {
-        int src = t + (w - 1 - j) - half;                 // padded index t + w-1-j, minus the left pad
-        src = src < 0 ? 0 : (src >= T ? T - 1 : src);     // mode='edge'
-        acc += (double)coords[(size_t)src * C + c] * weights[j];
-    }
-    out[i] = (float)acc;
-}
-extern "C" int pk_temporal_smooth(const float* coords, float* out, const double* weights, int T, int C, int window, void* stream) {
-    PK_REQUIRE(coords && out && weights && T > 0 && C > 0 && window > 0, "pk_temporal_smooth: bad argument");
-    PK_SUPPORTED((window & 1) == 1, "pk_temporal_smooth: window %d must be odd (the reference fails on even windows)", window);
-    hipLaunchKernelGGL(k_temporal_smooth, dim3((T * C + 255) / 256), dim3(256), 0, (hipStream_t)stream, coords, out, weights, T, C, window);
-    return pk_launch_status("pk_temporal_smooth");
-}
-
-// utils/postprocess.py::nms_pose (:241-267): greedy, order-dependent suppression inside one sample -> one thread per sample
-// walks the joints exactly like the reference's Python loop (distances on the ORIGINAL coordinates, `nearby` includes the
-// joint itself and already-suppressed joints, first maximum wins ties).
-__global__ void __launch_bounds__(64) k_nms_pose(const float* __restrict__ preds, const float* __restrict__ maxvals,
-                                                 float* __restrict__ out, uint8_t* __restrict__ keep, int B, int K, float thr) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    const float* p = preds + (size_t)b * K * 2;
-    const float* v = maxvals + (size_t)b * K;
-    uint8_t* kp = keep + (size_t)b * K;
-    for (int k = 0; k < K; ++k) kp[k] = 1;
-    for (int k = 0; k < K; ++k) {
-        if (!kp[k]) continue;
-        int count = 0, best = -1;
-        float bv = -INFINITY;
-        for (int j = 0; j < K; ++j) {
-            const float dx = p[2 * j] - p[2 * k], dy = p[2 * j + 1] - p[2 * k + 1];
-            if (sqrtf(dx * dx + dy * dy) < thr) {
-                ++count;
-                if (v[j] > bv) { bv = v[j]; best = j; }
-            }
-        }
-        if (count > 1)
-            for (int j = 0; j < K; ++j) {
-                const float dx = p[2 * j] - p[2 * k], dy = p[2 * j + 1] - p[2 * k + 1];
-                if (sqrtf(dx * dx + dy * dy) < thr && j != best) kp[j] = 0;
-            }
-    }
-    for (int k = 0; k < K; ++k) {
-        const float m = kp[k] ? 1.f : 0.f;
-        out[((size_t)b * K + k) * 2] = p[2 * k] * m;
-        out[((size_t)b * K + k) * 2 + 1] = p[2 * k + 1] * m;
-    }
-}
-extern "C" int pk_nms_pose(const float* preds, const float* maxvals, float* out, uint8_t* keep, int B, int K, float distance_threshold,
-                           void* stream) {
-    PK_REQUIRE(preds && maxvals && out && keep && B > 0 && K > 0, "pk_nms_pose: bad argument");
-    hipLaunchKernelGGL(k_nms_pose, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, preds, maxvals, out, keep, B, K, distance_threshold);
-    return pk_launch_status("pk_nms_pose");
-}
-
-// ================================================================================================ f1: evaluator records
-// COCOEvaluator.update (utils/metrics.py:84-106): per instance a (K,3) array [x, y, score] and the instance score = mean of the
-// strictly positive keypoint scores (0 when there is none).  One 64-lane wave per instance; the mean is an fp32 sum in keypoint
-// order divided by the count (numpy's float32 mean sums pairwise: equal to 1e-6 relative, stated in the test).
-__global__ void __launch_bounds__(64) k_pose_records(const float* __restrict__ kp, const float* __restrict__ sc, float* __restrict__ rec,
-                                                    float* __restrict__ inst, int K) {
-    const int b = blockIdx.x, t = threadIdx.x;
-    for (int k = t; k < K; k += 64) {
-        rec[((size_t)b * K + k) * 3 + 0] = kp[((size_t)b * K + k) * 2 + 0];
-        rec[((size_t)b * K + k) * 3 + 1] = kp[((size_t)b * K + k) * 2 + 1];
-        rec[((size_t)b * K + k) * 3 + 2] = sc[(size_t)b * K + k];
-    }
-    if (t == 0) {
-        float s = 0.f;
-        int n = 0;
-        for (int k = 0; k < K; ++k) {
-            const float v = sc[(size_t)b * K + k];
-            if (v > 0.f) {
-                s += v;
-                ++n;
-            }
-        }
-        inst[b] = n > 0 ? s / (float)n : 0.f;
-    }
-}
-extern "C" int pk_pose_records(const float* keypoints, const float* scores, float* records, float* instance_score, int B, int K,
-                               void* stream) {
-    PK_REQUIRE(keypoints && scores && records && instance_score && B > 0 && K > 0, "pk_pose_records: bad argument");
-    hipLaunchKernelGGL(k_pose_records, dim3(B), dim3(64), 0, (hipStream_t)stream, keypoints, scores, records, instance_score, K);
-    return pk_launch_status("pk_pose_records");
-}
-
-// ================================================================================================ f2: input pipeline
-// TopdownAffine(+rotation) image crop + RandomFlip + ToTensor/normalise of the reference's data pipeline (datasets/transforms.py:42-47,
-// 128-131, 212-217; datasets/coco_dataset.py:156-163; inference.py:93-110) for a whole batch in ONE launch, straight from the decoded
-// uint8 images to the network input.  The warp follows OpenCV's 8-bit `warpAffine(INTER_LINEAR, BORDER_CONSTANT 0)` integer algorithm as
-// restated in oracle/warp.py (coordinates in 10-bit fixed point rounded half-to-even, 5 bits of sub-pixel position, weights that sum to
-// 2^15, (sum + 2^14) >> 15) -- integer work, bit-exact against that restatement; cv2 itself is not in the image (parity unpinned vs cv2).
-// Normalisation is the reference's fp32 expression ((v / 255) - mean) / std with correctly rounded divisions.
-struct CropDesc {
-    int64_t src_offset;      // byte offset of this sample's (H, W, 3) uint8 image inside the source buffer
-    int32_t H, W;
-    int32_t flip;            // mirror the source columns (RandomFlip flips the image before the warp)
-    int32_t bgr;             // source is BGR (cv2.imread / inference.py:83): swap to RGB
-    double minv[6];          // inverse (destination -> source) affine matrix, float64 as OpenCV holds it
-};
-// The warp of one destination pixel -> its three RGB bytes.  Shared by every crop kernel, so the fused and the jittered path cannot drift.
-__device__ __forceinline__ void crop_warp_u8(const unsigned char* __restrict__ src, const CropDesc& d, int x, int y, int u[3]) {
-    auto sat = [](double v) { return (long long)max(-2147483648.0, min(2147483647.0, rint(v))); };
-    const long long adelta = sat(__dmul_rn(__dmul_rn(d.minv[0], (double)x), 1024.0)), bdelta = sat(__dmul_rn(__dmul_rn(d.minv[3], (double)x), 1024.0));
-    const long long X0 = sat(__dmul_rn(__dadd_rn(__dmul_rn(d.minv[1], (double)y), d.minv[2]), 1024.0)) + 16;
-    const long long Y0 = sat(__dmul_rn(__dadd_rn(__dmul_rn(d.minv[4], (double)y), d.minv[5]), 1024.0)) + 16;
-    const long long X = (X0 + adelta) >> 5, Y = (Y0 + bdelta) >> 5;
-    const long long sx = max(-32768LL, min(32767LL, X >> 5)), sy = max(-32768LL, min(32767LL, Y >> 5));
-    const int a = (int)(X & 31), b = (int)(Y & 31);
-    const int w4[4] = {(32 - a) * (32 - b) * 32, a * (32 - b) * 32, (32 - a) * b * 32, a * b * 32};
-    int acc[3] = {0, 0, 0};
-    const unsigned char* img = src + d.src_offset;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const long long xx = sx + (t & 1), yy = sy + (t >> 1);
-        if (xx < 0 || xx >= d.W || yy < 0 || yy >= d.H) continue;
-        const long long xs = d.flip ? d.W - 1 - xx : xx;
-        const unsigned char* p = img + (yy * d.W + xs) * 3;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) acc[c] += w4[t] * (int)p[d.bgr ? 2 - c : c];
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) u[c] = min(255, max(0, (acc[c] + (1 << 14)) >> 15));
-}
-// ((u / 255) - mean) / std of one pixel's bytes, written as fp32 NCHW and / or bf16 NHWC-8.
-__device__ __forceinline__ void crop_normalize_store(const int u[3], int sample, int pix, size_t plane, float* __restrict__ out_nchw,
-                                                     uint16_t* __restrict__ out_nhwc8, const float mean[3], const float sd[3]) {
-    float v[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) v[c] = __fdiv_rn(__fsub_rn(__fdiv_rn((float)u[c], 255.0f), mean[c]), sd[c]);
-    if (out_nchw) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) out_nchw[((size_t)sample * 3 + c) * plane + pix] = v[c];
-    }
-    if (out_nhwc8) {
-        uint4 o;
-        o.x = pack_bf16x2(v[0], v[1]);
-        o.y = pack_bf16x2(v[2], 0.f);
-        o.z = o.w = 0u;
-        *reinterpret_cast<uint4*>(out_nhwc8 + ((size_t)sample * plane + pix) * 8) = o;
-    }
-}
-__global__ void __launch_bounds__(256) k_affine_crop(const unsigned char* __restrict__ src, const CropDesc* __restrict__ desc, int out_w, int out_h,
-                                                     float* __restrict__ out_nchw, uint16_t* __restrict__ out_nhwc8, float m0, float m1, float m2,
-                                                     float s0, float s1, float s2) {
-    const CropDesc d = desc[blockIdx.y];
-    const int pix = blockIdx.x * 256 + threadIdx.x;
-    if (pix >= out_w * out_h) return;
-    const int y = pix / out_w, x = pix - y * out_w;
-    int u[3];
-    crop_warp_u8(src, d, x, y, u);
-    const float mean[3] = {m0, m1, m2}, sd[3] = {s0, s1, s2};
-    crop_normalize_store(u, blockIdx.y, pix, (size_t)out_w * out_h, out_nchw, out_nhwc8, mean, sd);
-}
-extern "C" int pk_affine_crop_normalize(const void* src_u8, const void* desc_table, int n_samples, int out_w, int out_h, float* out_nchw_f32,
-                                        void* out_nhwc8_bf16, const float* mean3, const float* std3, void* stream) {
-    PK_REQUIRE(src_u8 && desc_table && n_samples > 0 && out_w > 0 && out_h > 0 && (out_nchw_f32 || out_nhwc8_bf16) && mean3 && std3,
-               "pk_affine_crop_normalize: bad argument");
-    PK_REQUIRE(!out_nhwc8_bf16 || (((uintptr_t)out_nhwc8_bf16) & 15) == 0, "pk_affine_crop_normalize: 16-byte alignment of the NHWC output");
-    hipLaunchKernelGGL(k_affine_crop, dim3((out_w * out_h + 255) / 256, n_samples), dim3(256), 0, (hipStream_t)stream, (const unsigned char*)src_u8,
-                       (const CropDesc*)desc_table, out_w, out_h, out_nchw_f32, (uint16_t*)out_nhwc8_bf16, mean3[0], mean3[1], mean3[2], std3[0],
-                       std3[1], std3[2]);
-    return pk_launch_status("pk_affine_crop_normalize");
-}
-
-// ------------------------------------------------------------------------------------------------ f2 + colour jitter
-// The reference's CustomColorJitter (data/examples.py:367-401) between the 8-bit warp and the normalisation, per sample:
-//   x = u8 / 255 * b;   x = (x - m) * c + m, m = mean of x over the crop;   x = g + (x - g) * s, g = mean of the pixel's 3 channels;
-//   u8' = trunc(clip(x, 0, 1) * 255)
-// m needs the whole crop, so this is two launches: k_crop_u8 warps to a packed-byte scratch and leaves one exact integer sum per
-// workgroup; k_jitter_normalize re-adds the sample's partial sums itself (integers: every order gives the same S; no atomics, no
-// last-arriver), applies the arithmetic below with one rounding per operation, and normalises like k_affine_crop.  A sample whose
-// `enable` is 0 skips the arithmetic altogether: factors (1, 1, 1) are NOT the identity (u8 / 255 * 255 truncates).
-struct JitterDesc {
-    int32_t enable;
-    float b, c, s;           // brightness, contrast, saturation factors
-};
-// Sum of `v` over a 256-thread block (exact, unsigned), returned to every thread.
-__device__ __forceinline__ uint32_t block_sum_u32(uint32_t v, uint32_t* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
-__global__ void __launch_bounds__(256) k_crop_u8(const unsigned char* __restrict__ src, const CropDesc* __restrict__ desc, int out_w, int out_h,
-                                                 uint32_t* __restrict__ crop, uint32_t* __restrict__ partial) {
-    __shared__ uint32_t red[4];
-    const CropDesc d = desc[blockIdx.y];
-    const int pix = blockIdx.x * 256 + threadIdx.x, plane = out_w * out_h;
-    uint32_t sum = 0;                    // a thread past the end of the crop adds nothing
-    if (pix < plane) {
-        const int y = pix / out_w, x = pix - y * out_w;
-        int u[3];
-        crop_warp_u8(src, d, x, y, u);
-        crop[(size_t)blockIdx.y * plane + pix] = (uint32_t)u[0] | ((uint32_t)u[1] << 8) | ((uint32_t)u[2] << 16);
-        sum = (uint32_t)(u[0] + u[1] + u[2]);
-    }
-    sum = block_sum_u32(sum, red);
-    if (threadIdx.x == 0) partial[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = sum;
-}
-__global__ void __launch_bounds__(256) k_jitter_normalize(const uint32_t* __restrict__ crop, const uint32_t* __restrict__ partial,
-                                                          const JitterDesc* __restrict__ jit, int out_w, int out_h, float* __restrict__ out_nchw,
-                                                          uint16_t* __restrict__ out_nhwc8, float m0, float m1, float m2, float s0, float s1,
-                                                          float s2) {
-    __shared__ uint32_t red[4];
-    const JitterDesc j = jit[blockIdx.y];
-    const int pix = blockIdx.x * 256 + threadIdx.x, plane = out_w * out_h;
-    float m = 0.f;
-    if (j.enable) {                      // uniform over the block
-        uint32_t S = 0;                  // < 2^32: the entry point rejects crops with 765 h w >= 2^32
-        for (int i = threadIdx.x; i < (int)gridDim.x; i += 256) S += partial[(size_t)blockIdx.y * gridDim.x + i];
-        S = block_sum_u32(S, red);
-        m = (float)__dmul_rn(__ddiv_rn((double)S, __dmul_rn(255.0, (double)plane * 3.0)), (double)j.b);
-    }
-    if (pix >= plane) return;
-    const uint32_t p = crop[(size_t)blockIdx.y * plane + pix];
-    int u[3] = {(int)(p & 255u), (int)((p >> 8) & 255u), (int)(p >> 16)};
-    if (j.enable) {
-        float x[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            x[c] = __fmul_rn(__fdiv_rn((float)u[c], 255.0f), j.b);
-            x[c] = __fadd_rn(__fmul_rn(__fsub_rn(x[c], m), j.c), m);
-        }
-        const float g = __fdiv_rn(__fadd_rn(__fadd_rn(x[0], x[1]), x[2]), 3.0f);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float v = fminf(fmaxf(__fadd_rn(g, __fmul_rn(__fsub_rn(x[c], g), j.s)), 0.f), 1.f);
-            u[c] = (int)__fmul_rn(v, 255.0f);
-        }
-    }
-    const float mean[3] = {m0, m1, m2}, sd[3] = {s0, s1, s2};
-    crop_normalize_store(u, blockIdx.y, pix, (size_t)plane, out_nchw, out_nhwc8, mean, sd);
-}
-// Workspace: n * w * h packed crop pixels, then n * ceil(w h / 256) partial sums, all uint32.  PK_ERR_INVALID (and an error string) if the
-// shape is refused.
-static inline int64_t jitter_partial_offset(int n_samples, int out_w, int out_h) { return (int64_t)n_samples * out_w * out_h; }   // in uint32 words
-extern "C" int pk_affine_crop_jitter_ws_bytes(int n_samples, int out_w, int out_h) {
-    PK_REQUIRE(n_samples > 0 && out_w > 0 && out_h > 0 && (int64_t)out_w * out_h * 765 < (int64_t)1 << 32,
-               "pk_affine_crop_jitter_ws_bytes: bad shape n=%d w=%d h=%d (the byte sum of a crop must stay below 2^32)", n_samples, out_w, out_h);
-    const int64_t nblk = ((int64_t)out_w * out_h + 255) / 256, bytes = 4 * (jitter_partial_offset(n_samples, out_w, out_h) + n_samples * nblk);
-    PK_REQUIRE(bytes <= 0x7fffffff, "pk_affine_crop_jitter_ws_bytes: %lld-byte workspace for n=%d w=%d h=%d exceeds 2^31", (long long)bytes,
-               n_samples, out_w, out_h);
-    return (int)bytes;
-}
-extern "C" int pk_affine_crop_jitter_normalize(const void* src_u8, const void* desc_table, const void* jitter_table, int n_samples, int out_w,
-                                               int out_h, float* out_nchw_f32, void* out_nhwc8_bf16, const float* mean3, const float* std3,
-                                               void* ws, int64_t ws_bytes, void* stream) {
-    PK_REQUIRE(src_u8 && desc_table && jitter_table && ws && (out_nchw_f32 || out_nhwc8_bf16) && mean3 && std3,
-               "pk_affine_crop_jitter_normalize: null pointer");
-    const int need = pk_affine_crop_jitter_ws_bytes(n_samples, out_w, out_h);       // the shape checks live there
-    if (need < 0) return need;
-    PK_REQUIRE(ws_bytes >= need, "pk_affine_crop_jitter_normalize: workspace of %lld bytes, %d needed", (long long)ws_bytes, need);
-    PK_REQUIRE((((uintptr_t)ws) & 3) == 0 && (!out_nhwc8_bf16 || (((uintptr_t)out_nhwc8_bf16) & 15) == 0),
-               "pk_affine_crop_jitter_normalize: alignment (workspace 4 bytes, NHWC output 16 bytes)");
-    const int nblk = (out_w * out_h + 255) / 256;
-    uint32_t* crop = (uint32_t*)ws;
-    uint32_t* partial = crop + jitter_partial_offset(n_samples, out_w, out_h);
-    hipLaunchKernelGGL(k_crop_u8, dim3(nblk, n_samples), dim3(256), 0, (hipStream_t)stream, (const unsigned char*)src_u8, (const CropDesc*)desc_table,
-                       out_w, out_h, crop, partial);
-    hipLaunchKernelGGL(k_jitter_normalize, dim3(nblk, n_samples), dim3(256), 0, (hipStream_t)stream, (const uint32_t*)crop, (const uint32_t*)partial,
-                       (const JitterDesc*)jitter_table, out_w, out_h, out_nchw_f32, (uint16_t*)out_nhwc8_bf16, mean3[0], mean3[1], mean3[2],
-                       std3[0], std3[1], std3[2]);
-    return pk_launch_status("pk_affine_crop_jitter_normalize");
 }

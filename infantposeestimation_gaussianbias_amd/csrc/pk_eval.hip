@@ -1,4 +1,5 @@
-// f1: COCO keypoint evaluation (COCOeval with iouType='keypoints', one category, maxDets = [20]) on the device.
+// f1: COCO keypoint evaluation (COCOeval with iouType='keypoints', one category, maxDets = [20]) on the device, and the evaluator's
+// per-instance records (pk_pose_records, at the end).
 //
 // The host (utils/coco_eval.py) parses the annotation file, groups ground truths and detections by image (images in ascending id
 // order, file / record order inside an image) and computes every CSR offset; the four kernels here do the data-parallel part:
@@ -336,4 +337,36 @@ extern "C" int pk_coco_kpt_eval(const double* oks, const int64_t* oks_off, const
     hipLaunchKernelGGL(k_coco_accum, dim3(A * T), dim3(PK_COCO_ACC_THREADS), 0, st, dt_match, dt_ignore, npig, order, rec_thrs, ws_pr, ws_tp,
                        precision, recall, n_img, n_cap, A, T, R);
     return pk_launch_status("pk_coco_kpt_eval (accumulate)");
+}
+
+// ================================================================================================ f1: evaluator records
+// COCOEvaluator.update (utils/metrics.py:84-106): per instance a (K,3) array [x, y, score] and the instance score = mean of the
+// strictly positive keypoint scores (0 when there is none).  One 64-lane wave per instance; the mean is an fp32 sum in keypoint
+// order divided by the count (numpy's float32 mean sums pairwise: equal to 1e-6 relative, stated in the test).
+__global__ void __launch_bounds__(64) k_pose_records(const float* __restrict__ kp, const float* __restrict__ sc, float* __restrict__ rec,
+                                                    float* __restrict__ inst, int K) {
+    const int b = blockIdx.x, t = threadIdx.x;
+    for (int k = t; k < K; k += 64) {
+        rec[((size_t)b * K + k) * 3 + 0] = kp[((size_t)b * K + k) * 2 + 0];
+        rec[((size_t)b * K + k) * 3 + 1] = kp[((size_t)b * K + k) * 2 + 1];
+        rec[((size_t)b * K + k) * 3 + 2] = sc[(size_t)b * K + k];
+    }
+    if (t == 0) {
+        float s = 0.f;
+        int n = 0;
+        for (int k = 0; k < K; ++k) {
+            const float v = sc[(size_t)b * K + k];
+            if (v > 0.f) {
+                s += v;
+                ++n;
+            }
+        }
+        inst[b] = n > 0 ? s / (float)n : 0.f;
+    }
+}
+extern "C" int pk_pose_records(const float* keypoints, const float* scores, float* records, float* instance_score, int B, int K,
+                               void* stream) {
+    PK_REQUIRE(keypoints && scores && records && instance_score && B > 0 && K > 0, "pk_pose_records: bad argument");
+    hipLaunchKernelGGL(k_pose_records, dim3(B), dim3(64), 0, (hipStream_t)stream, keypoints, scores, records, instance_score, K);
+    return pk_launch_status("pk_pose_records");
 }

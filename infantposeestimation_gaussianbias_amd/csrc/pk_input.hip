@@ -1,0 +1,189 @@
+// The input pipeline: affine crop, colour jitter and normalisation, from the decoded uint8 images to the network input.
+#include "pk_common.h"
+
+// ================================================================================================ f2: input pipeline
+// TopdownAffine(+rotation) image crop + RandomFlip + ToTensor/normalise of the reference's data pipeline (datasets/transforms.py:42-47,
+// 128-131, 212-217; datasets/coco_dataset.py:156-163; inference.py:93-110) for a whole batch in ONE launch, straight from the decoded
+// uint8 images to the network input.  The warp follows OpenCV's 8-bit `warpAffine(INTER_LINEAR, BORDER_CONSTANT 0)` integer algorithm as
+// restated in oracle/warp.py (coordinates in 10-bit fixed point rounded half-to-even, 5 bits of sub-pixel position, weights that sum to
+// 2^15, (sum + 2^14) >> 15) -- integer work, bit-exact against that restatement; cv2 itself is not in the image (parity unpinned vs cv2).
+// Normalisation is the reference's fp32 expression ((v / 255) - mean) / std with correctly rounded divisions.
+struct CropDesc {
+    int64_t src_offset;      // byte offset of this sample's (H, W, 3) uint8 image inside the source buffer
+    int32_t H, W;
+    int32_t flip;            // mirror the source columns (RandomFlip flips the image before the warp)
+    int32_t bgr;             // source is BGR (cv2.imread / inference.py:83): swap to RGB
+    double minv[6];          // inverse (destination -> source) affine matrix, float64 as OpenCV holds it
+};
+// The warp of one destination pixel -> its three RGB bytes.  Shared by every crop kernel, so the fused and the jittered path cannot drift.
+__device__ __forceinline__ void crop_warp_u8(const unsigned char* __restrict__ src, const CropDesc& d, int x, int y, int u[3]) {
+    auto sat = [](double v) { return (long long)max(-2147483648.0, min(2147483647.0, rint(v))); };
+    const long long adelta = sat(__dmul_rn(__dmul_rn(d.minv[0], (double)x), 1024.0)), bdelta = sat(__dmul_rn(__dmul_rn(d.minv[3], (double)x), 1024.0));
+    const long long X0 = sat(__dmul_rn(__dadd_rn(__dmul_rn(d.minv[1], (double)y), d.minv[2]), 1024.0)) + 16;
+    const long long Y0 = sat(__dmul_rn(__dadd_rn(__dmul_rn(d.minv[4], (double)y), d.minv[5]), 1024.0)) + 16;
+    const long long X = (X0 + adelta) >> 5, Y = (Y0 + bdelta) >> 5;
+    const long long sx = max(-32768LL, min(32767LL, X >> 5)), sy = max(-32768LL, min(32767LL, Y >> 5));
+    const int a = (int)(X & 31), b = (int)(Y & 31);
+    const int w4[4] = {(32 - a) * (32 - b) * 32, a * (32 - b) * 32, (32 - a) * b * 32, a * b * 32};
+    int acc[3] = {0, 0, 0};
+    const unsigned char* img = src + d.src_offset;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const long long xx = sx + (t & 1), yy = sy + (t >> 1);
+        if (xx < 0 || xx >= d.W || yy < 0 || yy >= d.H) continue;
+        const long long xs = d.flip ? d.W - 1 - xx : xx;
+        const unsigned char* p = img + (yy * d.W + xs) * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) acc[c] += w4[t] * (int)p[d.bgr ? 2 - c : c];
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) u[c] = min(255, max(0, (acc[c] + (1 << 14)) >> 15));
+}
+// ((u / 255) - mean) / std of one pixel's bytes, written as fp32 NCHW and / or bf16 NHWC-8.
+__device__ __forceinline__ void crop_normalize_store(const int u[3], int sample, int pix, size_t plane, float* __restrict__ out_nchw,
+                                                     uint16_t* __restrict__ out_nhwc8, const float mean[3], const float sd[3]) {
+    float v[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = __fdiv_rn(__fsub_rn(__fdiv_rn((float)u[c], 255.0f), mean[c]), sd[c]);
+    if (out_nchw) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) out_nchw[((size_t)sample * 3 + c) * plane + pix] = v[c];
+    }
+    if (out_nhwc8) {
+        uint4 o;
+        o.x = pack_bf16x2(v[0], v[1]);
+        o.y = pack_bf16x2(v[2], 0.f);
+        o.z = o.w = 0u;
+        *reinterpret_cast<uint4*>(out_nhwc8 + ((size_t)sample * plane + pix) * 8) = o;
+    }
+}
+__global__ void __launch_bounds__(256) k_affine_crop(const unsigned char* __restrict__ src, const CropDesc* __restrict__ desc, int out_w, int out_h,
+                                                     float* __restrict__ out_nchw, uint16_t* __restrict__ out_nhwc8, float m0, float m1, float m2,
+                                                     float s0, float s1, float s2) {
+    const CropDesc d = desc[blockIdx.y];
+    const int pix = blockIdx.x * 256 + threadIdx.x;
+    if (pix >= out_w * out_h) return;
+    const int y = pix / out_w, x = pix - y * out_w;
+    int u[3];
+    crop_warp_u8(src, d, x, y, u);
+    const float mean[3] = {m0, m1, m2}, sd[3] = {s0, s1, s2};
+    crop_normalize_store(u, blockIdx.y, pix, (size_t)out_w * out_h, out_nchw, out_nhwc8, mean, sd);
+}
+// What both crop entries ask of their pointers: a source, a table, at least one output, mean and std; a 16-byte aligned NHWC output if any
+static inline bool crop_pointers_ok(const void* src_u8, const void* desc, const void* out_nchw, const void* out_nhwc8, const float* mean3, const float* std3) {
+    return src_u8 && desc && (out_nchw || out_nhwc8) && mean3 && std3;
+}
+static inline bool nhwc8_aligned(const void* out_nhwc8) { return !out_nhwc8 || (((uintptr_t)out_nhwc8) & 15) == 0; }
+extern "C" int pk_affine_crop_normalize(const void* src_u8, const void* desc_table, int n_samples, int out_w, int out_h, float* out_nchw_f32,
+                                        void* out_nhwc8_bf16, const float* mean3, const float* std3, void* stream) {
+    PK_REQUIRE(crop_pointers_ok(src_u8, desc_table, out_nchw_f32, out_nhwc8_bf16, mean3, std3) && n_samples > 0 && out_w > 0 && out_h > 0,
+               "pk_affine_crop_normalize: bad argument");
+    PK_REQUIRE(nhwc8_aligned(out_nhwc8_bf16), "pk_affine_crop_normalize: 16-byte alignment of the NHWC output");
+    hipLaunchKernelGGL(k_affine_crop, dim3((out_w * out_h + 255) / 256, n_samples), dim3(256), 0, (hipStream_t)stream, (const unsigned char*)src_u8,
+                       (const CropDesc*)desc_table, out_w, out_h, out_nchw_f32, (uint16_t*)out_nhwc8_bf16, mean3[0], mean3[1], mean3[2], std3[0],
+                       std3[1], std3[2]);
+    return pk_launch_status("pk_affine_crop_normalize");
+}
+
+// ------------------------------------------------------------------------------------------------ f2 + colour jitter
+// The reference's CustomColorJitter (data/examples.py:367-401) between the 8-bit warp and the normalisation, per sample:
+//   x = u8 / 255 * b;   x = (x - m) * c + m, m = mean of x over the crop;   x = g + (x - g) * s, g = mean of the pixel's 3 channels;
+//   u8' = trunc(clip(x, 0, 1) * 255)
+// m needs the whole crop, so this is two launches: k_crop_u8 warps to a packed-byte scratch and leaves one exact integer sum per
+// workgroup; k_jitter_normalize re-adds the sample's partial sums itself (integers: every order gives the same S; no atomics, no
+// last-arriver), applies the arithmetic below with one rounding per operation, and normalises like k_affine_crop.  A sample whose
+// `enable` is 0 skips the arithmetic altogether: factors (1, 1, 1) are NOT the identity (u8 / 255 * 255 truncates).
+struct JitterDesc {
+    int32_t enable;
+    float b, c, s;           // brightness, contrast, saturation factors
+};
+// Sum of `v` over a 256-thread block (exact, unsigned), returned to every thread.
+__device__ __forceinline__ uint32_t block_sum_u32(uint32_t v, uint32_t* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return red[0] + red[1] + red[2] + red[3];
+}
+__global__ void __launch_bounds__(256) k_crop_u8(const unsigned char* __restrict__ src, const CropDesc* __restrict__ desc, int out_w, int out_h,
+                                                 uint32_t* __restrict__ crop, uint32_t* __restrict__ partial) {
+    __shared__ uint32_t red[4];
+    const CropDesc d = desc[blockIdx.y];
+    const int pix = blockIdx.x * 256 + threadIdx.x, plane = out_w * out_h;
+    uint32_t sum = 0;                    // a thread past the end of the crop adds nothing
+    if (pix < plane) {
+        const int y = pix / out_w, x = pix - y * out_w;
+        int u[3];
+        crop_warp_u8(src, d, x, y, u);
+        crop[(size_t)blockIdx.y * plane + pix] = (uint32_t)u[0] | ((uint32_t)u[1] << 8) | ((uint32_t)u[2] << 16);
+        sum = (uint32_t)(u[0] + u[1] + u[2]);
+    }
+    sum = block_sum_u32(sum, red);
+    if (threadIdx.x == 0) partial[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = sum;
+}
+__global__ void __launch_bounds__(256) k_jitter_normalize(const uint32_t* __restrict__ crop, const uint32_t* __restrict__ partial,
+                                                          const JitterDesc* __restrict__ jit, int out_w, int out_h, float* __restrict__ out_nchw,
+                                                          uint16_t* __restrict__ out_nhwc8, float m0, float m1, float m2, float s0, float s1,
+                                                          float s2) {
+    __shared__ uint32_t red[4];
+    const JitterDesc j = jit[blockIdx.y];
+    const int pix = blockIdx.x * 256 + threadIdx.x, plane = out_w * out_h;
+    float m = 0.f;
+    if (j.enable) {                      // uniform over the block
+        uint32_t S = 0;                  // < 2^32: the entry point rejects crops with 765 h w >= 2^32
+        for (int i = threadIdx.x; i < (int)gridDim.x; i += 256) S += partial[(size_t)blockIdx.y * gridDim.x + i];
+        S = block_sum_u32(S, red);
+        m = (float)__dmul_rn(__ddiv_rn((double)S, __dmul_rn(255.0, (double)plane * 3.0)), (double)j.b);
+    }
+    if (pix >= plane) return;
+    const uint32_t p = crop[(size_t)blockIdx.y * plane + pix];
+    int u[3] = {(int)(p & 255u), (int)((p >> 8) & 255u), (int)(p >> 16)};
+    if (j.enable) {
+        float x[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            x[c] = __fmul_rn(__fdiv_rn((float)u[c], 255.0f), j.b);
+            x[c] = __fadd_rn(__fmul_rn(__fsub_rn(x[c], m), j.c), m);
+        }
+        const float g = __fdiv_rn(__fadd_rn(__fadd_rn(x[0], x[1]), x[2]), 3.0f);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float v = fminf(fmaxf(__fadd_rn(g, __fmul_rn(__fsub_rn(x[c], g), j.s)), 0.f), 1.f);
+            u[c] = (int)__fmul_rn(v, 255.0f);
+        }
+    }
+    const float mean[3] = {m0, m1, m2}, sd[3] = {s0, s1, s2};
+    crop_normalize_store(u, blockIdx.y, pix, (size_t)plane, out_nchw, out_nhwc8, mean, sd);
+}
+// Workspace: n * w * h packed crop pixels, then n * ceil(w h / 256) partial sums, all uint32.  PK_ERR_INVALID (and an error string) if the
+// shape is refused.
+static inline int64_t jitter_partial_offset(int n_samples, int out_w, int out_h) { return (int64_t)n_samples * out_w * out_h; }   // in uint32 words
+extern "C" int pk_affine_crop_jitter_ws_bytes(int n_samples, int out_w, int out_h) {
+    PK_REQUIRE(n_samples > 0 && out_w > 0 && out_h > 0 && (int64_t)out_w * out_h * 765 < (int64_t)1 << 32,
+               "pk_affine_crop_jitter_ws_bytes: bad shape n=%d w=%d h=%d (the byte sum of a crop must stay below 2^32)", n_samples, out_w, out_h);
+    const int64_t nblk = ((int64_t)out_w * out_h + 255) / 256, bytes = 4 * (jitter_partial_offset(n_samples, out_w, out_h) + n_samples * nblk);
+    PK_REQUIRE(bytes <= 0x7fffffff, "pk_affine_crop_jitter_ws_bytes: %lld-byte workspace for n=%d w=%d h=%d exceeds 2^31", (long long)bytes,
+               n_samples, out_w, out_h);
+    return (int)bytes;
+}
+extern "C" int pk_affine_crop_jitter_normalize(const void* src_u8, const void* desc_table, const void* jitter_table, int n_samples, int out_w,
+                                               int out_h, float* out_nchw_f32, void* out_nhwc8_bf16, const float* mean3, const float* std3,
+                                               void* ws, int64_t ws_bytes, void* stream) {
+    PK_REQUIRE(crop_pointers_ok(src_u8, desc_table, out_nchw_f32, out_nhwc8_bf16, mean3, std3) && jitter_table && ws,
+               "pk_affine_crop_jitter_normalize: null pointer");
+    const int need = pk_affine_crop_jitter_ws_bytes(n_samples, out_w, out_h);       // the shape checks live there
+    if (need < 0) return need;
+    PK_REQUIRE(ws_bytes >= need, "pk_affine_crop_jitter_normalize: workspace of %lld bytes, %d needed", (long long)ws_bytes, need);
+    PK_REQUIRE((((uintptr_t)ws) & 3) == 0 && nhwc8_aligned(out_nhwc8_bf16),
+               "pk_affine_crop_jitter_normalize: alignment (workspace 4 bytes, NHWC output 16 bytes)");
+    const int nblk = (out_w * out_h + 255) / 256;
+    uint32_t* crop = (uint32_t*)ws;
+    uint32_t* partial = crop + jitter_partial_offset(n_samples, out_w, out_h);
+    hipLaunchKernelGGL(k_crop_u8, dim3(nblk, n_samples), dim3(256), 0, (hipStream_t)stream, (const unsigned char*)src_u8, (const CropDesc*)desc_table,
+                       out_w, out_h, crop, partial);
+    hipLaunchKernelGGL(k_jitter_normalize, dim3(nblk, n_samples), dim3(256), 0, (hipStream_t)stream, (const uint32_t*)crop, (const uint32_t*)partial,
+                       (const JitterDesc*)jitter_table, out_w, out_h, out_nchw_f32, (uint16_t*)out_nhwc8_bf16, mean3[0], mean3[1], mean3[2],
+                       std3[0], std3[1], std3[2]);
+    return pk_launch_status("pk_affine_crop_jitter_normalize");
+}

@@ -1,4 +1,4 @@
-// Input layout conversion, weight packing and the padded-twin box copy.
+// Input layout conversion, weight packing, the padded-twin box copy, window partition / reverse (pk_rows_by_map) and DropPath.
 #include "pk_rowops.h"
 
 // ================================================================================================ layout / packing
@@ -104,4 +104,43 @@ extern "C" int pk_embed_boxes(float* twin_base, const void* desc_table, const in
     hipLaunchKernelGGL(k_embed_boxes, dim3(n_blocks), dim3(256), 0, (hipStream_t)stream, twin_base, (const EmbedDesc*)desc_table, block_desc,
                        block_first, direction);
     return pk_launch_status("pk_embed_boxes");
+}
+
+// window_partition / window_reverse (hrformer.py:67-114) as row moves through the window row map (window-order token -> pixel row, -1 = one
+// of the zero tokens appended at the bottom / right): gather = partition (pad tokens read as zeros), scatter = reverse (pad tokens dropped).
+// Rows are `row_dwords` 4-byte words of any element type.
+__global__ void k_rows_by_map(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, const int* __restrict__ map, long n_rows,
+                              int row_dwords, int scatter) {
+    const long total = n_rows * row_dwords;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const long r = i / row_dwords;
+        const int c = (int)(i - r * row_dwords), pr = map[r];
+        if (scatter) {
+            if (pr >= 0) dst[(long)pr * row_dwords + c] = src[i];
+        } else {
+            dst[i] = pr >= 0 ? src[(long)pr * row_dwords + c] : 0u;
+        }
+    }
+}
+extern "C" int pk_rows_by_map(const void* src, void* dst, const int* rowmap, int64_t n_rows, int row_bytes, int scatter, void* stream) {
+    PK_REQUIRE(src && dst && rowmap && n_rows > 0 && row_bytes > 0 && row_bytes % 4 == 0, "pk_rows_by_map: bad argument (rows of whole dwords)");
+    const long total = n_rows * (row_bytes / 4);
+    const int nb = capped_grid((total + 255) / 256, 4096);
+    hipLaunchKernelGGL(k_rows_by_map, dim3(nb), dim3(256), 0, (hipStream_t)stream, (const uint32_t*)src, (uint32_t*)dst, rowmap, (long)n_rows,
+                       row_bytes / 4, scatter);
+    return pk_launch_status("pk_rows_by_map");
+}
+
+// drop_path (hrformer.py:15-24): out = (x / keep) * mask[sample], mask in {0, 1}; fp32 elements, `per_sample` of them per sample.
+__global__ void k_drop_path(const float* __restrict__ x, const float* __restrict__ mask, float* __restrict__ out, long total, long per_sample,
+                            float keep) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x)
+        out[i] = (x[i] / keep) * mask[i / per_sample];
+}
+extern "C" int pk_drop_path_f32(const float* x, const float* mask, float* out, int64_t batch, int64_t per_sample, float keep_prob, void* stream) {
+    PK_REQUIRE(x && mask && out && batch > 0 && per_sample > 0 && keep_prob > 0.f, "pk_drop_path_f32: bad argument");
+    const long total = batch * per_sample;
+    const int nb = capped_grid((total + 255) / 256, 4096);
+    hipLaunchKernelGGL(k_drop_path, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, mask, out, total, (long)per_sample, keep_prob);
+    return pk_launch_status("pk_drop_path_f32");
 }

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Time the unbiased (DARK) decode against the quarter-shift decode on the device: `hipops.unbiased_decode(kernel=11)` and
-`hipops.argmax_decode(mode=1)` (pk_unbiased_decode / pk_argmax_decode, csrc/pk_target_decode.hip) on the same heatmaps, inputs already on the
+`hipops.argmax_decode(mode=1)` (pk_unbiased_decode / pk_argmax_decode, csrc/pk_decode.hip) on the same heatmaps, inputs already on the
 device, at the COCO shape (64, 17, 64, 48) and the infant shape (64, 13, 128, 128).  Both kernels read every map once; the unbiased one
 then blurs a (kernel + 4) x 5 patch per map.  Each figure is a host clock around `--inner` back-to-back calls that ends in a synchronise,
 divided by `--inner` (one call is a few microseconds: a single call would time the clock); the two decodes alternate inside every repeat.

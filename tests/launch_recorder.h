@@ -1,4 +1,4 @@
-// Preamble of the host-only launch recorders (tests/launch_recorder.hip, tests/launch_recorder_norm.hip): include it BEFORE the units.
+// Preamble of the host-only launch recorders (tests/launch_recorder*.hip): include it BEFORE the units.
 //
 // The units are compiled into the recorder with the HIP launch macro replaced by a printer, so the real entry points run their
 // argument checks and their routing on any machine and no kernel is ever started: hipGetDevice fails, every pointer is a made-up
@@ -14,7 +14,6 @@
 
 static char g_line[1 << 16];
 static size_t g_len = 0;
-static char g_err[1024];
 static void emit(const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
@@ -41,7 +40,7 @@ static void rec_launch(const char* kern, dim3 grid, dim3 block, size_t lds, cons
     rec_args(Rec{}, a...);
 }
 #undef hipLaunchKernelGGL
-#define hipLaunchKernelGGL(kern, grid, block, lds, stream, ...) rec_launch(#kern, grid, block, lds, __VA_ARGS__)
+#define hipLaunchKernelGGL(kern, grid, block, lds, stream, ...) rec_launch(#kern, grid, block, lds, ##__VA_ARGS__)
 #define hipFuncSetAttribute(...) hipSuccess
 #define hipGetLastError() hipSuccess
 #define hipGetDevice(p) hipErrorNoDevice
@@ -52,16 +51,26 @@ static void rec_launch(const char* kern, dim3 grid, dim3 block, size_t lds, cons
 #define __launch_bounds__(...)
 #define amdgpu_waves_per_eu(...)
 
+// The error text: the recorder's own pk_set_error, or, for a recorder that includes the unit which defines the library's
+// (REC_LIBRARY_ERRORS), what pk_last_error_string gives back.
+#ifdef REC_LIBRARY_ERRORS
+extern "C" const char* pk_last_error_string(void);
+void pk_set_error(const char* fmt, ...);
+static const char* rec_error() { return pk_last_error_string(); }
+#else
+static char g_err[1024];
 void pk_set_error(const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
 }
+static const char* rec_error() { return g_err; }
+#endif
 static void finish(int rc) {
     emit(" | rc=%d", rc);
-    if (rc) emit(" err=\"%s\"", g_err);
-    g_err[0] = 0;
+    if (rc) emit(" err=\"%s\"", rec_error());
+    pk_set_error("%s", "");
 }
 
 // made-up addresses: 16-byte aligned unless an offset is added
