@@ -215,6 +215,20 @@ int pk_motion_stats(const float* coords, const float* conf, double* stats, int S
 int pk_position_histogram(const float* coords, const float* conf, const double* edges_x, const double* edges_y, int32_t* counts,
                           int S, int T, int K, int nbx, int nby, float min_conf, void* stream);
 
+/* ---- movement frequency spectrum of pose sequences (this project's own specification: DESIGN.md "Movement spectrum") -----------------
+ * pk_motion_spectrum: coords (S,T,K,2) f32 image pixels; conf (S,T,K) f32 or NULL; frames are valid as for pk_motion_stats.  power (S,K,F)
+ *   and summary (S,K,6) float64, every element written.  Two launches; no float atomics, every sum in a fixed order that depends on T
+ *   alone: two launches give identical bits, and a bin's bits depend neither on S, on K nor on the other bins of the launch.
+ *   Bin j (0 <= j < F) is the frequency (j0 + j) / N cycles per frame; j0 >= 1, j0 + F - 1 <= N / 2, 2 <= N <= 2^30 (N > T zero-pads),
+ *   1 <= F <= 16384.  window 0: w_t = 1; window 1: periodic Hann, w_t = 0.5 - 0.5 cos(6.283185307179586 ((double)t / (double)T)); an invalid
+ *   frame has weight 0.  Per joint, in float64 without FMA: n = valid frames, W = sum w_t, m = sum w_t p_t / W, u_t = w_t (p_t - m),
+ *   X_j = sum_t u_t.x (cos ang, sin ang) and Y_j likewise with r = ((int64)(j0 + j) t) mod N, ang = 6.283185307179586 ((double)r / (double)N),
+ *   P_j = (4 / (W W)) ((Xre^2 + Xim^2) + (Yre^2 + Yim^2)): a linear oscillation of amplitude A px at a bin frequency has P = A^2.  n < 2 or
+ *   not W > 0: the whole row is 0.  Summary columns: 0 n; 1 W; 2 band power sum_j P_j; 3 peak bin j0 + argmax_j P_j (the lowest among equal
+ *   maxima; -1 when column 2 is 0); 4 the peak's power (or 0); 5 centroid sum (j0 + j) P_j / sum P_j in bins (or 0).                      */
+int pk_motion_spectrum(const float* coords, const float* conf, double* power, double* summary, int S, int T, int K, float min_conf,
+                       int N, int j0, int F, int window, void* stream);
+
 /* ---- L1/L2: FusionPoseLoss.forward (models/fusion_head.py:745-806 with :405-559, :637-743) ---------------
  * stats: workspace of B*K*PK_LOSS_STAT floats + B*16*4 floats + 16 floats (see PK_LOSS_WS_FLOATS);
  * losses: 7 floats (heatmap, offset, peak, variance, overlap, shape, total — already multiplied by lambdas).

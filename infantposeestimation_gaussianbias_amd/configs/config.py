@@ -14,7 +14,8 @@ identically.  Extension over the reference: `get_config(path_or_name)` also acce
     `in_vis_thr` / `soft_nms` (validation on detector boxes; `TEST.USE_GT_BBOX: false` without a box file changes nothing and says so),
     and `TEST.DECODE: 'shift' | 'unbiased'` / `TEST.MODULATE_KERNEL` onto `cfg.decode` / `cfg.modulate_kernel` (the heatmap decode of the
     heatmap-head models; a bad value raises and names the key).  `TEST.POST_PROCESS` and `TEST.SHIFT_HEATMAP` are deliberately NOT mapped:
-    both shipped yamls set them true, and mapping them would change what those configurations do today.
+    both shipped yamls set them true, and mapping them would change what those configurations do today.  `CLINICAL.FREQUENCY_BAND:
+    [lo, hi]` (Hz; this project's own key) maps onto `cfg.frequency_band`, the band of the movement spectrum; a bad value names the key.
 """
 import logging
 import math
@@ -123,6 +124,9 @@ class Config:
     # log of the map smoothed with `modulate_kernel` Gaussian taps, an odd size from 3 to 31).
     decode = None
     modulate_kernel = 11
+    # Movement spectrum (this project's own legacy-yaml key CLINICAL.FREQUENCY_BAND, `inference.py --freq_band`), a plain class attribute as
+    # well.  frequency_band: None or (f_min, f_max) in Hz, the band whose dominant frequency and power `movement_report` adds per joint.
+    frequency_band = None
 
 
 _PRESETS = {
@@ -167,6 +171,21 @@ def check_decode(decode, modulate_kernel=11, what=("decode", "modulate_kernel"))
     if not ok:
         raise ValueError(f"{what[1]} must be an odd integer from 3 to 31, got {modulate_kernel!r}")
     return decode, k
+
+
+def check_frequency_band(band, what="frequency_band") -> Tuple[float, float]:
+    """A movement-frequency band as (f_min, f_max) in Hz: two finite numbers with 0 <= f_min < f_max.  ValueError naming `what` (the key or
+    flag the value came from) otherwise."""
+    try:
+        lo, hi = band
+        ok = not isinstance(lo, (bool, str)) and not isinstance(hi, (bool, str))
+        lo, hi = float(lo), float(hi)
+        ok = ok and math.isfinite(lo) and math.isfinite(hi) and 0 <= lo < hi
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"{what} must be [f_min, f_max] in Hz with 0 <= f_min < f_max, got {band!r}")
+    return lo, hi
 
 
 def _apply_preset(cfg: Config, name: str) -> Config:
@@ -257,6 +276,9 @@ def _apply_legacy_yaml(cfg: Config, path: str) -> Config:
     if cl.get('ENABLE_MOVEMENT_TRACKING'):
         cfg.clinical = {'min_movement': float(cl.get('MIN_MOVEMENT_THRESHOLD', 5.0)), 'max_movement': float(cl.get('MAX_MOVEMENT_THRESHOLD', 200.0)),
                         'alert_low': bool(cl.get('ALERT_ON_LOW_MOVEMENT', False)), 'alert_asymmetry': bool(cl.get('ALERT_ON_ASYMMETRY', False))}
+    # CLINICAL.FREQUENCY_BAND: [lo, hi] in Hz is this project's own key (the reference's yamls have none): the band of the movement spectrum
+    if cl.get('FREQUENCY_BAND') is not None:
+        cfg.frequency_band = check_frequency_band(cl['FREQUENCY_BAND'], 'CLINICAL.FREQUENCY_BAND')
     cfg.exp_name = os.path.splitext(os.path.basename(path))[0]
     return cfg
 

@@ -628,6 +628,36 @@ def position_histogram(coords, edges_x, edges_y, conf=None, min_conf=0.3):
     return counts
 
 
+SPECTRUM_MAX_BINS = 16384
+SPECTRUM_MAX_NFFT = 1 << 30
+
+
+def motion_spectrum(coords, conf=None, min_conf=0.3, n_fft=None, j0=1, n_bins=None, window=1):
+    """(S,T,K,2) image-pixel trajectories (+ (S,T,K) confidences) -> power (S,K,F) and summary (S,K,6), float64 (pk_motion_spectrum).
+    Bin j is the frequency (j0 + j) / n_fft cycles per frame (n_fft: T when None; larger zero-pads; n_bins: up to n_fft // 2 when None);
+    window 0 rectangular, 1 periodic Hann.  A linear oscillation of amplitude A px at a bin frequency has power A^2.  Summary columns:
+    valid frames, window sum, band power, peak bin (-1 without power), peak power, centroid in bins."""
+    coords, conf, S, T, K = _sequences(coords, conf)
+    N = T if n_fft is None else int(n_fft)
+    j0 = int(j0)
+    F = N // 2 - j0 + 1 if n_bins is None else int(n_bins)
+    if not 2 <= N <= SPECTRUM_MAX_NFFT:
+        raise ValueError(f"n_fft: expected 2 to {SPECTRUM_MAX_NFFT}, got {N}")
+    if j0 < 1 or F < 1 or j0 + F - 1 > N // 2:
+        raise ValueError(f"bins {j0} to {j0 + F - 1}: expected a non-empty range inside 1 to n_fft // 2 = {N // 2}")
+    if F > SPECTRUM_MAX_BINS:
+        raise ValueError(f"n_bins: {F} bins in one call (at most {SPECTRUM_MAX_BINS}); take the band in parts")
+    if window not in (0, 1):
+        raise ValueError(f"window: expected 0 (rectangular) or 1 (Hann), got {window!r}")
+    power = torch.zeros(S, K, F, dtype=F64, device=coords.device)
+    summary = torch.zeros(S, K, 6, dtype=F64, device=coords.device)
+    if S * T * K > 0:
+        call("pk_motion_spectrum", coords, conf, power, summary, S, T, K, float(min_conf), N, j0, F, int(window), stream_ptr())
+    else:
+        summary[..., 3] = -1.0                                    # no frame: no power, no peak
+    return power, summary
+
+
 # ------------------------------------------------------------------------------------------------ overlays
 U8 = torch.uint8
 

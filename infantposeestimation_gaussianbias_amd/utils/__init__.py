@@ -1,6 +1,6 @@
 """Utils module."""
 from .metrics import (AverageMeter, COCOEvaluator, MetricLogger, PCKAccumulator, calculate_movement_amplitude, calculate_pck,
-                      calculate_temporal_consistency, movement_heatmap, movement_report)
+                      calculate_temporal_consistency, movement_heatmap, movement_report, movement_spectrum)
 from . import postprocess
 from .postprocess import oks_nms, soft_oks_nms
 from . import visualization
@@ -10,4 +10,4 @@ from .visualization import (COCO_COLORS, COCO_SKELETON, create_grid_image, draw_
 __all__ = ['AverageMeter', 'COCOEvaluator', 'MetricLogger', 'postprocess', 'visualization', 'draw_skeleton', 'draw_heatmaps', 'draw_bbox',
            'draw_poses', 'draw_person_heatmaps', 'create_grid_image', 'save_visualization', 'save_person_visualization', 'COCO_SKELETON',
            'COCO_COLORS', 'PCKAccumulator', 'calculate_movement_amplitude', 'calculate_pck', 'calculate_temporal_consistency',
-           'movement_heatmap', 'movement_report', 'oks_nms', 'soft_oks_nms']
+           'movement_heatmap', 'movement_report', 'movement_spectrum', 'oks_nms', 'soft_oks_nms']

@@ -248,15 +248,46 @@ def calculate_temporal_consistency(keypoints_sequence, confidence=None, min_conf
 
 
 def movement_report(keypoints_sequence, confidence=None, flip_pairs=(), min_confidence: float = 0.3, min_movement: float = 5.0,
-                    max_movement: float = 200.0, asymmetry_threshold: float = 0.2, fps: Optional[float] = None) -> Dict:
+                    max_movement: float = 200.0, asymmetry_threshold: float = 0.2, fps: Optional[float] = None, spectrum=None) -> Dict:
     """JSON-serialisable movement summary of one (T,K,2) trajectory, built from ONE (K,11) device->host copy.  Per joint: amplitude, path
     length, mean and largest speed (px / frame, or px / s with `fps`), share of valid frames, and the flag 'low' (amplitude below
     `min_movement`), 'high' (above `max_movement`) or None.  Per (left, right) pair of `flip_pairs`: ratio = |a_L - a_R| / max(a_L, a_R)
     (0 when both are 0) and asymmetric = ratio > asymmetry_threshold (examples/quick_start.py:242,249 of the reference; 5 / 200 px are
-    its yaml's CLINICAL thresholds)."""
-    stats, _ = _sequence_stats(keypoints_sequence, confidence, min_confidence)
-    return _report_from_stats(stats.cpu().numpy(), int(keypoints_sequence.shape[0]), flip_pairs, min_movement, max_movement,
-                              asymmetry_threshold, fps)
+    its yaml's CLINICAL thresholds).
+    spectrum=(f_min, f_max) in Hz (needs `fps`): the Hann-windowed movement spectrum of that band (`movement_spectrum`) adds, from one more
+    (K,6) copy, `dominant_frequency` (Hz; None for a joint without power in the band), `peak_amplitude` (px) and `band_power` to each
+    joint, `frequency_difference` (Hz, or None) to each pair and `frequency_band` to the report.  Without it the report is unchanged."""
+    band = None
+    if spectrum is not None:
+        if fps is None:
+            raise ValueError("movement_report: spectrum=(f_min, f_max) is in Hz and needs fps")
+        from ..configs.config import check_frequency_band
+        band = check_frequency_band(spectrum, "spectrum")
+        T = int(keypoints_sequence.shape[0])
+        j0, F = _band_bins(float(fps), T, band[0], band[1])
+    from .. import hipops
+    coords, conf, _ = _sequence_in(keypoints_sequence, confidence)
+    stats = hipops.motion_stats(coords, conf, min_confidence)[0]
+    report = _report_from_stats(stats.cpu().numpy(), int(keypoints_sequence.shape[0]), flip_pairs, min_movement, max_movement,
+                                asymmetry_threshold, fps)
+    if band is not None:
+        _, summary = hipops.motion_spectrum(coords, conf, min_confidence, T, j0, F, 1)
+        _add_spectrum_to_report(report, summary[0].cpu().numpy(), band, T, float(fps))
+    return report
+
+
+def _add_spectrum_to_report(report: Dict, summary: np.ndarray, band, n_fft: int, fps: float) -> Dict:
+    """The spectrum entries of `movement_report` from the (K,6) summary of pk_motion_spectrum."""
+    peak = [float(summary[k, 3]) / n_fft * fps if summary[k, 3] >= 0 else None for k in range(summary.shape[0])]
+    for k, joint in enumerate(report["joints"]):
+        joint["dominant_frequency"] = peak[k]
+        joint["peak_amplitude"] = float(np.sqrt(summary[k, 4]))
+        joint["band_power"] = float(summary[k, 2])
+    for pair in report["pairs"]:
+        a, b = peak[pair["left"]], peak[pair["right"]]
+        pair["frequency_difference"] = None if a is None or b is None else abs(a - b)
+    report["frequency_band"] = [float(band[0]), float(band[1])]
+    return report
 
 
 def _report_from_stats(st: np.ndarray, n_frames: int, flip_pairs, min_movement, max_movement, asymmetry_threshold, fps) -> Dict:
@@ -289,6 +320,80 @@ def movement_heatmap(keypoints_sequence, image_shape, bin_size: int = 10, confid
     coords, conf, as_numpy = _sequence_in(keypoints_sequence, confidence)
     counts = hipops.position_histogram(coords, np.linspace(0, W, nbx + 1), np.linspace(0, H, nby + 1), conf, min_confidence)[0]
     return counts.cpu().numpy() if as_numpy else counts
+
+
+# ---------------------------------------------------------------------------------------------- movement spectrum
+# How fast a joint oscillates and how much of its movement lies in a frequency band (DESIGN.md "Movement spectrum"): pk_motion_spectrum on
+# the device, bin selection and unit conversion (bins -> Hz) here.
+_WINDOWS = {"rect": 0, "hann": 1}
+
+
+def _band_bins(fps: float, n_fft: int, f_min, f_max):
+    """First bin j0 and number of bins F of the band: the bins j of 1 .. n_fft // 2 with f_min <= j / n_fft * fps <= f_max, decided on the
+    very expression that `frequencies` reports.  ValueError for a band beyond the Nyquist frequency fps / 2 or one that holds no bin."""
+    if not (np.isfinite(fps) and fps > 0):
+        raise ValueError(f"fps must be a positive number, got {fps!r}")
+    if n_fft < 2:
+        raise ValueError(f"n_fft must be at least 2 (a sequence of at least 2 frames), got {n_fft}")
+    if (f_min is not None and not f_min >= 0) or (f_max is not None and not f_max >= (f_min or 0)):
+        raise ValueError(f"frequency band: expected 0 <= f_min <= f_max in Hz, got f_min={f_min!r}, f_max={f_max!r}")
+    freq = lambda j: j / n_fft * fps
+    top = n_fft // 2
+    shown = f"[{0.0 if f_min is None else f_min:g}, {fps / 2 if f_max is None else f_max:g}] Hz"
+    if (f_max is not None and f_max > fps / 2) or (f_min is not None and f_min > fps / 2):
+        raise ValueError(f"frequency band {shown} reaches beyond the Nyquist frequency fps / 2 = {fps / 2:g} Hz")
+    lo = 1 if f_min is None else min(max(int(np.ceil(f_min * n_fft / fps)), 1), top)
+    while f_min is not None and lo > 1 and freq(lo - 1) >= f_min:
+        lo -= 1
+    while f_min is not None and lo <= top and freq(lo) < f_min:
+        lo += 1
+    hi = top if f_max is None else min(max(int(np.floor(f_max * n_fft / fps)), 0), top)
+    while f_max is not None and hi < top and freq(hi + 1) <= f_max:
+        hi += 1
+    while f_max is not None and hi >= 1 and freq(hi) > f_max:
+        hi -= 1
+    if hi < lo:
+        raise ValueError(f"frequency band {shown} holds no bin of a {n_fft}-point transform at {fps:g} fps (bins are {fps / n_fft:g} Hz apart, "
+                         f"fps / 2 = {fps / 2:g} Hz)")
+    return lo, hi - lo + 1
+
+
+def movement_spectrum(keypoints_sequence, fps: float, confidence=None, min_confidence: float = 0.3, f_min: Optional[float] = None,
+                      f_max: Optional[float] = None, n_fft: Optional[int] = None, window: str = 'hann') -> Dict:
+    """Movement frequency spectrum of one (T,K,2) trajectory in pixels, recorded at `fps` frames per second (pk_motion_spectrum).  Frames
+    count as for `calculate_movement_amplitude`.  The transform has `n_fft` points (default T; more zero-pads and interpolates the
+    spectrum) under the periodic 'hann' window or 'rect'; the bins with f_min <= f <= f_max are computed (default: every bin from 1 to
+    n_fft // 2; at most 16 384 in one call -- give a band for longer transforms).  The joint's weighted mean is removed first, so there is
+    no bin 0.  ->
+      frequencies (F,) Hz      (j0 + j) / n_fft * fps
+      power (K,F) px^2         a linear oscillation of amplitude A px at a bin frequency has power A^2, a circle of radius R 2 R^2
+      peak_frequency (K,) Hz   the bin of the largest power (NaN for a joint without power: fewer than 2 valid frames, or no movement)
+      peak_amplitude (K,) px   the square root of that power
+      band_power (K,) px^2     the sum over the band
+      mean_frequency (K,) Hz   the power-weighted mean frequency of the band (0 without power)
+    numpy in -> numpy out, device tensor in -> device tensors out (float64).  ValueError for an empty band or one beyond fps / 2."""
+    from .. import hipops
+    if window not in _WINDOWS:
+        raise ValueError(f"window must be one of {sorted(_WINDOWS)}, got {window!r}")
+    shape = tuple(keypoints_sequence.shape)
+    if len(shape) != 3 or shape[-1] != 2:
+        raise ValueError(f"sequence: expected (T, K, 2), got {shape}")
+    N = shape[0] if n_fft is None else int(n_fft)
+    j0, F = _band_bins(float(fps), N, f_min, f_max)
+    coords, conf, as_numpy = _sequence_in(keypoints_sequence, confidence)
+    power, summary = hipops.motion_spectrum(coords, conf, min_confidence, N, j0, F, _WINDOWS[window])
+    power, summary = power[0], summary[0]
+    freqs = (j0 + np.arange(F)) / N * float(fps)
+    if as_numpy:
+        power, summary = power.cpu().numpy(), summary.cpu().numpy()
+        xp_where, nan, sqrt = np.where, np.nan, np.sqrt
+    else:
+        import torch
+        freqs = torch.from_numpy(freqs).to(power.device)
+        xp_where, nan, sqrt = torch.where, torch.full_like(summary[:, 3], float("nan")), torch.sqrt
+    peak = summary[:, 3]
+    return {"frequencies": freqs, "power": power, "peak_frequency": xp_where(peak >= 0, peak / N * float(fps), nan),
+            "peak_amplitude": sqrt(summary[:, 4]), "band_power": summary[:, 2], "mean_frequency": summary[:, 5] / N * float(fps)}
 
 
 class PCKAccumulator:

@@ -11,7 +11,8 @@ cropper launch, each image uploaded once -- and the passes are merged on the dev
 With `decode='unbiased'` (`--decode unbiased [--modulate_kernel K]`, or the config's `decode`) a heatmap-head model's maps are decoded by the
 unbiased, distribution-aware step (pk_unbiased_decode) instead of the quarter-pixel shift -- single images, `--scales` and `--sequence` alike.
 `predict_sequence` / `--sequence` take the frames of a video (a directory of images) for one person and keep the trajectory on the device
-for the movement analysis of utils/metrics.py (temporal smoothing, `movement_report`, `movement_heatmap`).
+for the movement analysis of utils/metrics.py (temporal smoothing, `movement_report`, `movement_heatmap`); `--freq_band LO HI` with `--fps`
+adds the movement spectrum of that band (pk_motion_spectrum) to the report.
 Visualisation is on the device too: `visualize` / `visualize_batch` draw through utils/visualization.py (pk_draw_shapes,
 pk_heatmap_overlay, pk_heatmap_overlay_patches: this project's own integer rasterisation rule, not OpenCV's pixels) and files are written
 with Pillow.
@@ -231,18 +232,23 @@ def detect_persons(img: np.ndarray) -> List[np.ndarray]:
 _FRAME_SUFFIXES = (".png", ".jpg", ".jpeg", ".bmp")
 
 
-def sequence_report(pose: PoseInference, frames, bbox=None, smooth: Optional[int] = None, fps: Optional[float] = None, batch_size: int = 16):
+def sequence_report(pose: PoseInference, frames, bbox=None, smooth: Optional[int] = None, fps: Optional[float] = None, batch_size: int = 16,
+                    freq_band=None):
     """Movement analysis of one person over `frames` (BGR arrays of one size): `predict_sequence`, temporal smoothing when `smooth` (an odd
     window, 'gaussian') or the config's `temporal` asks for it, then `movement_report` with the config's visibility and CLINICAL
-    thresholds.  -> (report dict, keypoints (T,K,2) and scores (T,K) on the device, the keypoints as analysed)."""
+    thresholds.  `freq_band` (f_min, f_max) in Hz, or the config's `frequency_band` when `fps` is known, adds the movement spectrum's
+    entries (dominant frequency, peak amplitude, band power); `freq_band` without `fps` is a ValueError.
+    -> (report dict, keypoints (T,K,2) and scores (T,K) on the device, the keypoints as analysed)."""
     cfg = pose.cfg
     kp, sc = pose.predict_sequence(frames, bbox, batch_size=batch_size)
     temporal = (int(smooth), "gaussian") if smooth else getattr(cfg, "temporal", None)
     if temporal:
         kp = temporal_smoothing(kp, window_size=temporal[0], method=temporal[1])
     clinical = getattr(cfg, "clinical", None) or {}
+    band = freq_band if freq_band is not None else (getattr(cfg, "frequency_band", None) if fps is not None else None)
     report = movement_report(kp, sc, flip_pairs=cfg.data.flip_pairs, min_confidence=cfg.min_keypoint_visibility,
-                             min_movement=clinical.get("min_movement", 5.0), max_movement=clinical.get("max_movement", 200.0), fps=fps)
+                             min_movement=clinical.get("min_movement", 5.0), max_movement=clinical.get("max_movement", 200.0), fps=fps,
+                             spectrum=None if band is None else tuple(band))
     report["smoothing"] = list(temporal) if temporal else None
     return report, kp, sc
 
@@ -258,7 +264,7 @@ def main_sequence(args, pose):
     if len({f.shape for f in frames}) != 1:
         raise SystemExit("--sequence: the frames differ in size")
     bbox = np.array(args.bbox) if args.bbox else None
-    report, kp, sc = sequence_report(pose, frames, bbox, smooth=args.smooth, fps=args.fps)
+    report, kp, sc = sequence_report(pose, frames, bbox, smooth=args.smooth, fps=args.fps, freq_band=getattr(args, "freq_band", None))
     report["frames"] = names
     text = json.dumps(report, indent=2)
     if args.report:
@@ -276,6 +282,8 @@ def main_sequence(args, pose):
 
 def main(args):
     from PIL import Image
+    if getattr(args, "freq_band", None) is not None and args.fps is None:
+        build_parser().error("--freq_band is in Hz and needs --fps")
     pose = PoseInference(checkpoint=args.checkpoint, device=args.device, flip_test=not args.no_flip, config=args.config, scales=args.scales,
                          decode=args.decode, modulate_kernel=args.modulate_kernel)
     if getattr(args, "sequence", False):
@@ -327,6 +335,10 @@ def build_parser():
     p.add_argument('--smooth', type=int, default=None, help='--sequence: smooth the trajectory with an odd gaussian window of this many '
                                                              'frames before the analysis (default: the config\'s TEMPORAL block)')
     p.add_argument('--fps', type=float, default=None, help='--sequence: frame rate, turns the speeds into pixels per second')
+    p.add_argument('--freq_band', type=float, nargs=2, default=None, metavar=('LO', 'HI'),
+                   help='--sequence with --fps: add the movement spectrum of the band LO to HI Hz to the report (per joint the dominant '
+                        'frequency, its amplitude and the band power; per left/right pair the frequency difference); default: the '
+                        'config\'s frequency_band')
     p.add_argument('--report', type=str, default=None, help='--sequence: write the movement report (JSON) here instead of printing it')
     p.add_argument('--decode', type=str, choices=('shift', 'unbiased'), default=None,
                    help='heatmap decode of a heatmap-head model, for single images, --scales and --sequence alike: shift = argmax + '

@@ -6,11 +6,13 @@
 Workloads:
   * pk_motion_stats and pk_position_histogram (640 x 480 frame, 10-px bins: 64 x 48) on (S, T, K) = (1, 18000, 17), ten minutes of one
     infant at 30 frames a second, and (64, 900, 13), 64 clips of half a minute; with confidences;
+  * pk_motion_spectrum (both launches) on the same two shapes, a band of 256 bins under the Hann window: bins 300 .. 555 of an 18 000-point
+    transform (0.5 to 0.925 Hz at 30 frames a second) and bins 1 .. 256 of a 1024-point one (zero-padded clips);
   * pk_pck on N = 6352 instances of K = 17 joints (the person instances of COCO val2017) at 6 thresholds.
 Kernels only (the C entries called directly into preallocated outputs), device-resident inputs, HIP events around `iters` back-to-back calls, `repeats` windows per variant with the variants
 ALTERNATING inside every repeat; median and min .. max of the per-call time.  The inputs are small (2.5 to 8 MB) and stay in the caches
 between calls: these are warm numbers, which is how a report over one trajectory calls the kernels (statistics, then histogram, on the same
-tensor).  Before anything is timed every kernel is checked against its numpy restatement (tests/motion_np.py), and the restatement is timed on
+tensor).  Before anything is timed every kernel is checked against its numpy restatement (tests/motion_np.py, tests/spectrum_np.py), and the restatement is timed on
 the host of the same box (best of 3) for scale.  Prints readable lines and one JSON line.
 """
 import argparse
@@ -26,11 +28,13 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import motion_np as mnp  # noqa: E402
+import spectrum_np as snp  # noqa: E402
 from infantposeestimation_gaussianbias_amd import _lib, hipops  # noqa: E402
 from infantposeestimation_gaussianbias_amd._lib import stream_ptr  # noqa: E402
 
 W, H, BIN = 640, 480, 10
 SHAPES = [(1, 18000, 17), (64, 900, 13)]
+SPECTRUM = {(1, 18000, 17): (18000, 300, 256), (64, 900, 13): (1024, 1, 256)}      # (S, T, K) -> n_fft, first bin, bins
 PCK_N, PCK_K, PCK_THR = 6352, 17, 6
 
 
@@ -99,6 +103,16 @@ def main():
         variants[f"position_histogram {tag}"] = entry("pk_position_histogram", dc, dconf, dex, dey, counts, S, T, K, W // BIN, H // BIN, 0.3)
         host[f"motion_stats {tag}"] = host_ms(lambda: mnp.motion_stats(c, conf, 0.3))
         host[f"position_histogram {tag}"] = host_ms(lambda: mnp.histogram2d(c, ex, ey, conf, 0.3))
+        n_fft, j0, nb = SPECTRUM[(S, T, K)]
+        p_want, n_valid, _, scale = snp.power(c, conf, 0.3, n_fft, j0, nb, 1)
+        p_got, s_got = (t.cpu().numpy() for t in hipops.motion_spectrum(dc, dconf, 0.3, n_fft, j0, nb, 1))
+        share = float((np.abs(p_got - p_want) / ((n_valid + 16) * 2.0 ** -50 * scale)[..., None]).max())      # of the tests' bound
+        assert share <= 1.0 and np.array_equal(s_got[..., 0], n_valid), (tag, share)
+        checks[tag]["spectrum_err_share_of_bound"] = share
+        power = torch.empty(S, K, nb, dtype=torch.float64, device=dev)
+        summary = torch.empty(S, K, 6, dtype=torch.float64, device=dev)
+        variants[f"motion_spectrum {tag} {nb} bins"] = entry("pk_motion_spectrum", dc, dconf, power, summary, S, T, K, 0.3, n_fft, j0, nb, 1)
+        host[f"motion_spectrum {tag} {nb} bins"] = host_ms(lambda: snp.spectrum(c, conf, 0.3, n_fft, j0, nb, 1))
     g = np.random.default_rng(3)
     gt = (g.random((PCK_N, PCK_K, 2)) * [W, H]).astype(np.float32)
     norm = (g.random(PCK_N) * 300 + 30).astype(np.float32)
