@@ -303,6 +303,17 @@ int pk_adamw_step_guarded(float* param, const float* grad, float* exp_avg, float
                           uint16_t* param_bf16, int64_t n, const float* lr_dev, const int32_t* step_dev,
                           float beta1, float beta2, float eps, float weight_decay, float grad_scale,
                           const int32_t* guard_state, void* stream);
+/* Weight EMA (opt-in): the update of pk_adamw_step (guard_state NULL) or of pk_adamw_step_guarded (guard_state given), and in the same
+ * pass, for every element whose flag has bit1 set, ema += (1 - d_t) * (param_new - ema) in fp32 with param_new taken from registers.
+ * d_t = min(ema_decay, (1 + t) / (10 + t)) with t = (float)step_dev[0], the bias correction's t (applied updates, >= 1), computed on
+ * the device in every launch: a replayed graph and a guarded run advance the warm-up without a host write.  Elements without bit1
+ * keep their ema bits.  A skipped step (guard_state[2] set) touches nothing, ema included.  param, exp_avg, exp_avg_sq and the bf16
+ * copy come out bitwise as from the entry point it stands in for.  ema: n floats, 16-byte aligned, not overlapping param;
+ * 0 < ema_decay < 1.  36 bytes per element instead of 28.                                                                        */
+int pk_adamw_step_ema(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const uint8_t* decay_mask,
+                      uint16_t* param_bf16, int64_t n, const float* lr_dev, const int32_t* step_dev,
+                      float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                      const int32_t* guard_state, float* ema, float ema_decay, void* stream);
 
 
 /* ======================= network contractions (bf16 MFMA, fp32 accumulate; NHWC activations) =======================

@@ -89,6 +89,9 @@ class TrainConfig:
     # saturation) ranges.  Plain class attributes, NOT dataclass fields: the field set stays the reference's (asdict, __init__, ==).
     color_jitter = None
     color_jitter_prob = 0.5
+    # Weight EMA (`train.py --ema DECAY`): None (off) or the decay of the average the optimiser kernel keeps.  A plain class attribute too;
+    # no yaml key (the reference's configs have none).
+    ema_decay = None
 
 
 @dataclass

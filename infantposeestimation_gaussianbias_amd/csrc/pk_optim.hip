@@ -11,12 +11,15 @@ static inline int64_t optim_blocks(int64_t n) {
     return blocks > PK_OPTIM_MAX_BLOCKS ? PK_OPTIM_MAX_BLOCKS : blocks;
 }
 
-// The update of both AdamW kernels: everything after the learning rate, the step number and the gradient factor are known.  The lane's
+// The update of the AdamW kernels: everything after the learning rate, the step number and the gradient factor are known.  The lane's
 // first float4 and the grid stride come from the kernel (blockDim read inside a device function compiles to a slower lookup).
+// EMA: e += ema_w * (p_new - e) on the elements that were updated, with p_new still in registers (ema_w = 1 - d_t; +8 B/elem).  With
+// EMA = false neither `ema` nor `ema_w` is read, and k_adamw / k_adamw_guarded compile to the code they had before the flag existed.
+template <bool EMA>
 __device__ __forceinline__ void adamw_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                              float* __restrict__ v, const uint8_t* __restrict__ flags, uint16_t* __restrict__ pb,
                                              int64_t n, int64_t first, int64_t stride, float lr, float t, float b1, float b2, float eps,
-                                             float wd, float gscale) {
+                                             float wd, float gscale, float* __restrict__ ema, float ema_w) {
     const float bc1 = 1.f - powf(b1, t), bc2s = sqrtf(1.f - powf(b2, t));
     const float step_size = lr / bc1;
     const int64_t n4 = n >> 2;
@@ -24,7 +27,9 @@ __device__ __forceinline__ void adamw_update(float* __restrict__ p, const float*
         float4 P = reinterpret_cast<float4*>(p)[i], G = reinterpret_cast<const float4*>(g)[i];
         float4 M = reinterpret_cast<float4*>(m)[i], V = reinterpret_cast<float4*>(v)[i];
         const uint32_t f4 = reinterpret_cast<const uint32_t*>(flags)[i];
-        float* pp = &P.x; float* gg = &G.x; float* mm = &M.x; float* vv = &V.x;
+        float4 E;
+        if constexpr (EMA) E = reinterpret_cast<float4*>(ema)[i];
+        float* pp = &P.x; float* gg = &G.x; float* mm = &M.x; float* vv = &V.x; float* ee = &E.x;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const uint32_t f = (f4 >> (8 * j)) & 0xff;
@@ -34,11 +39,13 @@ __device__ __forceinline__ void adamw_update(float* __restrict__ p, const float*
                 mm[j] = b1 * mm[j] + (1.f - b1) * gr;
                 vv[j] = b2 * vv[j] + (1.f - b2) * gr * gr;
                 pp[j] -= step_size * mm[j] / (sqrtf(vv[j]) / bc2s + eps);
+                if constexpr (EMA) ee[j] = ee[j] + ema_w * (pp[j] - ee[j]);
             }
         }
         reinterpret_cast<float4*>(p)[i] = P;
         reinterpret_cast<float4*>(m)[i] = M;
         reinterpret_cast<float4*>(v)[i] = V;
+        if constexpr (EMA) reinterpret_cast<float4*>(ema)[i] = E;  // elements without bit1 go back as they came
         if (pb) {
             uint2 o;
             o.x = pack_bf16x2(P.x, P.y);
@@ -52,8 +59,8 @@ __global__ void __launch_bounds__(256) k_adamw(float* __restrict__ p, const floa
                                                float* __restrict__ v, const uint8_t* __restrict__ flags, uint16_t* __restrict__ pb,
                                                int64_t n, const float* __restrict__ lr_dev, const int32_t* __restrict__ step_dev,
                                                float b1, float b2, float eps, float wd, float gscale) {
-    adamw_update(p, g, m, v, flags, pb, n, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x, lr_dev[0],
-                 (float)step_dev[0], b1, b2, eps, wd, gscale);
+    adamw_update<false>(p, g, m, v, flags, pb, n, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x,
+                        lr_dev[0], (float)step_dev[0], b1, b2, eps, wd, gscale, nullptr, 0.f);
 }
 
 // guard_state (written by k_grad_guard_finalize): [0] norm (float), [1] coef (float), [2] skipped_last, [3] skipped_total (int32)
@@ -64,8 +71,26 @@ __global__ void __launch_bounds__(256) k_adamw_guarded(float* __restrict__ p, co
                                                        float gscale, const int32_t* __restrict__ guard_state) {
     if (guard_state[2]) return;  // a gradient was inf/NaN: p, m, v and the bf16 copy keep their values
     const float coef = __int_as_float(guard_state[1]);
-    adamw_update(p, g, m, v, flags, pb, n, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x, lr_dev[0],
-                 (float)step_dev[0], b1, b2, eps, wd, gscale * coef);
+    adamw_update<false>(p, g, m, v, flags, pb, n, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x,
+                        lr_dev[0], (float)step_dev[0], b1, b2, eps, wd, gscale * coef, nullptr, 0.f);
+}
+
+// The update plus the weight average.  guard_state == NULL: k_adamw's update, else k_adamw_guarded's.  The decay is worked out here, in
+// every launch, from the same step count as the bias correction (applied updates, >= 1): d_t = min(ema_decay, (1 + t) / (10 + t)), so
+// a replayed graph and a guarded run advance the warm-up with no host write, and a skipped step leaves `ema` alone with everything else.
+__global__ void __launch_bounds__(256) k_adamw_ema(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                   float* __restrict__ v, const uint8_t* __restrict__ flags, uint16_t* __restrict__ pb,
+                                                   int64_t n, const float* __restrict__ lr_dev, const int32_t* __restrict__ step_dev,
+                                                   float b1, float b2, float eps, float wd, float gscale,
+                                                   const int32_t* __restrict__ guard_state, float* __restrict__ ema, float ema_decay) {
+    if (guard_state) {
+        if (guard_state[2]) return;  // a gradient was inf/NaN: p, m, v, the bf16 copy and ema keep their values
+        gscale *= __int_as_float(guard_state[1]);
+    }
+    const float t = (float)step_dev[0];
+    const float d = fminf(ema_decay, (1.f + t) / (10.f + t));
+    adamw_update<true>(p, g, m, v, flags, pb, n, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x,
+                       lr_dev[0], t, b1, b2, eps, wd, gscale, ema, 1.f - d);
 }
 
 // Fixed-order sum over the 256 lanes of a workgroup (fp64 has no wave_sum): LDS tree, one barrier per level.  Result in s[0] / bad[0].
@@ -200,4 +225,21 @@ extern "C" int pk_adamw_step_guarded(float* param, const float* grad, float* exp
     hipLaunchKernelGGL(k_adamw_guarded, dim3((unsigned)optim_blocks(n)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
                        exp_avg_sq, decay_mask, param_bf16, n, lr_dev, step_dev, beta1, beta2, eps, weight_decay, grad_scale, guard_state);
     return pk_launch_status("pk_adamw_step_guarded");
+}
+
+extern "C" int pk_adamw_step_ema(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const uint8_t* decay_mask,
+                                 uint16_t* param_bf16, int64_t n, const float* lr_dev, const int32_t* step_dev, float beta1, float beta2,
+                                 float eps, float weight_decay, float grad_scale, const int32_t* guard_state, float* ema, float ema_decay,
+                                 void* stream) {
+    if (int rc = adamw_check("pk_adamw_step_ema", param, grad, exp_avg, exp_avg_sq, decay_mask, param_bf16, n, lr_dev, step_dev)) return rc;
+    PK_REQUIRE(ema && ((uintptr_t)ema & 15) == 0, "pk_adamw_step_ema: ema is null or not 16-byte aligned");
+    PK_REQUIRE((uintptr_t)ema >= (uintptr_t)(param + n) || (uintptr_t)(ema + n) <= (uintptr_t)param,
+               "pk_adamw_step_ema: ema overlaps param (the average needs a buffer of its own)");
+    PK_REQUIRE(ema_decay > 0.f && ema_decay < 1.f, "pk_adamw_step_ema: ema_decay=%g must be finite and in (0, 1)",  // false for NaN too
+               (double)ema_decay);
+    PK_REQUIRE(((uintptr_t)guard_state & 3) == 0, "pk_adamw_step_ema: guard_state is misaligned");
+    hipLaunchKernelGGL(k_adamw_ema, dim3((unsigned)optim_blocks(n)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq,
+                       decay_mask, param_bf16, n, lr_dev, step_dev, beta1, beta2, eps, weight_decay, grad_scale, guard_state, ema,
+                       ema_decay);
+    return pk_launch_status("pk_adamw_step_ema");
 }

@@ -10,6 +10,7 @@ Semantics follow train.py:55-128: AdamW(lr 5e-4, betas (.9,.999), wd .01 on the 
 contains 'bias' / 'bn' / 'norm' are not decayed; parameters that never receive a gradient (41 tensors for
 HRFormer-small) are left untouched exactly as torch.optim.AdamW skips `grad is None`.
 """
+import contextlib
 import math
 import os
 from typing import Dict, List, Optional
@@ -37,22 +38,39 @@ def lr_factor(it: int, iters_per_epoch: int, cfg_train) -> float:
     return f
 
 
+def checkpoint_weights(ckpt, ema=False):
+    """The model state dict of a train.py checkpoint: the raw weights, or with `ema` the averaged ones a run with `--ema` saved."""
+    key = "ema_state_dict" if ema else "model_state_dict"
+    if key not in ckpt:
+        hint = " (it was not trained with train.py --ema)" if ema else ""
+        raise KeyError(f"the checkpoint has no '{key}'{hint}; its keys: {sorted(ckpt)}")
+    return ckpt[key]
+
+
 class FlatAdamW:
     """Owns the flat buffers of `model` and applies the fused optimiser step."""
 
     ALIGN = 4            # elements: every tensor starts 16-byte aligned inside the flat buffers
 
     def __init__(self, model: torch.nn.Module, lr=5e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, direct_grads=False,
-                 clip_grad_norm=0.0, skip_nonfinite=False):
+                 clip_grad_norm=0.0, skip_nonfinite=False, ema_decay=0.0):
         """`clip_grad_norm` > 0 (torch.nn.utils.clip_grad_norm_'s max_norm) or `skip_nonfinite` select the guarded step: the global
         gradient norm is reduced on the device, the update is scaled by the clip coefficient and dropped as a whole when a gradient is
-        inf / NaN (what GradScaler.step does in the reference).  A non-finite norm cannot clip anything, so clipping implies skipping."""
+        inf / NaN (what GradScaler.step does in the reference).  A non-finite norm cannot clip anything, so clipping implies skipping.
+
+        `ema_decay` in (0, 1) keeps an exponential moving average of the masters in `self.ema`, written by the update kernel itself
+        (pk_adamw_step_ema): e += (1 - d_t) (p_new - e) with d_t = min(ema_decay, (1 + t) / (10 + t)), t = applied updates.  It moves
+        only when the masters do (a skipped step freezes it), and only on the elements the optimiser updates.  0 = off: no buffer, and
+        the launches are the ones above."""
         if not (math.isfinite(clip_grad_norm) and clip_grad_norm >= 0):
             raise ValueError(f"clip_grad_norm must be finite and >= 0 (0 = off), got {clip_grad_norm}")
+        if not (math.isfinite(ema_decay) and 0 <= ema_decay < 1):
+            raise ValueError(f"ema_decay must be finite and in [0, 1) (0 = off), got {ema_decay}")
         self.model = model
         self.direct_grads = direct_grads
         self.clip_grad_norm = float(clip_grad_norm)
         self.guarded = self.clip_grad_norm > 0 or bool(skip_nonfinite)
+        self.ema_decay = float(ema_decay)
         named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
         if not named:
             raise ValueError("model has no trainable parameters")
@@ -85,6 +103,8 @@ class FlatAdamW:
             # static buffers (a captured graph holds their addresses): per-workgroup partial sums, and the record the update reads
             self.guard_partials = torch.zeros(hipops.grad_sumsq_partials(off), 2, dtype=torch.float64, device=dev)
             self.guard_state = torch.zeros(hipops.GUARD_STATE_WORDS, dtype=torch.int32, device=dev)
+        # static as well: the averaged weights, starting as a copy of the masters (padding and inactive elements keep that copy)
+        self.ema = self.flat.clone() if self.ema_decay > 0 else None
 
     # -- gradient storage ---------------------------------------------------------------------------------
     def grad_view(self, i):
@@ -148,18 +168,69 @@ class FlatAdamW:
             # the finalize kernel advances step_dev, and only when the update is applied
             hipops.grad_sumsq(self.grad, self.flags, self.guard_partials)
             hipops.grad_guard_finalize(self.guard_partials, grad_scale, self.clip_grad_norm, self.guard_state, self.step_dev)
+        else:
+            self.step_dev.add_(1)
+        if self.ema is not None:
+            # update and average in one pass; the kernel reads the skip decision and the step count where the update reads them
+            hipops.adamw_step_ema(self.flat, self.grad, self.exp_avg, self.exp_avg_sq, self.flags, None, self.lr_dev, self.step_dev,
+                                  self.betas[0], self.betas[1], self.eps, self.weight_decay, self.guard_state if self.guarded else None,
+                                  self.ema, self.ema_decay, grad_scale)
+        elif self.guarded:
             hipops.adamw_step_guarded(self.flat, self.grad, self.exp_avg, self.exp_avg_sq, self.flags, None, self.lr_dev, self.step_dev,
                                       self.betas[0], self.betas[1], self.eps, self.weight_decay, self.guard_state, grad_scale)
         else:
-            self.step_dev.add_(1)
             hipops.adamw_step(self.flat, self.grad, self.exp_avg, self.exp_avg_sq, self.flags, None, self.lr_dev, self.step_dev,
                               self.betas[0], self.betas[1], self.eps, self.weight_decay, grad_scale)
+        self._masters_rewritten()
+
+    def _masters_rewritten(self):
         wc = getattr(self.model, "_pk_weight_cache", None)
         if wc is not None:
             wc.mark_dirty()          # the kernel rewrote the fp32 masters behind torch's back: bf16 copies are stale
         tw = getattr(self.model, "_pk_twin", None)
         if tw:
             tw.mark_dirty()          # ... and so is the padded twin's embedded copy
+
+    # -- weight EMA --------------------------------------------------------------------------------------------
+    def _need_ema(self, who):
+        if self.ema is None:
+            raise RuntimeError(f"{who}: the weight EMA is off (ema_decay=0)")
+
+    def reset_ema(self):
+        """ema <- flat: after the masters were replaced from outside (initial broadcast, a checkpoint without averaged weights)."""
+        self._need_ema("reset_ema")
+        self.ema.copy_(self.flat)
+
+    def ema_state_dict(self):
+        """The model's state dict with the averaged value of every tensor that lives in the flat buffer.  Everything else (BatchNorm
+        running statistics and counters, other buffers, tensors that do not train) is the live model's current value: running
+        statistics are moving averages already, so they are copied, not averaged a second time."""
+        self._need_ema("ema_state_dict")
+        sd = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
+        for n, p, o in zip(self.names, self.params, self.offsets):
+            if n in sd:
+                sd[n] = self.ema[o:o + p.numel()].view_as(p).clone()
+        return sd
+
+    def load_ema_state_dict(self, sd):
+        """Fill the EMA buffer from a model-style state dict (ema_state_dict's); entries for tensors outside the flat buffer are ignored
+        (they belong to the model's own state dict)."""
+        self._need_ema("load_ema_state_dict")
+        missing = [n for n in self.names if n not in sd]
+        if missing:
+            raise KeyError(f"load_ema_state_dict: no entry for {missing[:5]}{' ...' if len(missing) > 5 else ''}")
+        for n, p, o in zip(self.names, self.params, self.offsets):
+            if tuple(sd[n].shape) != tuple(p.shape):
+                raise ValueError(f"load_ema_state_dict: {n} has shape {tuple(sd[n].shape)}, the model's is {tuple(p.shape)}")
+            self.ema[o:o + p.numel()].copy_(sd[n].reshape(-1))
+
+    def swap_ema(self):
+        """Exchange the CONTENTS of flat and ema: captured graphs and every param.data view hold flat's address, so pointers stay."""
+        self._need_ema("swap_ema")
+        tmp = self.flat.clone()
+        self.flat.copy_(self.ema)
+        self.ema.copy_(tmp)
+        self._masters_rewritten()
 
     def guard_stats(self):
         """Last step's gradient norm (after grad_scale, before clipping), clip coefficient, whether it was skipped, and the number of
@@ -371,7 +442,8 @@ class Trainer:
     each replay, so the per-iteration schedule advances normally.  Batches are copied into static input buffers."""
 
     def __init__(self, model, cfg, iters_per_epoch: int, bucket_mb: float = 8.0, use_graph: bool = False, graph_warmup: int = 3,
-                 overlap_comm: bool = True, graph_streams: bool = False, clip_grad_norm: float = 0.0, skip_nonfinite: bool = False):
+                 overlap_comm: bool = True, graph_streams: bool = False, clip_grad_norm: float = 0.0, skip_nonfinite: bool = False,
+                 ema_decay: float = 0.0):
         self.model, self.cfg = model, cfg
         self.overlap_comm = overlap_comm
         # concurrent branch streams: on for eager steps; inside a captured graph only on request (fork/join capture across
@@ -386,10 +458,14 @@ class Trainer:
         # optimiser between forward+backward-only replays all take it; the LR schedule advances on skipped steps too (as the
         # reference's scheduler.step() does)
         self.opt = FlatAdamW(model, t.lr, tuple(t.betas), 1e-8, t.weight_decay, direct_grads=True, clip_grad_norm=clip_grad_norm,
-                             skip_nonfinite=skip_nonfinite)
+                             skip_nonfinite=skip_nonfinite, ema_decay=ema_decay)
         self.sched = WarmupMultiStepLR(self.opt, t, iters_per_epoch)
         self.comm = GradientExchange(self.opt, bucket_mb, overlap=overlap_comm)
         self.comm.broadcast_initial_state()
+        if self.opt.ema is not None:
+            # every rank starts its average from the broadcast weights; from here on the ranks average identical masters with
+            # identical arithmetic, so the average needs no collective
+            self.opt.reset_ema()
         self._ms_cb = None
         if self.comm.world > 1 and overlap_comm:
             self._ms_cb = self._milestone
@@ -524,6 +600,22 @@ class Trainer:
             self.opt.step(self.comm.grad_scale)
         self.sched.step()
         return self._static_out
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Evaluate under the averaged weights: waits for the step's stream, exchanges the contents of the masters and the average, and
+        puts the model in eval mode; on exit (also by an exception) exchanges them back and restores the train/eval mode.  Usable between
+        graph replays: the captured graph holds addresses, and only contents move."""
+        if self._stream is not None:
+            torch.cuda.current_stream().wait_stream(self._stream)
+        was_training = self.model.training
+        self.opt.swap_ema()
+        self.model.eval()
+        try:
+            yield self.model
+        finally:
+            self.opt.swap_ema()
+            self.model.train(was_training)
 
     def step(self, batch):
         from . import dispatch

@@ -814,3 +814,15 @@ def adamw_step_guarded(param, grad, exp_avg, exp_avg_sq, flags, param_bf16, lr_d
     _chk_guard_state(guard_state)
     call("pk_adamw_step_guarded", param, grad, exp_avg, exp_avg_sq, flags, param_bf16, param.numel(), lr_dev, step_dev, float(beta1),
          float(beta2), float(eps), float(weight_decay), float(grad_scale), guard_state, stream_ptr())
+
+
+def adamw_step_ema(param, grad, exp_avg, exp_avg_sq, flags, param_bf16, lr_dev, step_dev, beta1, beta2, eps, weight_decay, guard_state, ema,
+                   ema_decay, grad_scale=1.0):
+    """The plain (guard_state None) or guarded update, and in the same pass ema += (1 - d_t) * (param_new - ema) on the elements that were
+    updated; d_t = min(ema_decay, (1 + t) / (10 + t)) is worked out on the device from step_dev.  A skipped step leaves `ema` alone too."""
+    if guard_state is not None:
+        _chk_guard_state(guard_state)
+    if _chk(ema, name="ema").numel() != param.numel() or not ema.is_contiguous():
+        raise _lib.PoseKernelError(f"adamw_step_ema: ema must be a contiguous buffer of {param.numel()} floats (updated in place)")
+    call("pk_adamw_step_ema", param, grad, exp_avg, exp_avg_sq, flags, param_bf16, param.numel(), lr_dev, step_dev, float(beta1),
+         float(beta2), float(eps), float(weight_decay), float(grad_scale), guard_state, ema, float(ema_decay), stream_ptr())

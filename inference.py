@@ -30,6 +30,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from infantposeestimation_gaussianbias_amd.configs import get_config  # noqa: E402
 from infantposeestimation_gaussianbias_amd.configs.config import check_decode, check_test_scales  # noqa: E402
+from infantposeestimation_gaussianbias_amd.engine import checkpoint_weights  # noqa: E402
 from infantposeestimation_gaussianbias_amd.datasets.transforms import DeviceCropper, get_affine_matrix, multiscale_matrices  # noqa: E402
 from infantposeestimation_gaussianbias_amd.models import build_model  # noqa: E402
 from infantposeestimation_gaussianbias_amd.utils.metrics import movement_heatmap, movement_report  # noqa: E402
@@ -43,7 +44,7 @@ class PoseInference:
     modulate_kernel = 11
 
     def __init__(self, checkpoint: Optional[str] = None, device: str = 'cuda', flip_test: bool = True, config: Optional[str] = None,
-                 scales=None, decode: Optional[str] = None, modulate_kernel: Optional[int] = None):
+                 scales=None, decode: Optional[str] = None, modulate_kernel: Optional[int] = None, ema: bool = False):
         if not torch.cuda.is_available():
             raise RuntimeError("PoseInference needs an MI355X: the hot path has no CPU implementation")
         self.device = torch.device(device)
@@ -56,8 +57,9 @@ class PoseInference:
         self.model = build_model(self.cfg).to(self.device).eval()
         if checkpoint and os.path.isfile(checkpoint):
             ckpt = torch.load(checkpoint, map_location="cpu", weights_only=True)
-            self.model.load_state_dict(ckpt['model_state_dict'])
-            print(f'Loaded checkpoint: {checkpoint}')
+            # ema: the averaged weights a `train.py --ema` run saved next to the raw ones (an error if the checkpoint has none)
+            self.model.load_state_dict(checkpoint_weights(ckpt, ema=ema))
+            print(f'Loaded checkpoint: {checkpoint}' + (' (averaged weights)' if ema else ''))
         self.input_size = self.cfg.data.input_size          # (w, h)
         self.flip_pairs = self.cfg.data.flip_pairs
         self._crop = DeviceCropper(self.input_size, self.device, nchw=True, nhwc8=False)
@@ -285,7 +287,7 @@ def main(args):
     if getattr(args, "freq_band", None) is not None and args.fps is None:
         build_parser().error("--freq_band is in Hz and needs --fps")
     pose = PoseInference(checkpoint=args.checkpoint, device=args.device, flip_test=not args.no_flip, config=args.config, scales=args.scales,
-                         decode=args.decode, modulate_kernel=args.modulate_kernel)
+                         decode=args.decode, modulate_kernel=args.modulate_kernel, ema=getattr(args, "ema", False))
     if getattr(args, "sequence", False):
         return main_sequence(args, pose)
     rgb = np.asarray(Image.open(args.input).convert("RGB"))
@@ -346,6 +348,8 @@ def build_parser():
                         'decode; none: shift)')
     p.add_argument('--modulate_kernel', type=int, default=None, metavar='K',
                    help='--decode unbiased: taps of the Gaussian smoothing, odd, 3 to 31 (default: the config\'s modulate_kernel, 11)')
+    p.add_argument('--ema', action='store_true',
+                   help='load the averaged weights (the checkpoint\'s ema_state_dict, saved by train.py --ema) instead of model_state_dict')
     return p
 
 

@@ -8,9 +8,11 @@ Differences from the reference loop (train.py:131-228): no per-step `loss.item()
 log interval), bf16 instead of fp16+GradScaler, fused AdamW over a flat parameter buffer, optional hipGraph replay
 (`--graph`), GradScaler's "drop the step when a gradient is inf/NaN" and gradient-norm clipping as an opt-in device-side guard
 (`--skip_nonfinite`, `--clip_grad_norm X`), colour jitter on the device (`--color_jitter B C S`, or DATA.COLOR_JITTER of a legacy
-yaml).  With POSE_SYNTHETIC=1 the loader yields device-resident synthetic batches (no COCO on disk needed; they are not jittered).
+yaml), and an exponential moving average of the weights kept by the optimiser kernel (`--ema DECAY`): validation inside the loop then
+scores the averaged weights, and checkpoints carry them as "ema_state_dict" (validate.py / inference.py `--ema` load them).  With POSE_SYNTHETIC=1 the loader yields device-resident synthetic batches (no COCO on disk needed; they are not jittered).
 """
 import argparse
+import contextlib
 import copy
 import logging
 import os
@@ -38,10 +40,13 @@ def set_seed(seed: int):
 
 
 def save_checkpoint(model, trainer, epoch, metrics, output_dir, is_best=False):
-    """Same dict as the reference (train.py:351-357); optimizer state is exported in torch.optim.AdamW's format."""
+    """Same dict as the reference (train.py:351-357); optimizer state is exported in torch.optim.AdamW's format.  With the weight EMA on,
+    and only then, two more keys: the averaged weights as a model state dict, and the decay."""
     os.makedirs(output_dir, exist_ok=True)
     ckpt = {"epoch": epoch, "model_state_dict": model.state_dict(), "optimizer_state_dict": trainer.opt.state_dict(),
             "scheduler_state_dict": trainer.sched.state_dict(), "metrics": metrics}
+    if trainer.opt.ema is not None:
+        ckpt["ema_state_dict"], ckpt["ema_decay"] = trainer.opt.ema_state_dict(), trainer.opt.ema_decay
     torch.save(ckpt, os.path.join(output_dir, "latest.pth"))
     if is_best:
         torch.save(ckpt, os.path.join(output_dir, "best.pth"))
@@ -88,6 +93,8 @@ def main(args):
         cfg.train.color_jitter = tuple(args.color_jitter)
     if args.color_jitter_prob is not None:
         cfg.train.color_jitter_prob = args.color_jitter_prob
+    if args.ema is not None:
+        cfg.train.ema_decay = args.ema
     world, rank, local = int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0))
     torch.cuda.set_device(local)
     if world > 1:
@@ -99,13 +106,20 @@ def main(args):
     loader = build_dataloader(cfg, is_train=True)
     model = build_model(cfg).to(torch.device("cuda", local))
     trainer = engine.Trainer(model, cfg, iters_per_epoch=len(loader), use_graph=args.graph, graph_streams=args.graph,
-                             clip_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite)
+                             clip_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite, ema_decay=cfg.train.ema_decay or 0.0)
     start_epoch, best_ap = 0, 0.0
     if args.resume and os.path.isfile(args.resume):
         ckpt = torch.load(args.resume, map_location="cpu", weights_only=True)
         model.load_state_dict(ckpt["model_state_dict"])
         trainer.opt.load_state_dict(ckpt["optimizer_state_dict"])
         trainer.sched.load_state_dict(ckpt["scheduler_state_dict"])
+        if trainer.opt.ema is not None:
+            # load_state_dict above rewrote the masters through the parameter views: the average taken at construction is stale
+            if "ema_state_dict" in ckpt:
+                trainer.opt.load_ema_state_dict(ckpt["ema_state_dict"])
+            else:
+                trainer.opt.reset_ema()
+                logger.info("Checkpoint has no ema_state_dict: the weight EMA restarts from the loaded weights")
         start_epoch, best_ap = ckpt["epoch"] + 1, ckpt.get("metrics", {}).get("AP", 0.0)
         logger.info(f"Resumed from epoch {start_epoch}")
     val_loader = None
@@ -119,7 +133,9 @@ def main(args):
                 val_cfg.test_scales = None           # this monitor stays single-scale and un-flipped; validate.py runs the multi-scale test
                 val_loader = build_dataloader(val_cfg, is_train=False)
             # the heatmap decode follows the config (cfg.decode / cfg.modulate_kernel); a config that names none keeps the quarter-pixel shift
-            metrics, _ = validate(model, val_loader, torch.device("cuda", local), cfg, logger, flip_test=False)
+            # with the weight EMA on, the averaged weights are the ones scored (and so the ones that pick best.pth)
+            with trainer.ema_weights() if trainer.opt.ema is not None else contextlib.nullcontext():
+                metrics, _ = validate(model, val_loader, torch.device("cuda", local), cfg, logger, flip_test=False)
             model.train()
             is_best = metrics["AP"] > best_ap
             best_ap = max(best_ap, metrics["AP"])
@@ -154,6 +170,9 @@ def build_parser():
                    help="clip the global gradient norm to X on the device (torch.nn.utils.clip_grad_norm_; 0 = off); implies --skip_nonfinite")
     p.add_argument("--skip_nonfinite", action="store_true",
                    help="drop the whole optimiser step when a gradient is inf or NaN (what GradScaler.step does in the reference)")
+    p.add_argument("--ema", type=float, default=None, metavar="DECAY",
+                   help="keep an exponential moving average of the weights in the optimiser kernel (e.g. 0.9998; warm-up "
+                        "min(DECAY, (1+t)/(10+t))); validation and best.pth use the averaged weights (default: off)")
     return p
 
 

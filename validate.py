@@ -5,7 +5,8 @@ multi-scale test: predictions from `PoseEstimator.inference_multiscale` over the
 plus --bbox_file / --det_score_thr / --oks_nms THR / --soft_nms / --in_vis_thr for the detector-box protocol: crops from a person-detection
 file instead of the ground-truth boxes, every pose rescored as box score x mean confident keypoint score, duplicate poses removed per image
 by OKS-NMS on the device, then AP; plus --decode {shift,unbiased} / --modulate_kernel K for the heatmap decode of the heatmap-head models:
-the quarter-pixel shift (the default) or the unbiased, distribution-aware step on the log of the smoothed map).
+the quarter-pixel shift (the default) or the unbiased, distribution-aware step on the log of the smoothed map); plus --ema to score the
+averaged weights of a checkpoint written by `train.py --ema`).
 
 Flip-test inference + decode run entirely on the GPU (`PoseEstimator.inference`: two forwards, one flip-merge kernel, one
 decode kernel); the heat-px -> image transform of validate.py:100-117 is one kernel (`heatmap_to_image_coords`) instead of a
@@ -24,6 +25,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from infantposeestimation_gaussianbias_amd.configs import get_config  # noqa: E402
 from infantposeestimation_gaussianbias_amd.configs.config import check_decode, check_test_scales  # noqa: E402
+from infantposeestimation_gaussianbias_amd.engine import checkpoint_weights  # noqa: E402
 from infantposeestimation_gaussianbias_amd.datasets import build_dataloader  # noqa: E402
 from infantposeestimation_gaussianbias_amd.models import build_model  # noqa: E402
 from infantposeestimation_gaussianbias_amd.utils import AverageMeter  # noqa: E402
@@ -136,8 +138,8 @@ def main(args):
     loader = build_dataloader(cfg, is_train=False)
     model = build_model(cfg).to(device)
     ckpt = torch.load(args.checkpoint, map_location="cpu", weights_only=True)
-    model.load_state_dict(ckpt["model_state_dict"])
-    logger.info(f"Loaded checkpoint from epoch {ckpt.get('epoch', 'unknown')}")
+    model.load_state_dict(checkpoint_weights(ckpt, ema=getattr(args, "ema", False)))
+    logger.info(f"Loaded checkpoint from epoch {ckpt.get('epoch', 'unknown')}" + (" (averaged weights)" if getattr(args, "ema", False) else ""))
     # --pck alone: the config's pck_threshold; --pck THR ...: those; no flag: PCK only when the config's yaml names it among EVAL.METRICS
     pck_thresholds = None
     if getattr(args, "pck", None) is not None:
@@ -193,6 +195,8 @@ def build_parser():
                         "the log of the smoothed map (default: the config's decode; none: shift)")
     p.add_argument("--modulate_kernel", type=int, default=None, metavar="K",
                    help="--decode unbiased: taps of the Gaussian smoothing, odd, 3 to 31 (default: the config's modulate_kernel, 11)")
+    p.add_argument("--ema", action="store_true",
+                   help="score the averaged weights (the checkpoint's ema_state_dict, saved by train.py --ema) instead of model_state_dict")
     return p
 
 
