@@ -273,6 +273,21 @@ int pk_pixel_loss_fwd(const float* pred, const float* target, const float* weigh
                       int B, int K, int HW, int kind, void* stream);
 int pk_pixel_loss_bwd(const float* pred, const float* target, const float* weight, const float* grad_out,
                       float* d_pred, int B, int K, int HW, int kind, void* stream);
+/* Online hard keypoint mining (CPN; HRNet's JointsOHKMMSELoss, mmpose's KeypointOHKMMSELoss): per sample only the `topk` maps with the
+ * largest error count.  L[b,k] = (1/HW) sum_i (w[b,k] (pred - target))^2;  selected: the topk largest L of the sample in torch.topk's
+ * order (descending, a NaN before every number, equal values and NaNs among themselves by lower joint index);
+ * mask[b,k] = 1 for the selected maps;  loss = scale / (B topk) * sum of the selected L;  counts[k] += sum_b mask[b,k] (counts may be NULL).
+ * d_pred = mask * G * scale * 2 w^2 (pred - target) / (HW topk B), zero (and stored) for unselected maps; nothing flows through the
+ * selection.  weight (B,K) or NULL = 1; a map with w = 0 has L = 0, may be selected when fewer than topk are non-zero, and adds nothing.
+ * topk = K is the plain weighted mean (pixel loss kind 0 times scale).  Refused before any launch: a null required pointer, B or HW <= 0,
+ * K outside 1..PK_OHKM_MAX_K, topk outside 1..K, a scale that is not finite and positive.  Three launches in all (per-map sums, a
+ * one-workgroup selection, the gradient), no atomics, no host synchronisation: the same input gives the same bits.               */
+#define PK_OHKM_MAX_K 256
+int pk_ohkm_loss_fwd(const float* pred, const float* target, const float* weight /* (B,K) or NULL = 1 */,
+                     float* per_map /* (B,K) out */, uint8_t* mask /* (B,K) out */, float* loss /* 1 out */,
+                     int64_t* counts /* (K) in/out, or NULL */, int B, int K, int HW, int topk, float scale, void* stream);
+int pk_ohkm_loss_bwd(const float* pred, const float* target, const float* weight, const uint8_t* mask,
+                     const float* grad_out /* 1, or NULL = 1 */, float* d_pred, int B, int K, int HW, int topk, float scale, void* stream);
 /* MorphologyShapeLoss statistics (models/losses.py:69-104): mean (BK,2), variance (BK,2) of hm/(sum+1e-8) */
 int pk_spatial_stats(const float* heatmaps, float* mean, float* var, int BK, int H, int W, void* stream);
 /* backward of pk_spatial_stats (MorphologyShapeLoss, models/losses.py:50-135): grad_mean / grad_var (BK,2) -> grad_heatmaps */

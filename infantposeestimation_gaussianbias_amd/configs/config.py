@@ -16,6 +16,8 @@ identically.  Extension over the reference: `get_config(path_or_name)` also acce
     heatmap-head models; a bad value raises and names the key).  `TEST.POST_PROCESS` and `TEST.SHIFT_HEATMAP` are deliberately NOT mapped:
     both shipped yamls set them true, and mapping them would change what those configurations do today.  `CLINICAL.FREQUENCY_BAND:
     [lo, hi]` (Hz; this project's own key) maps onto `cfg.frequency_band`, the band of the movement spectrum; a bad value names the key.
+    `LOSS.USE_OHKM` / `LOSS.TOPK` (HRNet's keys; TOPK defaults to 8) / `LOSS.OHKM_WEIGHT` map onto `cfg.model.ohkm_topk` /
+    `cfg.model.ohkm_weight` (online hard keypoint mining; off unless USE_OHKM is true).
 """
 import logging
 import math
@@ -61,6 +63,11 @@ class ModelConfig:
     overlap_loss_weight: float = 0.05
     shape_loss_weight: float = 0.05
     target_sigma: float = 2.0
+    # Online hard keypoint mining (legacy yaml LOSS.USE_OHKM / LOSS.TOPK / LOSS.OHKM_WEIGHT, `train.py --ohkm TOPK --ohkm_weight W`): 0 (off)
+    # or the number of worst-fitted joints per sample that count in the heatmap loss, and the weight of that term in the fusion loss.  Plain
+    # class attributes like TrainConfig.color_jitter: the field set stays the reference's.
+    ohkm_topk = 0
+    ohkm_weight = 1.0
 
 
 @dataclass
@@ -191,6 +198,28 @@ def check_frequency_band(band, what="frequency_band") -> Tuple[float, float]:
     return lo, hi
 
 
+def check_ohkm(topk, weight=1.0, num_keypoints=None, allow_off=True, what=("ohkm_topk", "ohkm_weight")):
+    """The settings of online hard keypoint mining as (int topk, float weight): `topk` an integer from 1 to `num_keypoints` (to the
+    kernels' 256 where the number of joints is not known yet), or 0 = off where `allow_off`; `weight` finite and >= 0.  ValueError naming
+    `what` (the argument, key or flag the value came from) otherwise."""
+    hi = 256 if num_keypoints is None else int(num_keypoints)
+    try:
+        k = int(topk)
+        ok = not isinstance(topk, bool) and k == topk and ((allow_off and k == 0) or 1 <= k <= hi)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"{what[0]} must be an integer from 1 to {hi}" + (" (or 0 = off)" if allow_off else "") + f", got {topk!r}")
+    try:
+        w = float(weight)
+        ok = not isinstance(weight, (bool, str)) and math.isfinite(w) and w >= 0
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"{what[1]} must be finite and >= 0, got {weight!r}")
+    return k, w
+
+
 def _apply_preset(cfg: Config, name: str) -> Config:
     bb, head, ch, insz, hmsz, K, sigma = _PRESETS[name]
     cfg.model.backbone, cfg.model.head_type = bb, head
@@ -241,6 +270,12 @@ def _apply_legacy_yaml(cfg: Config, path: str) -> Config:
         # not the identity (u / 255 * 255 truncates)
         rng = tuple(float((cj or {}).get(k, 0) or 0) for k in ('BRIGHTNESS', 'CONTRAST', 'SATURATION'))
         cfg.train.color_jitter = rng if any(rng) else None
+    # LOSS.USE_OHKM / LOSS.TOPK are HRNet's own keys (TOPK defaults to its 8); LOSS.OHKM_WEIGHT weighs the term in the fusion loss.  A yaml
+    # without USE_OHKM: true keeps mining off whatever else the block holds
+    ls = y.get('LOSS', {}) or {}
+    if ls.get('USE_OHKM'):
+        cfg.model.ohkm_topk, cfg.model.ohkm_weight = check_ohkm(ls.get('TOPK', 8), ls.get('OHKM_WEIGHT', ModelConfig.ohkm_weight),
+                                                                cfg.model.num_keypoints, False, ('LOSS.TOPK', 'LOSS.OHKM_WEIGHT'))
     adv = y.get('ADVANCED', {}) or {}
     if adv.get('MULTI_SCALE_TEST'):
         sl = adv.get('SCALE_LIST')

@@ -390,6 +390,188 @@ extern "C" int pk_pixel_loss_bwd(const float* pred, const float* target, const f
     return pk_launch_status("pk_pixel_loss_bwd");
 }
 
+// ================================================================================================ online hard keypoint mining
+// L[b,k] = mean_i (w (p - t))^2 per map; per sample the `topk` maps with the largest L count: loss = scale / (B topk) * sum of the selected L.
+// Three launches, no atomics, no arrival counters: the same input gives the same bits, eagerly or replayed.
+//   k_ohkm_map    one workgroup per map: strided fp32 partials + block_sum, like k_floss_map; 16-byte loads when `vec`
+//   k_ohkm_final  one workgroup: every (sample, joint) pair ranks itself within its sample, then the sums in a fixed order, then the counts
+//   k_ohkm_bwd    one workgroup per map: an unselected map is stored as zeros and its pred / target are never read
+__global__ void __launch_bounds__(256) k_ohkm_map(const float* __restrict__ pred, const float* __restrict__ tgt,
+                                                  const float* __restrict__ wt, float* __restrict__ per_map, int HW, int vec) {
+    __shared__ float red[16];
+    const int map = blockIdx.x;
+    const float w = wt ? wt[map] : 1.f;
+    const float* p = pred + (size_t)map * HW;
+    const float* t = tgt + (size_t)map * HW;
+    float acc = 0.f;
+    if (vec) {       // HW % 4 == 0 and both tensors start on a 16-byte boundary: so does every map
+        const f32x4* p4 = (const f32x4*)p;
+        const f32x4* t4 = (const f32x4*)t;
+        // four 16-byte loads of each tensor in flight per thread: at 13 x 24 maps of 128 x 128 there are barely more workgroups than
+        // CUs, and one load pair at a time leaves the kernel waiting on latency (measured: DESIGN.md "Hard keypoint mining")
+        const int n4 = HW / 4;
+        for (int i0 = threadIdx.x; i0 < n4; i0 += 4 * 256) {
+            f32x4 a[4], b[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int i = i0 + u * 256;
+                if (i < n4) {
+                    a[u] = p4[i];
+                    b[u] = t4[i];
+                } else {
+                    a[u] = b[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float d = (a[u][j] - b[u][j]) * w;
+                    acc += d * d;
+                }
+        }
+    } else {
+        for (int i = threadIdx.x; i < HW; i += blockDim.x) {
+            const float d = (p[i] - t[i]) * w;
+            acc += d * d;
+        }
+    }
+    acc = block_sum(acc, red);
+    if (threadIdx.x == 0) per_map[map] = acc / (float)HW;
+}
+
+// The ranking of torch.topk -- a NaN before every number, larger before smaller, equal values (and NaNs among themselves) by lower index --
+// as ONE unsigned comparison: the value's bits made monotone (sign flipped for positive numbers, every bit for negative ones; -0 counts
+// as +0; every NaN becomes the largest key) in the high word, K - 1 - index ... i.e. the complement of the index in the low word.  The
+// keys of one sample are distinct, so "how many keys of my sample are larger than mine" is a permutation of 0..K-1: map (b,k) is
+// selected iff that rank is below topk.  No scan depends on the one before it, so all 256 threads work whatever B is.  (The first version
+// let thread b pick sample b's maps one after the other, topk scans of K values: 64 busy lanes at B = 64, and the serial compare chain,
+// not memory, was most of the loss's time -- staging the rows in LDS changed nothing.  Numbers: DESIGN.md "Hard keypoint mining".)
+__device__ __forceinline__ unsigned long long ohkm_key(float v, int k) {
+    uint32_t bits = __float_as_uint(v);
+    bits = (v != v) ? 0xffffffffu : (v == 0.f) ? 0x80000000u : (bits & 0x80000000u) ? ~bits : (bits | 0x80000000u);
+    return ((unsigned long long)bits << 32) | (uint32_t)(0xffffffffu - (uint32_t)k);
+}
+
+#define OHKM_TILE 4096   // (sample, joint) pairs per tile: 32 KB of keys and 4 KB of selection bytes in LDS; K <= 256, so >= 16 samples
+__global__ void __launch_bounds__(256) k_ohkm_final(const float* __restrict__ per_map, uint8_t* __restrict__ mask, float* __restrict__ loss,
+                                                    int64_t* __restrict__ counts, int B, int K, int topk, float scale) {
+    __shared__ unsigned long long keys[OHKM_TILE];
+    __shared__ uint8_t sel[OHKM_TILE];
+    __shared__ double red[256];
+    const int tid = threadIdx.x, tile_b = OHKM_TILE / K;
+    // the sums are taken in double: a few hundred values, and the loss then carries the rounding of the per-map errors and one more.
+    // Pair i of a tile always belongs to thread i % 256, and the partial sums meet in a fixed tree: the same bits every time.
+    double acc = 0.0;
+    int64_t cnt = 0;
+    for (int b0 = 0; b0 < B; b0 += tile_b) {
+        const int nb = min(tile_b, B - b0), n = nb * K;
+        const float* L = per_map + (size_t)b0 * K;
+        uint8_t* m = mask + (size_t)b0 * K;
+        for (int i = tid; i < n; i += 256) keys[i] = ohkm_key(L[i], i % K);
+        __syncthreads();
+        for (int i = tid; i < n; i += 256) {
+            const unsigned long long mine = keys[i];
+            const unsigned long long* row = keys + (i / K) * K;
+            int rank = 0;
+            for (int j = 0; j < K; ++j) rank += row[j] > mine ? 1 : 0;
+            const uint8_t s = rank < topk ? 1 : 0;
+            sel[i] = s;
+            m[i] = s;
+            if (s) acc += (double)L[i];
+        }
+        __syncthreads();
+        if (tid < K)
+            for (int b = 0; b < nb; ++b) cnt += sel[b * K + tid];
+        __syncthreads();         // the next tile overwrites keys and sel
+    }
+    red[tid] = acc;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) red[tid] += red[tid + o];
+        __syncthreads();
+    }
+    if (tid == 0) loss[0] = (float)((double)scale / ((double)B * (double)topk) * red[0]);
+    if (counts && tid < K) counts[tid] += cnt;
+}
+
+__global__ void __launch_bounds__(256) k_ohkm_bwd(const float* __restrict__ pred, const float* __restrict__ tgt,
+                                                  const float* __restrict__ wt, const uint8_t* __restrict__ mask,
+                                                  const float* __restrict__ gout, float* __restrict__ dp, int HW, int vec, double coef) {
+    // coef = scale * 2 / (HW topk B);  d_pred = (G coef w^2) (p - t): the factor rounded once, one subtraction, one product
+    const int map = blockIdx.x;
+    float* d = dp + (size_t)map * HW;
+    if (!mask[map]) {        // workgroup-uniform
+        if (vec) {
+            f32x4* d4 = (f32x4*)d;
+            for (int i = threadIdx.x; i < HW / 4; i += blockDim.x) d4[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        } else {
+            for (int i = threadIdx.x; i < HW; i += blockDim.x) d[i] = 0.f;
+        }
+        return;
+    }
+    const double w = wt ? (double)wt[map] : 1.0;
+    const float c = (float)((gout ? (double)gout[0] : 1.0) * coef * w * w);
+    const float* p = pred + (size_t)map * HW;
+    const float* t = tgt + (size_t)map * HW;
+    if (vec) {
+        const f32x4* p4 = (const f32x4*)p;
+        const f32x4* t4 = (const f32x4*)t;
+        f32x4* d4 = (f32x4*)d;
+        const int n4 = HW / 4;
+        for (int i0 = threadIdx.x; i0 < n4; i0 += 4 * 256) {       // as in k_ohkm_map: four load pairs in flight
+            f32x4 a[4], b[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int i = i0 + u * 256;
+                if (i < n4) {
+                    a[u] = p4[i];
+                    b[u] = t4[i];
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int i = i0 + u * 256;
+                if (i < n4) d4[i] = (a[u] - b[u]) * c;
+            }
+        }
+    } else {
+        for (int i = threadIdx.x; i < HW; i += blockDim.x) d[i] = (p[i] - t[i]) * c;
+    }
+}
+
+static bool ohkm_aligned16(const void* a, const void* b, const void* c) {
+    return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15u) == 0;
+}
+#define PK_OHKM_CHECK(entry)                                                                                                     \
+    PK_REQUIRE(B > 0 && HW > 0, entry ": bad shape B=%d HW=%d", B, HW);                                                          \
+    PK_REQUIRE(K >= 1 && K <= PK_OHKM_MAX_K, entry ": K=%d outside 1..%d", K, PK_OHKM_MAX_K);                                    \
+    PK_REQUIRE(topk >= 1 && topk <= K, entry ": topk=%d outside 1..K=%d", topk, K);                                              \
+    PK_REQUIRE(scale > 0.f && scale <= 3.402823466e38f, entry ": scale=%g is not finite and positive", (double)scale);           \
+    PK_REQUIRE((int64_t)B * K <= 0x7fffffff, entry ": B*K=%lld maps exceed one grid", (long long)B * K)
+
+extern "C" int pk_ohkm_loss_fwd(const float* pred, const float* target, const float* weight, float* per_map, uint8_t* mask, float* loss,
+                                int64_t* counts, int B, int K, int HW, int topk, float scale, void* stream) {
+    PK_REQUIRE(pred && target && per_map && mask && loss, "pk_ohkm_loss_fwd: null pointer");
+    PK_OHKM_CHECK("pk_ohkm_loss_fwd");
+    hipStream_t st = (hipStream_t)stream;
+    const int vec = (HW % 4 == 0 && ohkm_aligned16(pred, target, nullptr)) ? 1 : 0;
+    hipLaunchKernelGGL(k_ohkm_map, dim3(B * K), dim3(256), 0, st, pred, target, weight, per_map, HW, vec);
+    hipLaunchKernelGGL(k_ohkm_final, dim3(1), dim3(256), 0, st, per_map, mask, loss, counts, B, K, topk, scale);
+    return pk_launch_status("pk_ohkm_loss_fwd");
+}
+
+extern "C" int pk_ohkm_loss_bwd(const float* pred, const float* target, const float* weight, const uint8_t* mask, const float* grad_out,
+                                float* d_pred, int B, int K, int HW, int topk, float scale, void* stream) {
+    PK_REQUIRE(pred && target && mask && d_pred, "pk_ohkm_loss_bwd: null pointer");
+    PK_OHKM_CHECK("pk_ohkm_loss_bwd");
+    const int vec = (HW % 4 == 0 && ohkm_aligned16(pred, target, d_pred)) ? 1 : 0;
+    const double coef = (double)scale * 2.0 / ((double)HW * (double)topk * (double)B);
+    hipLaunchKernelGGL(k_ohkm_bwd, dim3(B * K), dim3(256), 0, (hipStream_t)stream, pred, target, weight, mask, grad_out, d_pred, HW, vec, coef);
+    return pk_launch_status("pk_ohkm_loss_bwd");
+}
+#undef PK_OHKM_CHECK
+
 // MorphologyShapeLoss.compute_spatial_statistics: centre of mass and per-axis variance of hm/(sum+1e-8)
 __global__ void __launch_bounds__(256) k_spatial_stats(const float* __restrict__ hm, float* __restrict__ mean, float* __restrict__ var,
                                                        int H, int W) {

@@ -510,6 +510,50 @@ def pixel_loss(pred, target, weight, kind):
     return _PixelLoss.apply(pred, target, weight, int(kind))
 
 
+class _OhkmLoss(torch.autograd.Function):
+    """Online hard keypoint mining (pk_ohkm_loss_fwd / _bwd): the selection happens on the device, the mask it leaves is what backward reads."""
+
+    @staticmethod
+    def forward(ctx, pred, target, weight, topk, scale, counts):
+        pred, target = _chk(pred, name="pred"), _chk(target, name="target")
+        if pred.dim() < 3 or target.shape != pred.shape:
+            raise _lib.PoseKernelError(f"ohkm_loss: pred {tuple(pred.shape)} and target {tuple(target.shape)} must be the same (B,K,...) maps")
+        B, K = pred.shape[:2]
+        HW = pred.numel() // max(B * K, 1)
+        w = None if weight is None else _chk(weight, name="weight")
+        if w is not None and w.numel() != B * K:
+            raise _lib.PoseKernelError(f"ohkm_loss: weight has {w.numel()} elements, expected B*K = {B * K}")
+        if counts is not None:
+            _chk(counts, torch.int64, "counts")
+            if counts.shape != (K,) or not counts.is_contiguous():
+                raise _lib.PoseKernelError(f"ohkm_loss: counts must be a contiguous int64 ({K},) tensor, got {tuple(counts.shape)}")
+        per_map = torch.empty(B, K, dtype=F32, device=pred.device)
+        mask = torch.empty(B, K, dtype=torch.uint8, device=pred.device)
+        loss = torch.empty(1, dtype=F32, device=pred.device)
+        call("pk_ohkm_loss_fwd", pred, target, w, per_map, mask, loss, counts, B, K, HW, int(topk), float(scale), stream_ptr())
+        ctx.save_for_backward(pred, target, w if w is not None else pred.new_empty(0), mask)
+        ctx.topk, ctx.scale, ctx.has_w = int(topk), float(scale), w is not None
+        ctx.mark_non_differentiable(per_map, mask)
+        return loss.reshape(()), per_map, mask
+
+    @staticmethod
+    def backward(ctx, g, _g_per_map, _g_mask):
+        pred, target, w, mask = ctx.saved_tensors
+        B, K = pred.shape[:2]
+        dp = torch.empty_like(pred)
+        call("pk_ohkm_loss_bwd", pred, target, w if ctx.has_w else None, mask, _chk(g.reshape(1).float()), dp, B, K, pred.numel() // (B * K),
+             ctx.topk, ctx.scale, stream_ptr())
+        return dp, None, None, None, None, None
+
+
+def ohkm_loss(pred, target, weight, topk, scale=1.0, counts=None, return_selection=False):
+    """scale / (B topk) * sum over every sample's `topk` hardest maps of mean((w (pred - target))^2), as a scalar.  `counts`: an int64 (K,)
+    device tensor that gains the number of samples each joint was selected in.  `return_selection`: also the per-map errors (B,K) and the
+    uint8 selection mask (B,K), neither differentiable."""
+    loss, per_map, mask = _OhkmLoss.apply(pred, target, weight, topk, scale, counts)
+    return (loss, per_map, mask) if return_selection else loss
+
+
 class _SpatialStats(torch.autograd.Function):
     @staticmethod
     def forward(ctx, hm):

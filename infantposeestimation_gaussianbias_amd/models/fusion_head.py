@@ -13,6 +13,7 @@ import torch.nn as nn
 from .. import hipops
 from .. import dispatch as nnops
 from ._blocks import conv
+from .losses import HardKeypointMining
 
 
 class SoftArgmax2D(nn.Module):
@@ -172,13 +173,18 @@ class GaussianDistributionConstraint(nn.Module):
         return {"variance_loss": v[3], "overlap_loss": v[4], "shape_loss": v[5]}
 
 
-class FusionPoseLoss(nn.Module):
+class FusionPoseLoss(HardKeypointMining, nn.Module):
+    """The six terms of the reference's FusionPoseLoss and their sum.  `ohkm_topk > 0` (this project's extension, after the reference's
+    positional arguments) adds a seventh, "ohkm_loss" = ohkm_weight * the online-hard-keypoint-mining loss of the heatmaps
+    (pk_ohkm_loss_fwd: per sample only the `ohkm_topk` worst-fitted joints count), to the returned dict and to "total_loss"."""
     NAMES = ("heatmap_loss", "offset_loss", "peak_loss", "variance_loss", "overlap_loss", "shape_loss", "total_loss")
 
     def __init__(self, heatmap_weight: float = 1.0, offset_weight: float = 1.0, peak_weight: float = 0.5,
                  variance_weight: float = 0.1, overlap_weight: float = 0.05, shape_weight: float = 0.05,
-                 target_sigma: float = 2.0, use_target_weight: bool = True):
+                 target_sigma: float = 2.0, use_target_weight: bool = True, ohkm_topk: int = 0, ohkm_weight: float = 1.0,
+                 num_keypoints: Optional[int] = None):
         super().__init__()
+        self._init_ohkm(ohkm_topk, num_keypoints, ohkm_weight)
         self.heatmap_weight, self.offset_weight, self.peak_weight = heatmap_weight, offset_weight, peak_weight
         self.variance_weight, self.overlap_weight, self.shape_weight = variance_weight, overlap_weight, shape_weight
         self.use_target_weight = use_target_weight
@@ -209,7 +215,15 @@ class FusionPoseLoss(nn.Module):
         vals = hipops.fusion_loss(outputs["heatmaps"], outputs["offsets"], outputs["variances"], target_heatmaps.float(),
                                   target_weight.float(), gt_keypoints.float(), input_size, self.gaussian_constraint.target_sigma,
                                   self._lambdas, self.use_target_weight)
-        return {n: vals[i] for i, n in enumerate(self.NAMES)}
+        losses = {n: vals[i] for i, n in enumerate(self.NAMES)}
+        if self.ohkm_topk:
+            # the term's weight rides in the kernel's `scale` (which must be positive: a weight of 0 keeps the term in the log, as 0)
+            w = target_weight.float() if self.use_target_weight else None
+            term = self._ohkm(outputs["heatmaps"], target_heatmaps, w, self.ohkm_weight or 1.0)
+            total = losses.pop("total_loss")
+            losses["ohkm_loss"] = term if self.ohkm_weight else term * 0.0
+            losses["total_loss"] = total + losses["ohkm_loss"]
+        return losses
 
 
 def build_fusion_head(in_channels: int, num_keypoints: int = 17, hidden_dim: int = 256) -> HeatmapRegressionHead:

@@ -3,6 +3,37 @@ import torch
 import torch.nn as nn
 
 from .. import hipops
+from ..configs.config import check_ohkm
+
+
+class HardKeypointMining:
+    """What the three mining losses share: the validated `ohkm_topk`, the call into the kernels, and the per-joint selection counts.  The
+    counts live in a non-persistent int64 (K,) buffer that the kernel adds to, so its address is the same in every replay of a captured
+    step; without `num_keypoints` it is allocated by the first forward (before any capture: a trainer warms up eagerly)."""
+
+    def _init_ohkm(self, topk, num_keypoints=None, weight=1.0, allow_off=True, what=("ohkm_topk", "ohkm_weight")):
+        self.ohkm_topk, self.ohkm_weight = check_ohkm(topk, weight, num_keypoints, allow_off, what)
+        counts = torch.zeros(int(num_keypoints), dtype=torch.int64) if (self.ohkm_topk and num_keypoints is not None) else None
+        self.register_buffer("_ohkm_counts", counts, persistent=False)
+
+    def _ohkm(self, pred, target, weight, scale):
+        pred = pred.float()
+        K = pred.shape[1]
+        if self.ohkm_topk > K:
+            raise ValueError(f"ohkm_topk = {self.ohkm_topk} exceeds the {K} keypoint maps of the prediction")
+        if self._ohkm_counts is None or self._ohkm_counts.numel() != K or self._ohkm_counts.device != pred.device:
+            self._ohkm_counts = torch.zeros(K, dtype=torch.int64, device=pred.device)
+        return hipops.ohkm_loss(pred, target.float(), weight, self.ohkm_topk, scale, self._ohkm_counts)
+
+    def selection_counts(self, reset=False):
+        """How often each joint was among the selected ones since construction (or the last `reset=True`), as an int64 (K,) host array;
+        None while mining is off or nothing has run yet."""
+        if self._ohkm_counts is None:
+            return None
+        counts = self._ohkm_counts.cpu().numpy().copy()
+        if reset:
+            self._ohkm_counts.zero_()
+        return counts
 
 
 class FusedPoseLoss(nn.Module):
@@ -62,6 +93,21 @@ class JointsMSELoss(nn.Module):
 
     def forward(self, output, target, target_weight):
         return hipops.pixel_loss(output.float(), target.float(), target_weight.float() if self.use_target_weight else None, 3)
+
+
+class JointsOHKMMSELoss(HardKeypointMining, nn.Module):
+    """HRNet's JointsOHKMMSELoss: per sample the mean of the `topk` largest per-joint errors 0.5 * mean_hw((w (p - t))^2), averaged over
+    the batch.  `topk = K` is JointsMSELoss.  The selection runs on the device (pk_ohkm_loss_fwd); `selection_counts()` tells which
+    joints it picks."""
+
+    def __init__(self, use_target_weight=True, topk=8, num_keypoints=None):
+        super().__init__()
+        self.use_target_weight = use_target_weight
+        self._init_ohkm(topk, num_keypoints, allow_off=False, what=("topk", "weight"))
+        self.topk = self.ohkm_topk
+
+    def forward(self, output, target, target_weight):
+        return self._ohkm(output, target, target_weight.float() if self.use_target_weight else None, 0.5)
 
 
 class CombinedLoss(nn.Module):

@@ -59,7 +59,8 @@ def _build_twin(real):
         bb = _twin_backbone(real.backbone)
         if bb is None:
             return None
-        return PoseEstimator.from_backbone(bb, bb.out_channels, real.num_keypoints, real.head_type, real.use_fusion_loss)
+        return PoseEstimator.from_backbone(bb, bb.out_channels, real.num_keypoints, real.head_type, real.use_fusion_loss,
+                                           ohkm_topk=real.ohkm_topk, ohkm_weight=real.ohkm_weight)
     return _twin_backbone(real)
 
 

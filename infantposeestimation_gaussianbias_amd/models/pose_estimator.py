@@ -7,10 +7,11 @@ import torch.nn as nn
 
 from .. import hipops
 from .. import dispatch as nnops
-from ..configs.config import check_test_scales
+from ..configs.config import check_ohkm, check_test_scales
 from .fusion_head import FusionPoseLoss, HeatmapRegressionHead, SoftArgmax2D
 from .hrformer import hrformer_base, hrformer_small
 from .hrnet import hrnet_w18, hrnet_w32, hrnet_w48
+from .losses import HardKeypointMining
 
 _BACKBONES = {"hrnet_w32": (hrnet_w32, 32), "hrnet_w48": (hrnet_w48, 48), "hrnet_w18": (hrnet_w18, 18),
               "hrformer_base": (hrformer_base, 78), "hrformer_small": (hrformer_small, 32)}
@@ -56,52 +57,62 @@ class HeatmapHead(nn.Module):
             return nnops.head_out(t, self.final_layer)
 
 
-class KeypointMSELoss(nn.Module):
-    def __init__(self, use_target_weight: bool = True):
+class KeypointMSELoss(HardKeypointMining, nn.Module):
+    """mean(((p - t) w)^2); with `ohkm_topk > 0` (mmpose's KeypointOHKMMSELoss) per sample only the `ohkm_topk` joints with the largest
+    error count (pk_ohkm_loss_fwd), and `ohkm_topk = K` is the plain loss again."""
+
+    def __init__(self, use_target_weight: bool = True, ohkm_topk: int = 0, num_keypoints: Optional[int] = None):
         super().__init__()
         self.use_target_weight = use_target_weight
+        self._init_ohkm(ohkm_topk, num_keypoints)
 
     def forward(self, pred, target, target_weight=None):
         w = target_weight.float() if (self.use_target_weight and target_weight is not None) else None
+        if self.ohkm_topk:
+            return self._ohkm(pred, target, w, 1.0)
         return hipops.pixel_loss(pred.float(), target.float(), w, 0)
 
 
 class PoseEstimator(nn.Module):
     def __init__(self, backbone: str = "hrformer_base", num_keypoints: int = 17, pretrained: bool = True,
-                 head_type: str = "fusion", use_fusion_loss: bool = True):
+                 head_type: str = "fusion", use_fusion_loss: bool = True, ohkm_topk: int = 0, ohkm_weight: float = 1.0):
         super().__init__()
         if backbone not in _BACKBONES:
             raise ValueError(f"Unknown backbone: {backbone}")
         ctor, in_channels = _BACKBONES[backbone]
-        self.head_type = head_type
-        self.use_fusion_loss = use_fusion_loss and head_type == "fusion"
-        self.backbone = ctor(pretrained=pretrained)
-        if head_type == "fusion":
-            self.head = HeatmapRegressionHead(in_channels, num_keypoints, 256, True)
-            self.loss_fn = FusionPoseLoss(1.0, 1.0, 0.5, 0.1, 0.05, 0.05, 2.0, True)
-        else:
-            self.head = HeatmapHead(in_channels, num_keypoints, 0)
-            self.loss_fn = KeypointMSELoss(True)
-        self.num_keypoints = num_keypoints
-        self.soft_argmax = SoftArgmax2D()
+        check_ohkm(ohkm_topk, ohkm_weight, num_keypoints)         # before the backbone is built
+        self._compose(ctor(pretrained=pretrained), in_channels, num_keypoints, head_type, use_fusion_loss, ohkm_topk, ohkm_weight)
 
-    @classmethod
-    def from_backbone(cls, backbone_module: nn.Module, in_channels: int, num_keypoints: int, head_type: str, use_fusion_loss: bool):
-        """Same composition as __init__ around an already-built backbone (used for 8-aligned padded twins)."""
-        self = cls.__new__(cls)
-        nn.Module.__init__(self)
+    def _compose(self, backbone_module, in_channels, num_keypoints, head_type, use_fusion_loss, ohkm_topk, ohkm_weight):
+        """`ohkm_topk > 0`: online hard keypoint mining.  The fusion loss gains the term "ohkm_loss" with weight `ohkm_weight`; the heatmap
+        head's loss becomes the mined one (it has one term, so `ohkm_weight` does not apply there)."""
+        self.ohkm_topk, self.ohkm_weight = check_ohkm(ohkm_topk, ohkm_weight, num_keypoints)
         self.head_type = head_type
         self.use_fusion_loss = use_fusion_loss and head_type == "fusion"
         self.backbone = backbone_module
         if head_type == "fusion":
             self.head = HeatmapRegressionHead(in_channels, num_keypoints, 256, True)
-            self.loss_fn = FusionPoseLoss(1.0, 1.0, 0.5, 0.1, 0.05, 0.05, 2.0, True)
+            self.loss_fn = FusionPoseLoss(1.0, 1.0, 0.5, 0.1, 0.05, 0.05, 2.0, True, self.ohkm_topk, self.ohkm_weight, num_keypoints)
         else:
             self.head = HeatmapHead(in_channels, num_keypoints, 0)
-            self.loss_fn = KeypointMSELoss(True)
+            self.loss_fn = KeypointMSELoss(True, self.ohkm_topk, num_keypoints)
         self.num_keypoints = num_keypoints
         self.soft_argmax = SoftArgmax2D()
+
+    @classmethod
+    def from_backbone(cls, backbone_module: nn.Module, in_channels: int, num_keypoints: int, head_type: str, use_fusion_loss: bool,
+                      ohkm_topk: int = 0, ohkm_weight: float = 1.0):
+        """Same composition as __init__ around an already-built backbone (used for 8-aligned padded twins)."""
+        self = cls.__new__(cls)
+        nn.Module.__init__(self)
+        self._compose(backbone_module, in_channels, num_keypoints, head_type, use_fusion_loss, ohkm_topk, ohkm_weight)
         return self
+
+    def selection_counts(self, reset: bool = False):
+        """Per-joint selection counts of the mining loss that actually runs: the padded twin's where the model runs as its twin (the twin
+        owns the buffer the kernel adds to), this model's own otherwise.  None while mining is off or nothing has run yet."""
+        tw = nnops.padded_twin(self)
+        return (tw.twin if tw is not None else self).loss_fn.selection_counts(reset)
 
     def forward(self, x, target=None, target_weight=None, gt_keypoints=None, input_size: Tuple[int, int] = (192, 256)) -> Dict[str, torch.Tensor]:
         tw = nnops.padded_twin(self)
@@ -212,4 +223,5 @@ class PoseEstimator(nn.Module):
 
 def build_model(cfg) -> PoseEstimator:
     return PoseEstimator(backbone=cfg.model.backbone, num_keypoints=cfg.model.num_keypoints, pretrained=cfg.model.pretrained,
-                         head_type=getattr(cfg.model, "head_type", "fusion"), use_fusion_loss=getattr(cfg.model, "use_fusion_loss", True))
+                         head_type=getattr(cfg.model, "head_type", "fusion"), use_fusion_loss=getattr(cfg.model, "use_fusion_loss", True),
+                         ohkm_topk=getattr(cfg.model, "ohkm_topk", 0), ohkm_weight=getattr(cfg.model, "ohkm_weight", 1.0))

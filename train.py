@@ -9,7 +9,9 @@ log interval), bf16 instead of fp16+GradScaler, fused AdamW over a flat paramete
 (`--graph`), GradScaler's "drop the step when a gradient is inf/NaN" and gradient-norm clipping as an opt-in device-side guard
 (`--skip_nonfinite`, `--clip_grad_norm X`), colour jitter on the device (`--color_jitter B C S`, or DATA.COLOR_JITTER of a legacy
 yaml), and an exponential moving average of the weights kept by the optimiser kernel (`--ema DECAY`): validation inside the loop then
-scores the averaged weights, and checkpoints carry them as "ema_state_dict" (validate.py / inference.py `--ema` load them).  With POSE_SYNTHETIC=1 the loader yields device-resident synthetic batches (no COCO on disk needed; they are not jittered).
+scores the averaged weights, and checkpoints carry them as "ema_state_dict" (validate.py / inference.py `--ema` load them), and online
+hard keypoint mining (`--ohkm TOPK [--ohkm_weight W]`, or LOSS.USE_OHKM / TOPK of a legacy yaml): per sample only the TOPK worst-fitted
+joints count in the heatmap loss, selected on the device inside the step; every validation interval logs which joints were selected.  With POSE_SYNTHETIC=1 the loader yields device-resident synthetic batches (no COCO on disk needed; they are not jittered).
 """
 import argparse
 import contextlib
@@ -79,6 +81,17 @@ def train_one_epoch(trainer, loader, epoch, cfg, logger, rank):
     return loss_meter.avg
 
 
+def selection_report(model, names):
+    """'joint share%' of the mining loss's selections since the last report, hardest first (and the counts start again); None while mining
+    is off or nothing was selected."""
+    counts = model.selection_counts(reset=True)
+    if counts is None or counts.sum() == 0:
+        return None
+    share = counts / counts.sum()
+    names = list(names) if len(names) == len(counts) else [f"kpt_{i}" for i in range(len(counts))]
+    return ", ".join(f"{names[i]} {100 * share[i]:.1f}%" for i in np.argsort(-share, kind="stable"))
+
+
 def main(args):
     cfg = get_config(args.config) if args.config else get_config()
     if args.data_root:
@@ -95,6 +108,10 @@ def main(args):
         cfg.train.color_jitter_prob = args.color_jitter_prob
     if args.ema is not None:
         cfg.train.ema_decay = args.ema
+    if args.ohkm is not None:
+        cfg.model.ohkm_topk = args.ohkm
+    if args.ohkm_weight is not None:
+        cfg.model.ohkm_weight = args.ohkm_weight
     world, rank, local = int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0))
     torch.cuda.set_device(local)
     if world > 1:
@@ -125,6 +142,10 @@ def main(args):
     val_loader = None
     for epoch in range(start_epoch, cfg.train.max_epochs):
         loss = train_one_epoch(trainer, loader, epoch, cfg, logger, rank)
+        if rank == 0 and cfg.model.ohkm_topk and ((epoch + 1) % cfg.train.val_interval == 0 or epoch == cfg.train.max_epochs - 1):
+            report = selection_report(model, cfg.data.keypoint_names)      # which joints are the hard ones
+            if report:
+                logger.info(f"Epoch [{epoch}] hard keypoint selections (top {cfg.model.ohkm_topk}): {report}")
         if rank == 0 and ((epoch + 1) % cfg.train.val_interval == 0 or epoch == cfg.train.max_epochs - 1):
             # validation inside the training loop (train.py:231-325, 437-452 of the reference): AP decides `best.pth`
             from validate import validate
@@ -173,6 +194,10 @@ def build_parser():
     p.add_argument("--ema", type=float, default=None, metavar="DECAY",
                    help="keep an exponential moving average of the weights in the optimiser kernel (e.g. 0.9998; warm-up "
                         "min(DECAY, (1+t)/(10+t))); validation and best.pth use the averaged weights (default: off)")
+    p.add_argument("--ohkm", type=int, default=None, metavar="TOPK",
+                   help="online hard keypoint mining: per sample only the TOPK joints with the largest heatmap error count (the fusion "
+                        "loss gains the term ohkm_loss; the heatmap head's loss becomes the mined one; default: off)")
+    p.add_argument("--ohkm_weight", type=float, default=None, metavar="W", help="weight of ohkm_loss in the fusion loss (default 1.0)")
     return p
 
 
