@@ -123,7 +123,7 @@ int pk_coco_kpt_eval(const double* oks, const int64_t* oks_off, const int32_t* g
 /* ---- f1: validation on detector boxes: pose rescoring and OKS-NMS per image (this project's own specification, DESIGN.md "Detector boxes
  * and OKS-NMS": the reference's yaml says TEST.USE_GT_BBOX: false and its code has neither step).  Everything fp64; no atomics, fixed
  * orders: two launches give identical bytes.  Poses of all images in CSR form: off (n_img + 1) int32 offsets, kpt (N,K,3) rows
- * [x, y, keypoint score], area (N), score (N); vars = (2 sigma)^2 (K).  1 <= K <= 64 (else PK_ERR_INVALID).
+ * [x, y, keypoint score], area (N), score (N); vars = (2 sigma)^2 (K).  1 <= K <= PK_NMS_MAX_K (else PK_ERR_INVALID).
  * pk_pose_rescore: score_out[i] = box_score[i] * mean{ s_k : s_k > in_vis_thr }, the sum over k ascending, then one divide and one
  *   multiply; 0 when no joint qualifies; box_score == NULL means 1.  in_vis_thr may be -inf (every non-NaN score counts), not NaN.
  * pk_oks_nms: one workgroup per image.  Pose-pair OKS: joint k counts when both poses have a keypoint score > in_vis_thr;
@@ -135,9 +135,11 @@ int pk_coco_kpt_eval(const double* oks, const int64_t* oks_off, const int32_t* g
  *     (same ordering rule) is selected and every remaining score is multiplied by exp(-oks^2 / thr), oks taken to the selected pose.
  *   Outputs, every element of an image with poses written: keep (N) uint8; n_keep (n_img) int32; order (N) int32: per image its kept
  *   local indices in selection order, then -1; out_score (N): the input score (soft == 0) or the score at selection, 0 where not kept.
- *   At most 1024 poses per image.  The offsets are device memory, so the entry cannot read them: the caller checks them (hipops.oks_nms
+ *   At most PK_NMS_MAX_POSES poses per image.  The offsets are device memory, so the entry cannot read them: the caller checks them (hipops.oks_nms
  *   raises with PK_ERR_UNSUPPORTED, naming the image and its count, before anything is launched); a workgroup that meets more writes only
  *   n_keep = -1 for its image.  A non-finite thr, a NaN in_vis_thr and soft mode with thr <= 0 or max_dets <= 0 are PK_ERR_INVALID.      */
+#define PK_NMS_MAX_K 64
+#define PK_NMS_MAX_POSES 1024
 int pk_pose_rescore(const double* kpt, const double* box_score, double* score_out, int N, int K, double in_vis_thr, void* stream);
 int pk_oks_nms(const double* kpt, const double* area, const double* score, const int32_t* off, const double* vars, uint8_t* keep,
                int32_t* n_keep, int32_t* order, double* out_score, int n_img, int K, double thr, double in_vis_thr, int soft, int max_dets,
@@ -197,7 +199,7 @@ int pk_nms_pose(const float* preds, const float* maxvals, float* out, uint8_t* k
  * imports calculate_movement_amplitude / calculate_temporal_consistency from utils.metrics -- examples/quick_start.py:159,
  * visualization.py:385,441 -- and names PCK in both yamls, and defines none of them).  One launch each; no float atomics; every
  * floating-point sum in a fixed order, so two runs give identical bits.
- * pk_pck: pred, gt (N,K,2) f32; vis (N,K) f32; norm (N) f32; thresholds (n_thr) f32, 1 <= n_thr <= 16.  correct (n_thr,K) int64, valid (K)
+ * pk_pck: pred, gt (N,K,2) f32; vis (N,K) f32; norm (N) f32; thresholds (n_thr) f32, 1 <= n_thr <= PK_PCK_MAX_THR.  correct (n_thr,K) int64, valid (K)
  *   int64 and err_sum (K) float64 ACCUMULATE: the caller zeroes them once, every launch adds its batch.  Pair (n,k) counts iff vis > 0,
  *   norm[n] > 0 and the four coordinates are finite.  Decision in float32, one rounding per operation, no square root:
  *   dx = px - gx, dy = py - gy, d2 = dx dx + dy dy, r = thr norm, hit iff d2 <= r r.  err_sum[k] += sum_n sqrt((double)d2) / (double)norm[n].
@@ -208,7 +210,9 @@ int pk_nms_pose(const float* preds, const float* maxvals, float* out, uint8_t* k
  *   step; 9 sum over triples of |(p[t+1] - 2 p[t]) + p[t-1]|; 10 n_triples.  Differences, norms sqrt(dx dx + dy dy) and sums in float64.
  * pk_position_histogram: edges_x (nbx+1), edges_y (nby+1) float64 ascending, on the device; counts (S,K,nby,nbx) int32, overwritten.  A
  *   valid frame (as above) falls in bin i with e[i] <= v < e[i+1], the last bin also takes v == e[nb], anything outside [e[0], e[nb]] is
- *   dropped: np.histogram2d's rule for any edges.  nbx nby <= 16384 (one workgroup's LDS histogram), else PK_ERR_UNSUPPORTED.            */
+ *   dropped: np.histogram2d's rule for any edges.  nbx nby <= PK_HIST_MAX_BINS (one workgroup's LDS histogram), else PK_ERR_UNSUPPORTED.  */
+#define PK_PCK_MAX_THR 16
+#define PK_HIST_MAX_BINS 16384
 int pk_pck(const float* pred, const float* gt, const float* vis, const float* norm, const float* thresholds, int64_t* correct,
            int64_t* valid, double* err_sum, int N, int K, int n_thr, void* stream);
 int pk_motion_stats(const float* coords, const float* conf, double* stats, int S, int T, int K, float min_conf, void* stream);
@@ -219,13 +223,15 @@ int pk_position_histogram(const float* coords, const float* conf, const double* 
  * pk_motion_spectrum: coords (S,T,K,2) f32 image pixels; conf (S,T,K) f32 or NULL; frames are valid as for pk_motion_stats.  power (S,K,F)
  *   and summary (S,K,6) float64, every element written.  Two launches; no float atomics, every sum in a fixed order that depends on T
  *   alone: two launches give identical bits, and a bin's bits depend neither on S, on K nor on the other bins of the launch.
- *   Bin j (0 <= j < F) is the frequency (j0 + j) / N cycles per frame; j0 >= 1, j0 + F - 1 <= N / 2, 2 <= N <= 2^30 (N > T zero-pads),
- *   1 <= F <= 16384.  window 0: w_t = 1; window 1: periodic Hann, w_t = 0.5 - 0.5 cos(6.283185307179586 ((double)t / (double)T)); an invalid
+ *   Bin j (0 <= j < F) is the frequency (j0 + j) / N cycles per frame; j0 >= 1, j0 + F - 1 <= N / 2, 2 <= N <= PK_SPEC_MAX_NFFT = 2^30 (N > T zero-pads),
+ *   1 <= F <= PK_SPEC_MAX_BINS.  window 0: w_t = 1; window 1: periodic Hann, w_t = 0.5 - 0.5 cos(6.283185307179586 ((double)t / (double)T)); an invalid
  *   frame has weight 0.  Per joint, in float64 without FMA: n = valid frames, W = sum w_t, m = sum w_t p_t / W, u_t = w_t (p_t - m),
  *   X_j = sum_t u_t.x (cos ang, sin ang) and Y_j likewise with r = ((int64)(j0 + j) t) mod N, ang = 6.283185307179586 ((double)r / (double)N),
  *   P_j = (4 / (W W)) ((Xre^2 + Xim^2) + (Yre^2 + Yim^2)): a linear oscillation of amplitude A px at a bin frequency has P = A^2.  n < 2 or
  *   not W > 0: the whole row is 0.  Summary columns: 0 n; 1 W; 2 band power sum_j P_j; 3 peak bin j0 + argmax_j P_j (the lowest among equal
  *   maxima; -1 when column 2 is 0); 4 the peak's power (or 0); 5 centroid sum (j0 + j) P_j / sum P_j in bins (or 0).                      */
+#define PK_SPEC_MAX_BINS 16384
+#define PK_SPEC_MAX_NFFT 1073741824
 int pk_motion_spectrum(const float* coords, const float* conf, double* power, double* summary, int S, int T, int K, float min_conf,
                        int N, int j0, int F, int window, void* stream);
 

@@ -49,6 +49,15 @@ def declared_symbols(header_path=HEADER_PATH):
     return out
 
 
+def declared_constants(header_path=HEADER_PATH):
+    """Parse `#define PK_XXX <decimal integer>` out of the public header -> {name: int}: the limits the op layer checks as well."""
+    with open(header_path) as f:
+        return {m.group(1): int(m.group(2)) for m in re.finditer(r"^#define (PK_[A-Z0-9_]+) (\d+)\s*$", f.read(), flags=re.M)}
+
+
+CONSTANTS = declared_constants()
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise PoseKernelError(

@@ -108,6 +108,55 @@ __device__ __forceinline__ float block_max(float v, float* red) {
     return t;
 }
 
+// Reduction of `v` by `op` over a block of exactly WAVES waves, returned to every thread, for the analysis units, whose results are
+// compared bit for bit.  `red`: LDS scratch of WAVES entries of V.  The order is fixed: the xor butterfly inside the wave, offsets
+// 32, 16, ..., 1, then red[0] op red[1] op ... op red[WAVES - 1] from left to right.  Safe to call repeatedly (barriers on both sides).
+struct SumOp { template <class V> __device__ __forceinline__ V operator()(V a, V b) const { return a + b; } };
+struct MinOp { template <class V> __device__ __forceinline__ V operator()(V a, V b) const { return a < b ? a : b; } };
+struct MaxOp { template <class V> __device__ __forceinline__ V operator()(V a, V b) const { return a > b ? a : b; } };
+template <int WAVES, class V, class Op>
+__device__ __forceinline__ V block_reduce(V v, V* red, Op op) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o, 64));
+    __syncthreads();
+    if (lane == 0) red[w] = v;
+    __syncthreads();
+    V t = red[0];
+#pragma unroll
+    for (int i = 1; i < WAVES; ++i) t = op(t, red[i]);
+    return t;
+}
+
+// ---- rules the analysis units share ------------------------------------------------------------------------
+// Frame t of the joint at `base` of a pose sequence (S,T,K,2), 0 <= t < T: valid iff both coordinates are finite and (conf == NULL or
+// conf >= min_conf).  The float32 coordinates widen exactly.  (pk_motion_stats, pk_position_histogram, pk_motion_spectrum)
+struct SeqFrame { double x, y; bool ok; };
+__device__ __forceinline__ SeqFrame seq_frame(const float* __restrict__ coords, const float* __restrict__ conf, size_t base, int K, int t,
+                                              float min_conf) {
+    const size_t i = base + (size_t)t * K;
+    const float x = coords[2 * i], y = coords[2 * i + 1];
+    SeqFrame f;
+    f.ok = isfinite(x) && isfinite(y) && (conf == nullptr || conf[i] >= min_conf);
+    f.x = (double)x;
+    f.y = (double)y;
+    return f;
+}
+// What the entries of those sequences ask of (S, T, K): one workgroup per (sequence, joint), so S K is a grid dimension
+static inline int seq_shape_check(const char* who, int S, int T, int K) {
+    PK_REQUIRE(S > 0 && T > 0 && K > 0 && (int64_t)S * K <= 0x7fffffff, "%s: bad shape S=%d T=%d K=%d", who, S, T, K);
+    return PK_OK;
+}
+// Order-preserving key of np.argsort(-score, kind='mergesort'): ascending key == descending score, NaN last (all NaNs equal),
+// -0 == +0.  Ties are broken by position by the callers.  (k_coco_oks, k_coco_rank, k_oks_nms)
+__device__ __forceinline__ uint64_t desc_score_key(double s) {
+    if (isnan(s)) return ~0ull;
+    if (s == 0.0) s = 0.0;
+    const uint64_t b = __double_as_longlong(s);
+    const uint64_t asc = (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+    return ~asc;
+}
+
 // ---- bf16 <-> f32 ----------------------------------------------------------------------------------------
 __device__ __forceinline__ float bf16_to_f32(uint16_t h) { return __uint_as_float(((uint32_t)h) << 16); }
 // fp32 -> bf16, round-to-nearest-even, NaN stays NaN: gfx950 has the conversion in hardware (v_cvt_pk_bf16_f32, two

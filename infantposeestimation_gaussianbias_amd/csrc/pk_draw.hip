@@ -296,17 +296,12 @@ __global__ void __launch_bounds__(256) k_overlay_max(const float* __restrict__ h
     for (int k = 1; k < K; ++k) v = fmaxf(v, p[(size_t)k * hw]);
     m[(size_t)n * hw + i] = v;
 }
-__global__ void __launch_bounds__(256) k_overlay_minmax(const float* __restrict__ mplane, float* __restrict__ partial, int h, int w, int H, int W) {
+// Minimum of `lo` and maximum of `hi` over the 256 threads of the block, stored by thread 0 as the pair at `at()` (evaluated in that
+// thread alone): the xor butterfly inside the wave, one LDS slot per wave, the four waves as (0, 1), (2, 3).  fminf / fmaxf, not a
+// comparison: they ignore a NaN.  One barrier: a kernel calls it once.
+template <class At>
+__device__ __forceinline__ void ov_block_minmax_store(float lo, float hi, At at) {
     __shared__ float s_lo[4], s_hi[4];
-    const int n = blockIdx.y, total = H * W;
-    const float* m = mplane + (size_t)n * h * w;
-    float lo = INFINITY, hi = -INFINITY;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
-        const int y = i / W;
-        const float v = ov_resized(m, h, w, H, W, y, i - y * W);
-        lo = fminf(lo, v);
-        hi = fmaxf(hi, v);
-    }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         lo = fminf(lo, __shfl_xor(lo, o, 64));
@@ -318,10 +313,22 @@ __global__ void __launch_bounds__(256) k_overlay_minmax(const float* __restrict_
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        float* out = partial + ((size_t)n * gridDim.x + blockIdx.x) * 2;
+        float* out = at();
         out[0] = fminf(fminf(s_lo[0], s_lo[1]), fminf(s_lo[2], s_lo[3]));
         out[1] = fmaxf(fmaxf(s_hi[0], s_hi[1]), fmaxf(s_hi[2], s_hi[3]));
     }
+}
+__global__ void __launch_bounds__(256) k_overlay_minmax(const float* __restrict__ mplane, float* __restrict__ partial, int h, int w, int H, int W) {
+    const int n = blockIdx.y, total = H * W;
+    const float* m = mplane + (size_t)n * h * w;
+    float lo = INFINITY, hi = -INFINITY;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+        const int y = i / W;
+        const float v = ov_resized(m, h, w, H, W, y, i - y * W);
+        lo = fminf(lo, v);
+        hi = fmaxf(hi, v);
+    }
+    ov_block_minmax_store(lo, hi, [&] { return partial + ((size_t)n * gridDim.x + blockIdx.x) * 2; });
 }
 __global__ void __launch_bounds__(256) k_overlay_blend(uint8_t* __restrict__ img, const float* __restrict__ mplane, const float* __restrict__ partial,
                                                        int nb, const uint8_t* __restrict__ lut, uint8_t* __restrict__ index, int a256, int h, int w,
@@ -400,9 +407,8 @@ __device__ __forceinline__ double ovp_map(const double a, const double b, const 
     return (a * (double)X + b * (double)Y) + c;       // every operation rounds monotonically: over a rectangle the extremes are at its corners
 }
 
-// one workgroup per patch: min and max of its own max plane, fixed order (strided partials, wave butterflies, four waves in order)
+// one workgroup per patch: min and max of its own max plane, fixed order (strided partials, then `ov_block_minmax_store`)
 __global__ void __launch_bounds__(256) k_overlay_patch_minmax(const float* __restrict__ mplane, float* __restrict__ stats, int hw) {
-    __shared__ float s_lo[4], s_hi[4];
     const int p = blockIdx.x;
     const float* m = mplane + (size_t)p * hw;
     float lo = INFINITY, hi = -INFINITY;
@@ -411,20 +417,7 @@ __global__ void __launch_bounds__(256) k_overlay_patch_minmax(const float* __res
         lo = fminf(lo, v);
         hi = fmaxf(hi, v);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        lo = fminf(lo, __shfl_xor(lo, o, 64));
-        hi = fmaxf(hi, __shfl_xor(hi, o, 64));
-    }
-    if ((threadIdx.x & 63) == 0) {
-        s_lo[threadIdx.x >> 6] = lo;
-        s_hi[threadIdx.x >> 6] = hi;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        stats[2 * (size_t)p] = fminf(fminf(s_lo[0], s_lo[1]), fminf(s_lo[2], s_lo[3]));
-        stats[2 * (size_t)p + 1] = fmaxf(fmaxf(s_hi[0], s_hi[1]), fmaxf(s_hi[2], s_hi[3]));
-    }
+    ov_block_minmax_store(lo, hi, [&] { return stats + 2 * (size_t)p; });
 }
 
 // Gather over the tiles of k_draw_shapes: a workgroup owns a 32 x 8 tile of one frame, finds the frame's patches by binary search in the

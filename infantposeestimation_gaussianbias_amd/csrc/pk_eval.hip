@@ -20,16 +20,6 @@
 #define PK_COCO_MAX_CURVES 64      // A * T lanes of the match kernel (one wave)
 #define PK_COCO_GTM_LDS 512        // ground truths per image whose "already matched" flags live in LDS; beyond that: the workspace
 
-// Order-preserving key of np.argsort(-score, kind='mergesort'): ascending key == descending score, NaN last (all NaNs equal),
-// -0 == +0.  Ties are broken by position by the callers.
-__device__ __forceinline__ uint64_t desc_score_key(double s) {
-    if (isnan(s)) return ~0ull;
-    if (s == 0.0) s = 0.0;
-    const uint64_t b = __double_as_longlong(s);
-    const uint64_t asc = (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-    return ~asc;
-}
-
 // np.sum of n <= 128 float64 terms fed in order: n < 8 left to right; otherwise 8 strided partial sums over the first n - n % 8 terms,
 // combined ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then the tail in order (numpy's pairwise_sum leaf).  The partial sums rotate through
 // registers instead of being indexed by the term count.
@@ -66,7 +56,7 @@ __global__ void __launch_bounds__(256) k_coco_oks(const double* __restrict__ gt_
     const int g0 = gt_off[img], G = gt_off[img + 1] - g0;
     const int D = min(n, max_dets);
     for (int k = threadIdx.x; k < K; k += blockDim.x) svar[k] = vars[k];
-    // stable rank of each detection inside its image; ranks are a permutation, so every kept slot has exactly one writer
+    // stable rank of each detection inside its image by `desc_score_key` (pk_common.h); ranks are a permutation, so every kept slot has exactly one writer
     for (int j = threadIdx.x; j < n; j += blockDim.x) {
         const uint64_t kj = desc_score_key(dt_score[d0 + j]);
         int r = 0;

@@ -97,15 +97,6 @@ struct JitterDesc {
     int32_t enable;
     float b, c, s;           // brightness, contrast, saturation factors
 };
-// Sum of `v` over a 256-thread block (exact, unsigned), returned to every thread.
-__device__ __forceinline__ uint32_t block_sum_u32(uint32_t v, uint32_t* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
 __global__ void __launch_bounds__(256) k_crop_u8(const unsigned char* __restrict__ src, const CropDesc* __restrict__ desc, int out_w, int out_h,
                                                  uint32_t* __restrict__ crop, uint32_t* __restrict__ partial) {
     __shared__ uint32_t red[4];
@@ -119,7 +110,7 @@ __global__ void __launch_bounds__(256) k_crop_u8(const unsigned char* __restrict
         crop[(size_t)blockIdx.y * plane + pix] = (uint32_t)u[0] | ((uint32_t)u[1] << 8) | ((uint32_t)u[2] << 16);
         sum = (uint32_t)(u[0] + u[1] + u[2]);
     }
-    sum = block_sum_u32(sum, red);
+    sum = block_reduce<4>(sum, red, SumOp());          // exact, unsigned
     if (threadIdx.x == 0) partial[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = sum;
 }
 __global__ void __launch_bounds__(256) k_jitter_normalize(const uint32_t* __restrict__ crop, const uint32_t* __restrict__ partial,
@@ -133,7 +124,7 @@ __global__ void __launch_bounds__(256) k_jitter_normalize(const uint32_t* __rest
     if (j.enable) {                      // uniform over the block
         uint32_t S = 0;                  // < 2^32: the entry point rejects crops with 765 h w >= 2^32
         for (int i = threadIdx.x; i < (int)gridDim.x; i += 256) S += partial[(size_t)blockIdx.y * gridDim.x + i];
-        S = block_sum_u32(S, red);
+        S = block_reduce<4>(S, red, SumOp());
         m = (float)__dmul_rn(__ddiv_rn((double)S, __dmul_rn(255.0, (double)plane * 3.0)), (double)j.b);
     }
     if (pix >= plane) return;

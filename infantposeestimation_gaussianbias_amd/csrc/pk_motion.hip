@@ -12,27 +12,6 @@
 
 #define MOTION_THREADS 256
 #define MOTION_WAVES (MOTION_THREADS / PK_WAVE)
-#define PCK_MAX_THR 16
-#define HIST_MAX_BINS 16384      // int32 bins of one workgroup: 64 KB of LDS
-
-struct SumOp { template <class V> __device__ __forceinline__ V operator()(V a, V b) const { return a + b; } };
-struct MinOp { template <class V> __device__ __forceinline__ V operator()(V a, V b) const { return a < b ? a : b; } };
-struct MaxOp { template <class V> __device__ __forceinline__ V operator()(V a, V b) const { return a > b ? a : b; } };
-
-// Reduction of `v` over the 256 threads of the block, returned to every thread.  `red`: LDS scratch of MOTION_WAVES entries of V.
-template <class V, class Op>
-__device__ __forceinline__ V block_reduce(V v, V* red, Op op) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o, 64));
-    __syncthreads();
-    if (lane == 0) red[w] = v;
-    __syncthreads();
-    V t = red[0];
-#pragma unroll
-    for (int i = 1; i < MOTION_WAVES; ++i) t = op(t, red[i]);
-    return t;
-}
 
 __device__ __forceinline__ bool finite2(float x, float y) { return isfinite(x) && isfinite(y); }
 
@@ -48,10 +27,10 @@ __global__ void __launch_bounds__(MOTION_THREADS) k_pck(const float* __restrict_
     __shared__ double red_d[MOTION_WAVES];
     __shared__ int red_i[MOTION_WAVES];
     const int k = blockIdx.x;
-    float thr[PCK_MAX_THR];
-    int hit[PCK_MAX_THR];
+    float thr[PK_PCK_MAX_THR];
+    int hit[PK_PCK_MAX_THR];
 #pragma unroll
-    for (int j = 0; j < PCK_MAX_THR; ++j) {
+    for (int j = 0; j < PK_PCK_MAX_THR; ++j) {
         thr[j] = j < n_thr ? thresholds[j] : 0.f;
         hit[j] = 0;
     }
@@ -66,21 +45,21 @@ __global__ void __launch_bounds__(MOTION_THREADS) k_pck(const float* __restrict_
         ++n_valid;
         err += sqrt((double)d2) / (double)nm;
 #pragma unroll
-        for (int j = 0; j < PCK_MAX_THR; ++j) {
+        for (int j = 0; j < PK_PCK_MAX_THR; ++j) {
             const float r = thr[j] * nm;
             hit[j] += (j < n_thr && d2 <= r * r) ? 1 : 0;
         }
     }
-    const int tv = block_reduce(n_valid, red_i, SumOp());
-    const double te = block_reduce(err, red_d, SumOp());
+    const int tv = block_reduce<MOTION_WAVES>(n_valid, red_i, SumOp());
+    const double te = block_reduce<MOTION_WAVES>(err, red_d, SumOp());
     if (threadIdx.x == 0) {
         valid[k] += tv;
         err_sum[k] += te;
     }
 #pragma unroll
-    for (int j = 0; j < PCK_MAX_THR; ++j) {
+    for (int j = 0; j < PK_PCK_MAX_THR; ++j) {
         if (j < n_thr) {                                          // uniform over the block
-            const int th = block_reduce(hit[j], red_i, SumOp());
+            const int th = block_reduce<MOTION_WAVES>(hit[j], red_i, SumOp());
             if (threadIdx.x == 0) correct[(size_t)j * K + k] += th;
         }
     }
@@ -90,27 +69,20 @@ extern "C" int pk_pck(const float* pred, const float* gt, const float* vis, cons
                       int64_t* valid, double* err_sum, int N, int K, int n_thr, void* stream) {
     PK_REQUIRE(pred && gt && vis && norm && thresholds && correct && valid && err_sum, "pk_pck: null pointer");
     PK_REQUIRE(N > 0 && K > 0, "pk_pck: bad shape N=%d K=%d", N, K);
-    PK_REQUIRE(n_thr >= 1 && n_thr <= PCK_MAX_THR, "pk_pck: %d thresholds (1 to %d)", n_thr, PCK_MAX_THR);
+    PK_REQUIRE(n_thr >= 1 && n_thr <= PK_PCK_MAX_THR, "pk_pck: %d thresholds (1 to %d)", n_thr, PK_PCK_MAX_THR);
     hipLaunchKernelGGL(k_pck, dim3(K), dim3(MOTION_THREADS), 0, (hipStream_t)stream, pred, gt, vis, norm, thresholds, correct, valid, err_sum,
                        N, K, n_thr);
     return pk_launch_status("pk_pck");
 }
 
 // ================================================================================================ per-joint movement statistics
-// Frame t of joint k is valid iff both coordinates are finite and (conf == NULL or conf >= min_conf).  A step t -> t+1 counts iff both
+// Frame t of joint k is valid by `seq_frame`'s rule (pk_common.h), a frame outside [0, T) is not.  A step t -> t+1 counts iff both
 // frames are valid, a triple iff t-1, t, t+1 are.  The thread that owns frame t takes the step that starts at t and the triple centred on
 // t.  Differences, norms (sqrt(dx dx + dy dy), no FMA) and sums in float64; the float32 inputs widen exactly.
-struct MotionFrame { double x, y; bool ok; };
-__device__ __forceinline__ MotionFrame motion_frame(const float* __restrict__ coords, const float* __restrict__ conf, size_t base, int K, int t,
-                                                    int T, float min_conf) {
-    MotionFrame f = {0.0, 0.0, false};
-    if (t < 0 || t >= T) return f;
-    const size_t i = base + (size_t)t * K;
-    const float x = coords[2 * i], y = coords[2 * i + 1];
-    f.ok = finite2(x, y) && (conf == nullptr || conf[i] >= min_conf);
-    f.x = (double)x;
-    f.y = (double)y;
-    return f;
+__device__ __forceinline__ SeqFrame motion_frame(const float* __restrict__ coords, const float* __restrict__ conf, size_t base, int K, int t, int T,
+                                                 float min_conf) {
+    if (t < 0 || t >= T) return SeqFrame{0.0, 0.0, false};
+    return seq_frame(coords, conf, base, K, t, min_conf);
 }
 
 __global__ void __launch_bounds__(MOTION_THREADS) k_motion_stats(const float* __restrict__ coords, const float* __restrict__ conf,
@@ -124,30 +96,30 @@ __global__ void __launch_bounds__(MOTION_THREADS) k_motion_stats(const float* __
     float min_x = INFINITY, max_x = -INFINITY, min_y = INFINITY, max_y = -INFINITY;
     double path = 0.0, max_step = 0.0, accel = 0.0;
     for (int t = threadIdx.x; t < T; t += MOTION_THREADS) {
-        const MotionFrame c = motion_frame(coords, conf, base, K, t, T, min_conf);
+        const SeqFrame c = motion_frame(coords, conf, base, K, t, T, min_conf);
         if (!c.ok) continue;
         const float cx = (float)c.x, cy = (float)c.y;
         ++n_valid;
         min_x = fminf(min_x, cx), max_x = fmaxf(max_x, cx), min_y = fminf(min_y, cy), max_y = fmaxf(max_y, cy);
-        const MotionFrame nx = motion_frame(coords, conf, base, K, t + 1, T, min_conf);
+        const SeqFrame nx = motion_frame(coords, conf, base, K, t + 1, T, min_conf);
         if (!nx.ok) continue;
         const double dx = nx.x - c.x, dy = nx.y - c.y;
         const double step = sqrt(dx * dx + dy * dy);
         ++n_steps;
         path += step;
         max_step = step > max_step ? step : max_step;
-        const MotionFrame pv = motion_frame(coords, conf, base, K, t - 1, T, min_conf);
+        const SeqFrame pv = motion_frame(coords, conf, base, K, t - 1, T, min_conf);
         if (!pv.ok) continue;
         const double ax = (nx.x - 2.0 * c.x) + pv.x, ay = (nx.y - 2.0 * c.y) + pv.y;
         ++n_triples;
         accel += sqrt(ax * ax + ay * ay);
     }
-    const int tv = block_reduce(n_valid, red_i, SumOp()), ts = block_reduce(n_steps, red_i, SumOp()),
-              tt = block_reduce(n_triples, red_i, SumOp());
-    const float lo_x = block_reduce(min_x, red_f, MinOp()), hi_x = block_reduce(max_x, red_f, MaxOp()),
-                lo_y = block_reduce(min_y, red_f, MinOp()), hi_y = block_reduce(max_y, red_f, MaxOp());
-    const double tp = block_reduce(path, red_d, SumOp()), tm = block_reduce(max_step, red_d, MaxOp()),
-                 ta = block_reduce(accel, red_d, SumOp());
+    const int tv = block_reduce<MOTION_WAVES>(n_valid, red_i, SumOp()), ts = block_reduce<MOTION_WAVES>(n_steps, red_i, SumOp()),
+              tt = block_reduce<MOTION_WAVES>(n_triples, red_i, SumOp());
+    const float lo_x = block_reduce<MOTION_WAVES>(min_x, red_f, MinOp()), hi_x = block_reduce<MOTION_WAVES>(max_x, red_f, MaxOp()),
+                lo_y = block_reduce<MOTION_WAVES>(min_y, red_f, MinOp()), hi_y = block_reduce<MOTION_WAVES>(max_y, red_f, MaxOp());
+    const double tp = block_reduce<MOTION_WAVES>(path, red_d, SumOp()), tm = block_reduce<MOTION_WAVES>(max_step, red_d, MaxOp()),
+                 ta = block_reduce<MOTION_WAVES>(accel, red_d, SumOp());
     if (threadIdx.x == 0) {
         double* o = stats + (size_t)blockIdx.x * 11;
         const double rx = tv ? (double)hi_x - (double)lo_x : 0.0, ry = tv ? (double)hi_y - (double)lo_y : 0.0;
@@ -167,7 +139,7 @@ __global__ void __launch_bounds__(MOTION_THREADS) k_motion_stats(const float* __
 
 extern "C" int pk_motion_stats(const float* coords, const float* conf, double* stats, int S, int T, int K, float min_conf, void* stream) {
     PK_REQUIRE(coords && stats, "pk_motion_stats: null pointer");
-    PK_REQUIRE(S > 0 && T > 0 && K > 0 && (int64_t)S * K <= 0x7fffffff, "pk_motion_stats: bad shape S=%d T=%d K=%d", S, T, K);
+    if (const int rc = seq_shape_check("pk_motion_stats", S, T, K)) return rc;
     hipLaunchKernelGGL(k_motion_stats, dim3(S * K), dim3(MOTION_THREADS), 0, (hipStream_t)stream, coords, conf, stats, T, K, min_conf);
     return pk_launch_status("pk_motion_stats");
 }
@@ -196,7 +168,7 @@ __global__ void __launch_bounds__(MOTION_THREADS) k_position_histogram(const flo
     for (int i = threadIdx.x; i < nb; i += MOTION_THREADS) hist[i] = 0;
     __syncthreads();
     for (int t = threadIdx.x; t < T; t += MOTION_THREADS) {
-        const MotionFrame c = motion_frame(coords, conf, base, K, t, T, min_conf);
+        const SeqFrame c = motion_frame(coords, conf, base, K, t, T, min_conf);
         if (!c.ok) continue;
         const int bx = edge_bin(c.x, edges_x, nbx), by = edge_bin(c.y, edges_y, nby);
         if (bx >= 0 && by >= 0) atomicAdd(&hist[by * nbx + bx], 1);      // integer counts: order-free
@@ -209,10 +181,10 @@ __global__ void __launch_bounds__(MOTION_THREADS) k_position_histogram(const flo
 extern "C" int pk_position_histogram(const float* coords, const float* conf, const double* edges_x, const double* edges_y, int32_t* counts,
                                      int S, int T, int K, int nbx, int nby, float min_conf, void* stream) {
     PK_REQUIRE(coords && edges_x && edges_y && counts, "pk_position_histogram: null pointer");
-    PK_REQUIRE(S > 0 && T > 0 && K > 0 && (int64_t)S * K <= 0x7fffffff, "pk_position_histogram: bad shape S=%d T=%d K=%d", S, T, K);
+    if (const int rc = seq_shape_check("pk_position_histogram", S, T, K)) return rc;
     PK_REQUIRE(nbx > 0 && nby > 0, "pk_position_histogram: bad bin counts %d x %d", nbx, nby);
-    PK_SUPPORTED((int64_t)nbx * nby <= HIST_MAX_BINS,
-                 "pk_position_histogram: %d x %d bins exceed the %d a workgroup keeps in LDS; take larger bins", nbx, nby, HIST_MAX_BINS);
+    PK_SUPPORTED((int64_t)nbx * nby <= PK_HIST_MAX_BINS,
+                 "pk_position_histogram: %d x %d bins exceed the %d a workgroup keeps in LDS; take larger bins", nbx, nby, PK_HIST_MAX_BINS);
     hipLaunchKernelGGL(k_position_histogram, dim3(S * K), dim3(MOTION_THREADS), (size_t)nbx * nby * sizeof(int), (hipStream_t)stream, coords,
                        conf, edges_x, edges_y, counts, T, K, nbx, nby, min_conf);
     return pk_launch_status("pk_position_histogram");

@@ -12,19 +12,7 @@
 
 #include <math.h>
 
-#define PK_NMS_MAX_K 64
-#define PK_NMS_MAX_POSES 1024      // poses per image whose scores, flags and rank live in LDS
-#define PK_NMS_THREADS 256
-
-// Ascending key == descending score, NaN last (all NaNs equal), -0 == +0: the rule of k_coco_oks (pk_eval.hip).  Ties go to the lower index
-// at the callers.
-__device__ __forceinline__ uint64_t nms_score_key(double s) {
-    if (isnan(s)) return ~0ull;
-    if (s == 0.0) s = 0.0;
-    const uint64_t b = __double_as_longlong(s);
-    const uint64_t asc = (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-    return ~asc;
-}
+#define PK_NMS_THREADS 256      // one workgroup per image; its PK_NMS_MAX_POSES scores, flags and ranks live in LDS
 
 __global__ void __launch_bounds__(256) k_pose_rescore(const double* __restrict__ kpt, const double* __restrict__ box_score,
                                                       double* __restrict__ score_out, int N, int K, double in_vis_thr) {
@@ -92,12 +80,13 @@ __global__ void __launch_bounds__(PK_NMS_THREADS) k_oks_nms(const double* __rest
     const double* kp0 = kpt + (size_t)d0 * K * 3;
     int cnt = 0;                                      // the same value in every thread
     if (!soft) {
-        // stable rank by descending score; the ranks are a permutation, so every slot of sorted[] has exactly one writer
+        // stable rank by descending score (`desc_score_key`, ties to the lower index); the ranks are a permutation, so every slot of
+        // sorted[] has exactly one writer
         for (int j = tid; j < n; j += PK_NMS_THREADS) {
-            const uint64_t kj = nms_score_key(cur[j]);
+            const uint64_t kj = desc_score_key(cur[j]);
             int r = 0;
             for (int q = 0; q < n; ++q) {
-                const uint64_t kq = nms_score_key(cur[q]);
+                const uint64_t kq = desc_score_key(cur[q]);
                 r += (kq < kj) || (kq == kj && q < j);
             }
             sorted[r] = j;
@@ -130,7 +119,7 @@ __global__ void __launch_bounds__(PK_NMS_THREADS) k_oks_nms(const double* __rest
             int bi = 0x7fffffff;
             for (int j = tid; j < n; j += PK_NMS_THREADS) {
                 if (!alive[j]) continue;
-                const uint64_t kj = nms_score_key(cur[j]);
+                const uint64_t kj = desc_score_key(cur[j]);
                 if (kj < bk || (kj == bk && j < bi)) {
                     bk = kj;
                     bi = j;

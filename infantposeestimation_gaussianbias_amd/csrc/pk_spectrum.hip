@@ -13,43 +13,25 @@
 #define SPEC_BINS PK_WAVE                    // bins of one workgroup: lane l of EVERY wave owns bin blockIdx.y 64 + l
 #define SPEC_TILE 256                        // frames of one LDS tile
 #define SPEC_CHUNK (SPEC_TILE / SPEC_WAVES)  // wave w takes frames [64 w, 64 w + 64) of every tile
-#define SPEC_MAX_BINS 16384
-#define SPEC_MAX_NFFT (1 << 30)
 #define SPEC_TWO_PI 6.283185307179586
 
-// Sum of `v` over the 256 threads of the block, returned to every thread: the xor butterfly inside the wave, then the waves in order.
-template <class V>
-__device__ __forceinline__ V spec_block_sum(V v, V* red) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if (lane == 0) red[w] = v;
-    __syncthreads();
-    V t = red[0];
-#pragma unroll
-    for (int i = 1; i < SPEC_WAVES; ++i) t += red[i];
-    return t;
-}
-
-// Frame t of the joint at `base`: valid iff both coordinates are finite and (conf == NULL or conf >= min_conf), pk_motion_stats' rule.
-// `w` is the window weight of a valid frame (0 of an invalid one): 1, or the periodic Hann window 0.5 - 0.5 cos(2 pi t / T).
+// Frame t of the joint at `base`, valid by `seq_frame`'s rule (pk_common.h).  `w` is the window weight of a valid frame (0 of an
+// invalid one): 1, or the periodic Hann window 0.5 - 0.5 cos(2 pi t / T).
 struct SpecFrame { double x, y, w; bool ok; };
 __device__ __forceinline__ SpecFrame spec_frame(const float* __restrict__ coords, const float* __restrict__ conf, size_t base, int K, int t, int T,
                                                 float min_conf, int window) {
-    const size_t i = base + (size_t)t * K;
-    const float x = coords[2 * i], y = coords[2 * i + 1];
+    const SeqFrame p = seq_frame(coords, conf, base, K, t, min_conf);
     SpecFrame f;
-    f.ok = isfinite(x) && isfinite(y) && (conf == nullptr || conf[i] >= min_conf);
-    f.x = (double)x;
-    f.y = (double)y;
+    f.ok = p.ok;
+    f.x = p.x;
+    f.y = p.y;
     f.w = !f.ok ? 0.0 : (window ? 0.5 - 0.5 * cos(SPEC_TWO_PI * ((double)t / (double)T)) : 1.0);
     return f;
 }
 
 // Everything float64 on the exactly widened float32 inputs, one rounding per operation (-ffp-contract=off: no FMA).
 //   1. n, W = sum w_t, sum w_t x_t, sum w_t y_t over the valid frames: thread i takes frames i, i + 256, ... in ascending order, then
-//      `spec_block_sum`.  m = (sum w x / W, sum w y / W).  n < 2 or not W > 0: the 64 bins are 0.
+//      `block_reduce` (pk_common.h).  m = (sum w x / W, sum w y / W).  n < 2 or not W > 0: the 64 bins are 0.
 //   2. The frames pass through LDS in tiles of 256: thread i stores u_t = w_t (p_t - m) of frame tile + i (0 for an invalid frame, which
 //      adds +-0 to every sum).  Wave w then walks frames 64 w .. 64 w + 63 of the tile in ascending order; all its lanes read the same
 //      u_t (one address: a broadcast), lane l multiplies it with (cos, sin) of ITS bin's phase and adds to its four sums.  The phase is
@@ -81,8 +63,9 @@ __global__ void __launch_bounds__(SPEC_THREADS) k_motion_spectrum(const float* _
         swx += f.w * f.x;
         swy += f.w * f.y;
     }
-    const int n = spec_block_sum(n_valid, red_i);
-    const double W = spec_block_sum(sw, red_d), SX = spec_block_sum(swx, red_d), SY = spec_block_sum(swy, red_d);
+    const int n = block_reduce<SPEC_WAVES>(n_valid, red_i, SumOp());
+    const double W = block_reduce<SPEC_WAVES>(sw, red_d, SumOp()), SX = block_reduce<SPEC_WAVES>(swx, red_d, SumOp()),
+                 SY = block_reduce<SPEC_WAVES>(swy, red_d, SumOp());
     if (blockIdx.y == 0 && threadIdx.x == 0) {
         summary[(size_t)sk * 6] = (double)n;
         summary[(size_t)sk * 6 + 1] = W;
@@ -152,7 +135,7 @@ __global__ void __launch_bounds__(SPEC_THREADS) k_motion_spectrum(const float* _
 }
 
 // Columns 2-5 of the summary from the stored power row.  Thread i takes bins i, i + 256, ... in ascending order, then the block
-// combines: sums by `spec_block_sum`, the peak as the largest power with the lowest bin among equal ones (exact in any order).
+// combines: sums by `block_reduce`, the peak as the largest power with the lowest bin among equal ones (exact in any order).
 __global__ void __launch_bounds__(SPEC_THREADS) k_spectrum_summary(const double* __restrict__ power, double* __restrict__ summary, int j0, int F) {
     __shared__ double red_d[SPEC_WAVES];
     __shared__ double best_p[SPEC_WAVES];
@@ -173,7 +156,8 @@ __global__ void __launch_bounds__(SPEC_THREADS) k_spectrum_summary(const double*
         if (op > bp || (op == bp && oj < bj)) bp = op, bj = oj;
     }
     if ((threadIdx.x & 63) == 0) best_p[threadIdx.x >> 6] = bp, best_j[threadIdx.x >> 6] = bj;
-    const double total = spec_block_sum(sum, red_d), mom = spec_block_sum(moment, red_d);       // its barriers also publish best_*
+    // the barriers of block_reduce also publish best_*
+    const double total = block_reduce<SPEC_WAVES>(sum, red_d, SumOp()), mom = block_reduce<SPEC_WAVES>(moment, red_d, SumOp());
     if (threadIdx.x == 0) {
         for (int w = 1; w < SPEC_WAVES; ++w)
             if (best_p[w] > bp || (best_p[w] == bp && best_j[w] < bj)) bp = best_p[w], bj = best_j[w];
@@ -189,10 +173,10 @@ __global__ void __launch_bounds__(SPEC_THREADS) k_spectrum_summary(const double*
 extern "C" int pk_motion_spectrum(const float* coords, const float* conf, double* power, double* summary, int S, int T, int K, float min_conf,
                                   int N, int j0, int F, int window, void* stream) {
     PK_REQUIRE(coords && power && summary, "pk_motion_spectrum: null pointer");
-    PK_REQUIRE(S > 0 && T >= 1 && K > 0 && (int64_t)S * K <= 0x7fffffff, "pk_motion_spectrum: bad shape S=%d T=%d K=%d", S, T, K);
+    if (const int rc = seq_shape_check("pk_motion_spectrum", S, T, K)) return rc;
     PK_REQUIRE(window == 0 || window == 1, "pk_motion_spectrum: window %d (0 rectangular, 1 Hann)", window);
-    PK_REQUIRE(N >= 2 && N <= SPEC_MAX_NFFT, "pk_motion_spectrum: transform length N=%d (2 to %d)", N, SPEC_MAX_NFFT);
-    PK_REQUIRE(F >= 1 && F <= SPEC_MAX_BINS, "pk_motion_spectrum: %d bins (1 to %d)", F, SPEC_MAX_BINS);
+    PK_REQUIRE(N >= 2 && N <= PK_SPEC_MAX_NFFT, "pk_motion_spectrum: transform length N=%d (2 to %d)", N, PK_SPEC_MAX_NFFT);
+    PK_REQUIRE(F >= 1 && F <= PK_SPEC_MAX_BINS, "pk_motion_spectrum: %d bins (1 to %d)", F, PK_SPEC_MAX_BINS);
     PK_REQUIRE(j0 >= 1, "pk_motion_spectrum: first bin j0=%d (the mean is removed: there is no bin 0)", j0);
     PK_REQUIRE((int64_t)j0 + F - 1 <= N / 2, "pk_motion_spectrum: bins %d to %lld lie beyond N / 2 = %d", j0, (long long)j0 + F - 1, N / 2);
     hipLaunchKernelGGL(k_motion_spectrum, dim3(S * K, (F + SPEC_BINS - 1) / SPEC_BINS), dim3(SPEC_THREADS), 0, (hipStream_t)stream, coords, conf,

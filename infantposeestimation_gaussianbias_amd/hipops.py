@@ -207,8 +207,8 @@ def coco_kpt_eval(oks, oks_off, gt_off, gt_area, gt_flags, cap_off, cap_idx, dt_
     return out
 
 
-OKS_NMS_MAX_POSES = 1024      # poses per image pk_oks_nms holds in LDS
-OKS_NMS_MAX_K = 64
+OKS_NMS_MAX_POSES = _lib.CONSTANTS["PK_NMS_MAX_POSES"]      # poses per image pk_oks_nms holds in LDS
+OKS_NMS_MAX_K = _lib.CONSTANTS["PK_NMS_MAX_K"]
 
 
 def pose_rescore(kpt, box_score=None, in_vis_thr=0.2):
@@ -600,8 +600,8 @@ def nms_pose(preds, maxvals, distance_threshold=5.0):
 
 
 # ------------------------------------------------------------------------------------------------ movement analysis and PCK
-PCK_MAX_THRESHOLDS = 16
-HIST_MAX_BINS = 16384
+PCK_MAX_THRESHOLDS = _lib.CONSTANTS["PK_PCK_MAX_THR"]
+HIST_MAX_BINS = _lib.CONSTANTS["PK_HIST_MAX_BINS"]
 
 
 def pck_buffers(num_keypoints, n_thr, device):
@@ -672,8 +672,8 @@ def position_histogram(coords, edges_x, edges_y, conf=None, min_conf=0.3):
     return counts
 
 
-SPECTRUM_MAX_BINS = 16384
-SPECTRUM_MAX_NFFT = 1 << 30
+SPECTRUM_MAX_BINS = _lib.CONSTANTS["PK_SPEC_MAX_BINS"]
+SPECTRUM_MAX_NFFT = _lib.CONSTANTS["PK_SPEC_MAX_NFFT"]
 
 
 def motion_spectrum(coords, conf=None, min_conf=0.3, n_fft=None, j0=1, n_bins=None, window=1):

@@ -168,6 +168,35 @@ def test_the_three_entries_are_declared_and_check_their_arguments():
     assert L.pk_position_histogram(p, None, None, p, p, 1, 5, 1, 4, 4, 0.3, None) == -1
 
 
+def test_the_limits_of_the_analysis_entries_come_from_the_public_header():
+    """The six limits that the library and the op layer both check: one #define each in include/posekernels.h, parsed by _lib, carried by
+    the hipops names and printed by the entries that refuse a value beyond them (PCK, histogram, spectrum, rescoring / OKS-NMS)."""
+    from infantposeestimation_gaussianbias_amd import _lib, hipops
+    want = {"PK_PCK_MAX_THR": 16, "PK_HIST_MAX_BINS": 16384, "PK_SPEC_MAX_BINS": 16384, "PK_SPEC_MAX_NFFT": 1073741824, "PK_NMS_MAX_K": 64,
+            "PK_NMS_MAX_POSES": 1024}
+    assert {k: _lib.CONSTANTS.get(k) for k in want} == want
+    assert _lib.CONSTANTS == _lib.declared_constants() and _lib.CONSTANTS["PK_REDUCE_BLOCKS"] == 1024 and _lib.CONSTANTS["PK_OHKM_MAX_K"] == 256
+    assert (hipops.PCK_MAX_THRESHOLDS, hipops.HIST_MAX_BINS, hipops.SPECTRUM_MAX_BINS, hipops.SPECTRUM_MAX_NFFT, hipops.OKS_NMS_MAX_K,
+            hipops.OKS_NMS_MAX_POSES) == (16, 16384, 16384, 1073741824, 64, 1024)
+    L, p = _lib.lib, 64                                           # a non-null pointer value that is never dereferenced: the checks refuse first
+    err = lambda: L.pk_last_error_string().decode()
+    assert L.pk_pck(p, p, p, p, p, p, p, p, 4, 3, 17, None) == -1 and err() == "pk_pck: 17 thresholds (1 to 16)"
+    assert L.pk_position_histogram(p, None, p, p, p, 1, 5, 1, 128, 129, 0.3, None) == -2
+    assert err() == "pk_position_histogram: 128 x 129 bins exceed the 16384 a workgroup keeps in LDS; take larger bins"
+    assert L.pk_motion_spectrum(p, None, p, p, 1, 5, 1, 0.3, 1 << 20, 1, 16385, 0, None) == -1
+    assert err() == "pk_motion_spectrum: 16385 bins (1 to 16384)"
+    assert L.pk_motion_spectrum(p, None, p, p, 1, 5, 1, 0.3, (1 << 30) + 1, 1, 4, 0, None) == -1
+    assert err() == "pk_motion_spectrum: transform length N=1073741825 (2 to 1073741824)"
+    assert L.pk_pose_rescore(p, None, p, 3, 65, 0.2, None) == -1 and err() == "pk_pose_rescore: bad size (N 3, K 65; 1 <= K <= 64)"
+    assert L.pk_oks_nms(p, p, p, p, p, p, p, p, p, 2, 65, 0.9, 0.2, 0, 20, None) == -1
+    assert err() == "pk_oks_nms: bad size (n_img 2, K 65; 1 <= K <= 64)"
+    # the poses of an image are device data: the op layer counts them on the host and refuses before any device work
+    n, va = hipops.OKS_NMS_MAX_POSES + 1, torch.ones(17, dtype=torch.float64)
+    with pytest.raises(_lib.PoseKernelError, match="image 0 holds 1025 poses; the kernel is built for at most 1024 per image"):
+        hipops.oks_nms(torch.zeros(n, 17, 3, dtype=torch.float64), torch.ones(n, dtype=torch.float64), torch.ones(n, dtype=torch.float64),
+                       np.array([0, n], np.int32), va, 0.9)
+
+
 def test_op_layer_refuses_mismatched_shapes_before_any_launch(monkeypatch):
     from infantposeestimation_gaussianbias_amd import hipops
 
