@@ -335,6 +335,32 @@ int pk_adamw_step_ema(float* param, const float* grad, float* exp_avg, float* ex
                       uint16_t* param_bf16, int64_t n, const float* lr_dev, const int32_t* step_dev,
                       float beta1, float beta2, float eps, float weight_decay, float grad_scale,
                       const int32_t* guard_state, float* ema, float ema_decay, void* stream);
+/* Per-tensor statistics of a flat fp32 buffer (opt-in diagnostics: which tensor was non-finite, gradient flow, weight scale, update
+ * size): a segmented reduction in two launches, no atomics, every sum in an order the plan fixes (same bits eager, on any stream, replayed).
+ * x = a[i], or with b given a[i] - b[i] rounded once to fp32; an element takes part iff flags == NULL or its flag has bit1 set.
+ * Segment table (host): n_tensors rows {int64 offset, int64 count}; offsets in elements and multiples of 4, counts >= 1.  Elements between
+ * offset + count and the next offset are padding and are never read.
+ * Record (PK_TENSOR_STATS_RECORD_BYTES each, table order):
+ *   +0 f64 sum x | +8 f64 sum x^2 (squares formed in fp64) | +16 f64 sum |x| | +24 f32 min (+inf if none) | +28 f32 max (-inf if none)
+ *   | +32 i64 participating elements | +40 i64 of them inf / NaN (exponent bits all ones) | +48 i64 finite with |x| <= tiny | +56 i64 0.
+ *   Sums, min, max and the small count run over the finite participating elements only.
+ * pk_tensor_stats_plan: builds the launch plan on the host from the table and returns the item count (one item per tensor and chunk of
+ *   pk_tensor_stats_chunk_elems() elements); plan_out_host NULL: count only.  The plan is pk_tensor_stats_plan_bytes(n_items, n_tensors)
+ *   bytes: 16-byte rows, n_tensors of {int32 first_item, int32 n_items, int64 0}, then n_items of {int64 first element, int32 count,
+ *   int32 tensor}; it carries the table, so the device needs no other copy of it.  The caller uploads it once.
+ * pk_tensor_stats: partial kernel (one wave per item, four items per workgroup) and finalize kernel (one wave per tensor).  ws:
+ *   pk_tensor_stats_ws_bytes(n_items, n_tensors) bytes; a, b, plan, ws, records 16-byte aligned, flags 4-byte; tiny finite and >= 0.
+ *   The caller guarantees that a, b and flags cover every offset + count of the table.
+ * pk_tensor_stats_latch: one workgroup.  If any record has a non-finite count > 0: latched <- all n_tensors records, latch_state
+ *   (4 int32) = {events + 1, first offending tensor, last offending tensor, offending tensors}.  Otherwise nothing is written.        */
+#define PK_TENSOR_STATS_RECORD_BYTES 64
+int pk_tensor_stats_chunk_elems(void);
+int pk_tensor_stats_plan(const int64_t* seg_host, int n_tensors, void* plan_out_host, int64_t capacity_bytes);
+int pk_tensor_stats_plan_bytes(int n_items, int n_tensors);
+int pk_tensor_stats_ws_bytes(int n_items, int n_tensors);
+int pk_tensor_stats(const float* a, const float* b, const uint8_t* flags, const void* plan_dev, int n_tensors, int n_items, float tiny,
+                    void* ws, int64_t ws_bytes, void* records, void* stream);
+int pk_tensor_stats_latch(const void* records, int n_tensors, void* latched, int32_t* latch_state, void* stream);
 
 
 /* ======================= network contractions (bf16 MFMA, fp32 accumulate; NHWC activations) =======================

@@ -10,6 +10,7 @@ Semantics follow train.py:55-128: AdamW(lr 5e-4, betas (.9,.999), wd .01 on the 
 contains 'bias' / 'bn' / 'norm' are not decayed; parameters that never receive a gradient (41 tensors for
 HRFormer-small) are left untouched exactly as torch.optim.AdamW skips `grad is None`.
 """
+import collections
 import contextlib
 import math
 import os
@@ -53,7 +54,7 @@ class FlatAdamW:
     ALIGN = 4            # elements: every tensor starts 16-byte aligned inside the flat buffers
 
     def __init__(self, model: torch.nn.Module, lr=5e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, direct_grads=False,
-                 clip_grad_norm=0.0, skip_nonfinite=False, ema_decay=0.0):
+                 clip_grad_norm=0.0, skip_nonfinite=False, ema_decay=0.0, trace_nonfinite=False):
         """`clip_grad_norm` > 0 (torch.nn.utils.clip_grad_norm_'s max_norm) or `skip_nonfinite` select the guarded step: the global
         gradient norm is reduced on the device, the update is scaled by the clip coefficient and dropped as a whole when a gradient is
         inf / NaN (what GradScaler.step does in the reference).  A non-finite norm cannot clip anything, so clipping implies skipping.
@@ -61,7 +62,11 @@ class FlatAdamW:
         `ema_decay` in (0, 1) keeps an exponential moving average of the masters in `self.ema`, written by the update kernel itself
         (pk_adamw_step_ema): e += (1 - d_t) (p_new - e) with d_t = min(ema_decay, (1 + t) / (10 + t)), t = applied updates.  It moves
         only when the masters do (a skipped step freezes it), and only on the elements the optimiser updates.  0 = off: no buffer, and
-        the launches are the ones above."""
+        the launches are the ones above.
+
+        `trace_nonfinite` adds the per-tensor gradient statistics (pk_tensor_stats) and their latch to every step, between the guard's
+        reduction and the update: when a gradient is inf / NaN the records of that step stay in `trace_latched` until the next such
+        step, and `nonfinite_trace()` names the tensors.  Off: no launch, no buffer."""
         if not (math.isfinite(clip_grad_norm) and clip_grad_norm >= 0):
             raise ValueError(f"clip_grad_norm must be finite and >= 0 (0 = off), got {clip_grad_norm}")
         if not (math.isfinite(ema_decay) and 0 <= ema_decay < 1):
@@ -105,6 +110,15 @@ class FlatAdamW:
             self.guard_state = torch.zeros(hipops.GUARD_STATE_WORDS, dtype=torch.int32, device=dev)
         # static as well: the averaged weights, starting as a copy of the masters (padding and inactive elements keep that copy)
         self.ema = self.flat.clone() if self.ema_decay > 0 else None
+        # per-tensor statistics: nothing exists until tensor_stats / snapshot_params are called or the trace is on
+        self._stats_plan = None
+        self.snapshot = None
+        self.trace_nonfinite = bool(trace_nonfinite)
+        if self.trace_nonfinite:
+            plan = self._need_stats_plan()
+            self.trace_records = torch.zeros_like(plan.records)          # the trace's own: a logged tensor_stats call leaves them alone
+            self.trace_latched = torch.zeros_like(plan.records)
+            self.trace_state = torch.zeros(hipops.LATCH_STATE_WORDS, dtype=torch.int32, device=dev)
 
     # -- gradient storage ---------------------------------------------------------------------------------
     def grad_view(self, i):
@@ -170,6 +184,10 @@ class FlatAdamW:
             hipops.grad_guard_finalize(self.guard_partials, grad_scale, self.clip_grad_norm, self.guard_state, self.step_dev)
         else:
             self.step_dev.add_(1)
+        if self.trace_nonfinite:
+            # static buffers throughout: inside a captured step these three launches are replayed with it
+            hipops.tensor_stats(self._stats_plan, self.grad, flags=self.flags, records=self.trace_records)
+            hipops.tensor_stats_latch(self.trace_records, len(self.params), self.trace_latched, self.trace_state)
         if self.ema is not None:
             # update and average in one pass; the kernel reads the skip decision and the step count where the update reads them
             hipops.adamw_step_ema(self.flat, self.grad, self.exp_avg, self.exp_avg_sq, self.flags, None, self.lr_dev, self.step_dev,
@@ -241,6 +259,62 @@ class FlatAdamW:
         norm, coef = st[:2].view(torch.float32).tolist()
         return {"grad_norm": norm, "clip_coef": coef, "skipped_last": int(st[2]), "skipped_steps": int(st[3])}
 
+    # -- per-tensor statistics ---------------------------------------------------------------------------------
+    STATS_BUFFERS = ("grad", "param", "exp_avg", "exp_avg_sq", "ema", "update")
+
+    def _need_stats_plan(self):
+        if self._stats_plan is None:
+            # one upload of the plan; the table never changes, so the same launches can sit in a graph
+            self._stats_plan = hipops.TensorStatsPlan(self.offsets, [p.numel() for p in self.params], self.flat.device)
+        return self._stats_plan
+
+    def _stats_buffer(self, which, who):
+        if which == "ema":
+            self._need_ema(who)
+            return self.ema
+        if which not in ("grad", "param", "exp_avg", "exp_avg_sq"):
+            raise ValueError(f"{who}: unknown buffer '{which}' (one of {', '.join(self.STATS_BUFFERS)})")
+        return {"grad": self.grad, "param": self.flat, "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq}[which]
+
+    def snapshot_params(self):
+        """snapshot <- flat on the current stream (a static buffer, allocated on first use): tensor_stats("update") is then the
+        statistics of flat - snapshot, i.e. of everything the steps since have done to the weights."""
+        if self.snapshot is None:
+            self.snapshot = torch.empty_like(self.flat)
+        self.snapshot.copy_(self.flat)
+
+    def tensor_stats(self, which="grad", against=None, tiny=0.0, scale=1.0):
+        """Per-tensor statistics of one flat buffer ("grad", "param", "exp_avg", "exp_avg_sq", "ema"), of `which - against`, or with
+        "update" of flat - snapshot: {name: {mean, std, min, max, norm, abs_mean, abs_max, numel, nonfinite, small}} in parameter
+        order, over the finite elements the optimiser updates (`small`: |x| <= tiny; inactive tensors have numel 0).  `scale`
+        multiplies the linear values (comm.grad_scale: the gradients the update sees).  Two launches on the current stream and ONE
+        device read of 64 bytes per tensor: for the log interval, never for the step path."""
+        if which == "update":
+            if against is not None:
+                raise ValueError("tensor_stats: 'update' is flat - snapshot already; it takes no `against`")
+            if self.snapshot is None:
+                raise RuntimeError("tensor_stats: 'update' needs a snapshot (snapshot_params(), or Trainer.step(batch, snapshot=True))")
+            a, b = self.flat, self.snapshot
+        else:
+            a = self._stats_buffer(which, "tensor_stats")
+            b = None if against is None else self._stats_buffer(against, "tensor_stats")
+        plan = self._need_stats_plan()
+        recs = hipops.tensor_stats_records(hipops.tensor_stats(plan, a, b, self.flags, tiny))
+        return collections.OrderedDict((n, hipops.derive_tensor_stats(r, scale)) for n, r in zip(self.names, recs))
+
+    def nonfinite_trace(self):
+        """None while no step held a non-finite gradient; else {"events": how many steps did, "tensors": {name: non-finite elements}
+        of the latest one, "first", "last": the first and last of them in parameter order}.  `last` is the tensor nearest the loss,
+        the one to look at once NaN has spread backwards.  One device read."""
+        if not self.trace_nonfinite:
+            raise RuntimeError("nonfinite_trace: the trace is off (trace_nonfinite=False)")
+        events, first, last, _ = self.trace_state.tolist()
+        if events == 0:
+            return None
+        recs = hipops.tensor_stats_records(self.trace_latched)
+        tensors = collections.OrderedDict((n, int(r["nonfinite"])) for n, r in zip(self.names, recs) if r["nonfinite"] > 0)
+        return {"events": events, "tensors": tensors, "first": self.names[first], "last": self.names[last]}
+
     # -- checkpoint format of the reference (train.py:351-357): per-parameter state keyed by index ---------------
     def state_dict(self):
         decay = [i for i, n in enumerate(self.names) if not is_no_decay(n)]
@@ -280,6 +354,13 @@ class FlatAdamW:
         self.step_dev.fill_(steps)
         if sd.get("param_groups"):
             self.set_lr(float(sd["param_groups"][0]["lr"]))
+
+
+def update_to_weight_ratio(update_stats, param_stats):
+    """norm(update) / norm(param) per tensor from tensor_stats("update") and tensor_stats("param"); nan where the weights are all zero
+    (or the tensor is inactive)."""
+    return collections.OrderedDict((n, u["norm"] / param_stats[n]["norm"] if param_stats[n]["norm"] > 0 else float("nan"))
+                                   for n, u in update_stats.items())
 
 
 class WarmupMultiStepLR:
@@ -443,7 +524,7 @@ class Trainer:
 
     def __init__(self, model, cfg, iters_per_epoch: int, bucket_mb: float = 8.0, use_graph: bool = False, graph_warmup: int = 3,
                  overlap_comm: bool = True, graph_streams: bool = False, clip_grad_norm: float = 0.0, skip_nonfinite: bool = False,
-                 ema_decay: float = 0.0):
+                 ema_decay: float = 0.0, trace_nonfinite: bool = False):
         self.model, self.cfg = model, cfg
         self.overlap_comm = overlap_comm
         # concurrent branch streams: on for eager steps; inside a captured graph only on request (fork/join capture across
@@ -458,7 +539,7 @@ class Trainer:
         # optimiser between forward+backward-only replays all take it; the LR schedule advances on skipped steps too (as the
         # reference's scheduler.step() does)
         self.opt = FlatAdamW(model, t.lr, tuple(t.betas), 1e-8, t.weight_decay, direct_grads=True, clip_grad_norm=clip_grad_norm,
-                             skip_nonfinite=skip_nonfinite, ema_decay=ema_decay)
+                             skip_nonfinite=skip_nonfinite, ema_decay=ema_decay, trace_nonfinite=trace_nonfinite)
         self.sched = WarmupMultiStepLR(self.opt, t, iters_per_epoch)
         self.comm = GradientExchange(self.opt, bucket_mb, overlap=overlap_comm)
         self.comm.broadcast_initial_state()
@@ -617,8 +698,12 @@ class Trainer:
             self.opt.swap_ema()
             self.model.train(was_training)
 
-    def step(self, batch):
+    def step(self, batch, snapshot=False):
+        """`snapshot`: copy the masters first (FlatAdamW.snapshot_params, eager, between replays), so that tensor_stats("update")
+        afterwards describes this step's update."""
         from . import dispatch
+        if snapshot:
+            self.opt.snapshot_params()
         dispatch.set_streams(self._want_streams)
         dispatch.set_region_mode(self._region)    # capturable fork/join (one autograd node per parallel region)
         nnops.set_milestone_callback(self._ms_cb)  # process-wide hook: the trainer that steps owns it

@@ -870,3 +870,107 @@ def adamw_step_ema(param, grad, exp_avg, exp_avg_sq, flags, param_bf16, lr_dev, 
         raise _lib.PoseKernelError(f"adamw_step_ema: ema must be a contiguous buffer of {param.numel()} floats (updated in place)")
     call("pk_adamw_step_ema", param, grad, exp_avg, exp_avg_sq, flags, param_bf16, param.numel(), lr_dev, step_dev, float(beta1),
          float(beta2), float(eps), float(weight_decay), float(grad_scale), guard_state, ema, float(ema_decay), stream_ptr())
+
+
+# ------------------------------------------------------------------------------------------------ per-tensor statistics
+# pk_tensor_stats: a segmented reduction over a flat fp32 buffer in two launches on the current stream; one 64-byte record per tensor.
+TENSOR_STATS_RECORD = np.dtype([("sum", "<f8"), ("sumsq", "<f8"), ("sumabs", "<f8"), ("min", "<f4"), ("max", "<f4"), ("n", "<i8"),
+                                ("nonfinite", "<i8"), ("small", "<i8"), ("zero", "<i8")])
+assert TENSOR_STATS_RECORD.itemsize == _lib.CONSTANTS["PK_TENSOR_STATS_RECORD_BYTES"]
+LATCH_STATE_WORDS = 4          # {int32 events, first offending tensor, last offending tensor, offending tensors}
+
+
+def _query(name, *args):
+    k = getattr(_lib.lib, name)(*args)
+    if k <= 0:
+        raise _lib.PoseKernelError(f"{name} failed: {_lib.lib.pk_last_error_string().decode()}")
+    return k
+
+
+def tensor_stats_chunk_elems():
+    return _query("pk_tensor_stats_chunk_elems")
+
+
+def tensor_stats_plan_host(offsets, counts):
+    """The launch plan of a segment table, built by the library on the host: (plan as a uint8 numpy array, n_items)."""
+    seg = np.ascontiguousarray(np.stack([np.asarray(offsets, np.int64), np.asarray(counts, np.int64)], axis=1))
+    if seg.ndim != 2 or seg.shape[0] == 0:
+        raise _lib.PoseKernelError("tensor_stats_plan_host: the segment table is empty")
+    n_items = _query("pk_tensor_stats_plan", seg.ctypes.data, seg.shape[0], None, 0)
+    plan = np.zeros(_query("pk_tensor_stats_plan_bytes", n_items, seg.shape[0]) // 8, np.int64)
+    if _query("pk_tensor_stats_plan", seg.ctypes.data, seg.shape[0], plan.ctypes.data, plan.nbytes) != n_items:
+        raise _lib.PoseKernelError("pk_tensor_stats_plan: the item count changed between two calls")
+    return plan.view(np.uint8), n_items
+
+
+class TensorStatsPlan:
+    """Static device memory of one segment table: the uploaded plan, the partial workspace and the records.  Built once (one
+    host-to-device copy), so that `tensor_stats` allocates and copies nothing and can be captured."""
+
+    def __init__(self, offsets, counts, device):
+        self.offsets, self.counts = [int(o) for o in offsets], [int(c) for c in counts]
+        self.n_tensors = len(self.offsets)
+        plan, self.n_items = tensor_stats_plan_host(self.offsets, self.counts)
+        self.extent = max(o + c for o, c in zip(self.offsets, self.counts))
+        self.plan = torch.from_numpy(plan.copy()).to(device)
+        self.ws = torch.empty(_query("pk_tensor_stats_ws_bytes", self.n_items, self.n_tensors), dtype=torch.uint8, device=device)
+        self.records = torch.zeros(self.n_tensors * TENSOR_STATS_RECORD.itemsize, dtype=torch.uint8, device=device)
+
+
+def tensor_stats(plan, a, b=None, flags=None, tiny=0.0, records=None):
+    """Records of `a` (or of a - b, rounded once to fp32) over `plan`'s tensors, elements with flag bit1 only when `flags` is given.
+    Returns the records tensor (uint8, n_tensors x 64 bytes; `plan.records` unless another is passed).  No allocation, copy or sync."""
+    if not isinstance(plan, TensorStatsPlan):
+        raise _lib.PoseKernelError("tensor_stats: plan must be a TensorStatsPlan")
+    for t, name, dt in ((a, "a", F32), (b, "b", F32), (flags, "flags", torch.uint8)):
+        if t is None and name != "a":
+            continue
+        _chk(t, dt, name)
+        if not t.is_contiguous() or t.numel() < plan.extent or t.device != plan.plan.device:
+            raise _lib.PoseKernelError(f"tensor_stats: {name} must be a contiguous buffer of at least {plan.extent} elements on "
+                                       f"{plan.plan.device}")
+    records = plan.records if records is None else records
+    if _chk(records, torch.uint8, "records").numel() != plan.records.numel() or not records.is_contiguous():
+        raise _lib.PoseKernelError(f"tensor_stats: records must be {plan.records.numel()} contiguous bytes")
+    call("pk_tensor_stats", a, b, flags, plan.plan, plan.n_tensors, plan.n_items, float(tiny), plan.ws, plan.ws.numel(), records,
+         stream_ptr())
+    return records
+
+
+def tensor_stats_latch(records, n_tensors, latched, latch_state):
+    """If any record counts a non-finite element: latched <- records, latch_state <- {events + 1, first, last, how many}; else nothing."""
+    if _chk(latch_state, I32, "latch_state").numel() != LATCH_STATE_WORDS:
+        raise _lib.PoseKernelError(f"latch_state: expected {LATCH_STATE_WORDS} int32 words, got {latch_state.numel()}")
+    need = n_tensors * TENSOR_STATS_RECORD.itemsize
+    if _chk(records, torch.uint8, "records").numel() != need or _chk(latched, torch.uint8, "latched").numel() != need:
+        raise _lib.PoseKernelError(f"tensor_stats_latch: records and latched must be {need} bytes each")
+    call("pk_tensor_stats_latch", records, int(n_tensors), latched, latch_state, stream_ptr())
+
+
+def tensor_stats_records(records):
+    """The records tensor as a numpy structured array (ONE device read)."""
+    return records.cpu().numpy().view(TENSOR_STATS_RECORD)
+
+
+def derive_tensor_stats(rec, scale=1.0):
+    """The reported values of one raw record, in float64: the reference's mean / std / min / max / norm (std: population value, clamped
+    at 0), abs_mean / abs_max, and the counts.  `scale` multiplies the linear quantities.  A tensor without a finite participating
+    element has mean = std = nan.  Pure host arithmetic: `rec` is anything indexable by the record's field names."""
+    n, bad = int(rec["n"]), int(rec["nonfinite"])
+    m, s = n - bad, abs(float(scale))
+    out = {"numel": n, "nonfinite": bad, "small": int(rec["small"])}
+    sc = float(scale)
+    lo, hi = float(rec["min"]) * sc, float(rec["max"]) * sc
+    out["min"], out["max"] = (lo, hi) if sc >= 0 else (hi, lo)
+    out["norm"] = s * math.sqrt(float(rec["sumsq"]))
+    out["abs_max"] = max(abs(float(rec["min"])), abs(float(rec["max"]))) * s if m else 0.0
+    if m == 0:
+        out["mean"] = out["std"] = out["abs_mean"] = float("nan")
+        return out
+    mean = float(rec["sum"]) / m
+    out["mean"] = mean * sc
+    # E[x^2] - mean^2 cancels to rounding noise of either sign on a constant tensor: min == max says so exactly
+    var = 0.0 if rec["min"] == rec["max"] else max(float(rec["sumsq"]) / m - mean * mean, 0.0)
+    out["std"] = s * math.sqrt(var)
+    out["abs_mean"] = s * float(rec["sumabs"]) / m
+    return out

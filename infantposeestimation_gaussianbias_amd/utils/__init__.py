@@ -3,6 +3,8 @@ from .metrics import (AverageMeter, COCOEvaluator, MetricLogger, PCKAccumulator,
                       calculate_temporal_consistency, movement_heatmap, movement_report, movement_spectrum)
 from . import postprocess
 from .postprocess import oks_nms, soft_oks_nms
+from . import tensor_stats
+from .tensor_stats import gradient_flow, gradient_statistics, tensor_statistics, weight_statistics
 from . import visualization
 from .visualization import (COCO_COLORS, COCO_SKELETON, create_grid_image, draw_bbox, draw_heatmaps, draw_person_heatmaps, draw_poses,
                             draw_skeleton, save_person_visualization, save_visualization)
@@ -10,4 +12,5 @@ from .visualization import (COCO_COLORS, COCO_SKELETON, create_grid_image, draw_
 __all__ = ['AverageMeter', 'COCOEvaluator', 'MetricLogger', 'postprocess', 'visualization', 'draw_skeleton', 'draw_heatmaps', 'draw_bbox',
            'draw_poses', 'draw_person_heatmaps', 'create_grid_image', 'save_visualization', 'save_person_visualization', 'COCO_SKELETON',
            'COCO_COLORS', 'PCKAccumulator', 'calculate_movement_amplitude', 'calculate_pck', 'calculate_temporal_consistency',
-           'movement_heatmap', 'movement_report', 'movement_spectrum', 'oks_nms', 'soft_oks_nms']
+           'movement_heatmap', 'movement_report', 'movement_spectrum', 'oks_nms', 'soft_oks_nms', 'tensor_stats', 'tensor_statistics',
+           'gradient_statistics', 'gradient_flow', 'weight_statistics']

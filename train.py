@@ -11,7 +11,9 @@ log interval), bf16 instead of fp16+GradScaler, fused AdamW over a flat paramete
 yaml), and an exponential moving average of the weights kept by the optimiser kernel (`--ema DECAY`): validation inside the loop then
 scores the averaged weights, and checkpoints carry them as "ema_state_dict" (validate.py / inference.py `--ema` load them), and online
 hard keypoint mining (`--ohkm TOPK [--ohkm_weight W]`, or LOSS.USE_OHKM / TOPK of a legacy yaml): per sample only the TOPK worst-fitted
-joints count in the heatmap loss, selected on the device inside the step; every validation interval logs which joints were selected.  With POSE_SYNTHETIC=1 the loader yields device-resident synthetic batches (no COCO on disk needed; they are not jittered).
+joints count in the heatmap loss, selected on the device inside the step; every validation interval logs which joints were selected, and
+per-tensor diagnostics reduced on the device (`--tensor_stats K`: at every log interval the K tensors with the largest gradient norm and
+with the smallest / largest update-to-weight ratio; `--trace_nonfinite`: which tensors held inf / NaN when a step's gradients did).  With POSE_SYNTHETIC=1 the loader yields device-resident synthetic batches (no COCO on disk needed; they are not jittered).
 """
 import argparse
 import contextlib
@@ -56,7 +58,28 @@ def save_checkpoint(model, trainer, epoch, metrics, output_dir, is_best=False):
         torch.save(ckpt, os.path.join(output_dir, f"epoch_{epoch}.pth"))
 
 
-def train_one_epoch(trainer, loader, epoch, cfg, logger, rank):
+def tensor_stats_report(opt, k, grad_scale=1.0):
+    """Three log lines from the flat buffers as the last step left them (which ran with snapshot=True): the k tensors with the largest
+    gradient norm, and the k with the smallest and the largest update-to-weight ratio.  Three statistics calls, three device reads."""
+    grad = opt.tensor_stats("grad", scale=grad_scale)
+    ratio = engine.update_to_weight_ratio(opt.tensor_stats("update"), opt.tensor_stats("param"))
+    by_norm = sorted((n for n, v in grad.items() if v["numel"]), key=lambda n: -grad[n]["norm"])[:k]
+    by_ratio = sorted((n for n, r in ratio.items() if r == r and grad[n]["numel"]), key=lambda n: ratio[n])
+    return ["largest grad norm: " + ", ".join(f"{n} {grad[n]['norm']:.3g}" for n in by_norm),
+            "smallest update/weight: " + ", ".join(f"{n} {ratio[n]:.3g}" for n in by_ratio[:k]),
+            "largest update/weight: " + ", ".join(f"{n} {ratio[n]:.3g}" for n in by_ratio[::-1][:k])]
+
+
+def nonfinite_report(opt, seen):
+    """(line or None, events so far): one line when steps with non-finite gradients happened since `seen` events."""
+    tr = opt.nonfinite_trace()
+    if tr is None or tr["events"] <= seen:
+        return None, seen
+    return (f"non-finite gradients in {tr['events'] - seen} step(s) since the last report; latest: {len(tr['tensors'])} tensors, nearest "
+            f"the loss: {tr['last']} ({tr['tensors'][tr['last']]} elements)"), tr["events"]
+
+
+def train_one_epoch(trainer, loader, epoch, cfg, logger, rank, tensor_stats=0, trace_state=None):
     loss_meter, batch_time = AverageMeter("Loss", ":.4f"), AverageMeter("Time", ":.3f")
     n = len(loader)
     log_interval = max(1, n // 10)
@@ -64,8 +87,9 @@ def train_one_epoch(trainer, loader, epoch, cfg, logger, rank):
     for i, batch in enumerate(loader):
         dev = next(trainer.model.parameters()).device
         batch = {k: (v.to(dev, non_blocking=True) if torch.is_tensor(v) else v) for k, v in batch.items()}
-        out = trainer.step(batch)
-        if i % log_interval == 0 or i == n - 1:          # the only host syncs of the epoch
+        logged = i % log_interval == 0 or i == n - 1
+        out = trainer.step(batch, snapshot=bool(tensor_stats) and logged and rank == 0)      # the copy is taken on log steps only
+        if logged:          # the only host syncs of the epoch
             loss_meter.update(float(out["loss"].detach()), batch["img"].size(0))
             batch_time.update((time.time() - end) / (log_interval if i else 1))
             end = time.time()
@@ -78,6 +102,13 @@ def train_one_epoch(trainer, loader, epoch, cfg, logger, rank):
                     gs = trainer.opt.guard_stats()
                     msg += f" | grad_norm: {gs['grad_norm']:.4g} clip_coef: {gs['clip_coef']:.4g} skipped_steps: {gs['skipped_steps']}"
                 logger.info(msg)
+                if tensor_stats:
+                    for line in tensor_stats_report(trainer.opt, tensor_stats, trainer.comm.grad_scale):
+                        logger.info(f"Epoch [{epoch}][{i}/{n}] {line}")
+                if trace_state is not None:
+                    line, trace_state["events"] = nonfinite_report(trainer.opt, trace_state["events"])
+                    if line:
+                        logger.info(f"Epoch [{epoch}][{i}/{n}] {line}")
     return loss_meter.avg
 
 
@@ -123,7 +154,9 @@ def main(args):
     loader = build_dataloader(cfg, is_train=True)
     model = build_model(cfg).to(torch.device("cuda", local))
     trainer = engine.Trainer(model, cfg, iters_per_epoch=len(loader), use_graph=args.graph, graph_streams=args.graph,
-                             clip_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite, ema_decay=cfg.train.ema_decay or 0.0)
+                             clip_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite, ema_decay=cfg.train.ema_decay or 0.0,
+                             trace_nonfinite=args.trace_nonfinite)
+    trace_state = {"events": 0} if args.trace_nonfinite else None
     start_epoch, best_ap = 0, 0.0
     if args.resume and os.path.isfile(args.resume):
         ckpt = torch.load(args.resume, map_location="cpu", weights_only=True)
@@ -141,7 +174,7 @@ def main(args):
         logger.info(f"Resumed from epoch {start_epoch}")
     val_loader = None
     for epoch in range(start_epoch, cfg.train.max_epochs):
-        loss = train_one_epoch(trainer, loader, epoch, cfg, logger, rank)
+        loss = train_one_epoch(trainer, loader, epoch, cfg, logger, rank, tensor_stats=args.tensor_stats, trace_state=trace_state)
         if rank == 0 and cfg.model.ohkm_topk and ((epoch + 1) % cfg.train.val_interval == 0 or epoch == cfg.train.max_epochs - 1):
             report = selection_report(model, cfg.data.keypoint_names)      # which joints are the hard ones
             if report:
@@ -198,6 +231,11 @@ def build_parser():
                    help="online hard keypoint mining: per sample only the TOPK joints with the largest heatmap error count (the fusion "
                         "loss gains the term ohkm_loss; the heatmap head's loss becomes the mined one; default: off)")
     p.add_argument("--ohkm_weight", type=float, default=None, metavar="W", help="weight of ohkm_loss in the fusion loss (default 1.0)")
+    p.add_argument("--tensor_stats", type=int, default=0, metavar="K",
+                   help="at every log interval log the K tensors with the largest gradient norm and the K with the smallest / largest "
+                        "update-to-weight ratio, reduced per tensor on the device (0 = off)")
+    p.add_argument("--trace_nonfinite", action="store_true",
+                   help="record on the device which tensors held inf / NaN gradients; logged at the log interval when it happened")
     return p
 
 
