@@ -235,6 +235,40 @@ int pk_position_histogram(const float* coords, const float* conf, const double* 
 int pk_motion_spectrum(const float* coords, const float* conf, double* power, double* summary, int S, int T, int K, float min_conf,
                        int N, int j0, int F, int window, void* stream);
 
+/* ---- localisation error analysis (this project's own specification, DESIGN.md "Localisation error analysis": the numbers behind the
+ * reference's PerformanceAnalyzer, analysis/nn_quantitative_viz.py:105-252).  One launch each; no float atomics, no global atomics; every
+ * output is an integer count, an order statistic or a fixed-order sum, so the same input gives the same bits.
+ * pk_kpt_error: pred, gt (N,K,2) f32; vis (N,K) f32; conf (N,K) f32 or NULL; norm (N) f32 or NULL.  err_out is a (K, ld) f32 matrix, ld >= N:
+ *   this launch writes columns 0..N-1 of each row (the caller passes the pointer already offset to its first free column).  calib_count,
+ *   calib_hit (K, n_bins) int64 and pr_hist (K, 2, T+1) int64 ACCUMULATE: the caller zeroes them once, every launch adds its batch.
+ *   Pair (n,k) counts iff vis > 0, its four coordinates are finite and, when norm is given, norm[n] > 0 (pk_pck's rule); an uncounted pair
+ *   writes NaN to err_out and touches no counter.  Error in float32, one rounding per operation, no FMA: dx = px - gx, dy = py - gy,
+ *   d2 = dx dx + dy dy, e = (float)sqrt((double)d2); with norm e = (float)((double)e / (double)norm[n]).  Both narrowings equal the correctly
+ *   rounded float32 operation and do not depend on how sqrtf or / are lowered.  hit = e < pixel_thr (strict).
+ *   conf == NULL: bin_edges, conf_thr and the three counters may be NULL as well; only the store is written.  With conf: a pair whose
+ *   confidence c is not finite stays in the store and enters neither calibration nor precision / recall.  Calibration: bin i of the
+ *   ascending bin_edges (n_bins + 1) takes e[i] <= c < e[i+1], anything outside is dropped, c == e[n_bins] included (the reference's rule,
+ *   not np.histogram's); there calib_count += 1, calib_hit += hit.  Precision / recall: m = the number of the ascending conf_thr (T) with
+ *   c > t_i, 0 <= m <= T; pr_hist[k][hit ? 0 : 1][m] += 1.  The host recovers the reference's counts at threshold i by suffix sums:
+ *   tp_i = sum_{m>i} pr_hist[.,0,m], fp_i = sum_{m>i} pr_hist[.,1,m], fn_i = sum_m pr_hist[.,0,m] - tp_i.
+ *   Refused before the launch: a null required pointer, N or K <= 0, ld < N, and with conf n_bins outside 1..PK_ERR_MAX_BINS or T outside
+ *   1..PK_ERR_MAX_CONF_THR (the int32 histograms one workgroup keeps in LDS).
+ * pk_kpt_error_quantiles: err (K, ld) f32, columns 0..n_cols-1 of each row; a NaN entry does not exist, every other value is non-negative
+ *   (its unsigned bit pattern orders it).  q (Q) float64 on the device, each in [0,1].  Per row with n values v[0] <= ... <= v[n-1]:
+ *   pos = q (double)(n - 1), lo = floor(pos), hi = min(lo + 1, n - 1); order (K,Q,2) f32 = v[lo], v[hi], found exactly by radix select over the
+ *   float bits (the interpolation between the two is the host's).  summary (K,4) float64 = n, sum, min, max; the sum in float64, per
+ *   thread in ascending column, then the block reduction.  n = 0: every output of the row is 0.
+ *   Refused before the launch: a null pointer, Q outside 1..PK_ERR_MAX_QUANTILES, K <= 0, n_cols outside 1..PK_ERR_MAX_COLS = 2^31 - 1, ld < n_cols.        */
+#define PK_ERR_MAX_BINS 256
+#define PK_ERR_MAX_CONF_THR 1024
+#define PK_ERR_MAX_QUANTILES 16
+#define PK_ERR_MAX_COLS 2147483647
+int pk_kpt_error(const float* pred, const float* gt, const float* vis, const float* conf /* or NULL */, const float* norm /* (N) or NULL */,
+                 float pixel_thr, const float* bin_edges /* (n_bins+1) */, int n_bins, const float* conf_thr /* (T) ascending */, int T,
+                 float* err_out, int64_t ld, int64_t* calib_count, int64_t* calib_hit, int64_t* pr_hist, int N, int K, void* stream);
+int pk_kpt_error_quantiles(const float* err, int64_t ld, int64_t n_cols, int K, const double* q /* (Q) device, each in [0,1] */, int Q,
+                           float* order /* (K,Q,2) */, double* summary /* (K,4) */, void* stream);
+
 /* ---- L1/L2: FusionPoseLoss.forward (models/fusion_head.py:745-806 with :405-559, :637-743) ---------------
  * stats: workspace of B*K*PK_LOSS_STAT floats + B*16*4 floats + 16 floats (see PK_LOSS_WS_FLOATS);
  * losses: 7 floats (heatmap, offset, peak, variance, overlap, shape, total — already multiplied by lambdas).

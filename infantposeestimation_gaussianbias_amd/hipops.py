@@ -702,6 +702,98 @@ def motion_spectrum(coords, conf=None, min_conf=0.3, n_fft=None, j0=1, n_bins=No
     return power, summary
 
 
+# ------------------------------------------------------------------------------------------------ localisation error analysis
+ERR_MAX_BINS = _lib.CONSTANTS["PK_ERR_MAX_BINS"]
+ERR_MAX_CONF_THRESHOLDS = _lib.CONSTANTS["PK_ERR_MAX_CONF_THR"]
+ERR_MAX_QUANTILES = _lib.CONSTANTS["PK_ERR_MAX_QUANTILES"]
+ERR_MAX_COLS = _lib.CONSTANTS["PK_ERR_MAX_COLS"]
+
+
+def kpt_error_buffers(num_keypoints, n_bins, n_thr, device):
+    """Zeroed counters of `kpt_error_accumulate`: calib_count, calib_hit (K, n_bins) int64 and pr_hist (K, 2, n_thr + 1) int64."""
+    return (torch.zeros(num_keypoints, n_bins, dtype=I64, device=device), torch.zeros(num_keypoints, n_bins, dtype=I64, device=device),
+            torch.zeros(num_keypoints, 2, n_thr + 1, dtype=I64, device=device))
+
+
+def kpt_error_accumulate(pred, gt, visible, store, column, pixel_threshold, confidence=None, normalizer=None, bin_edges=None,
+                         conf_thresholds=None, calib_count=None, calib_hit=None, pr_hist=None):
+    """One batch into the error store and the counters, in place (pk_kpt_error; no synchronisation).  pred, gt (N,K,2); visible (N,K);
+    store (K, capacity) float32, row-contiguous: columns column .. column + N - 1 of every row are written (NaN for a pair that does not
+    count).  normalizer (N,) or None (errors in pixels).  confidence (N,K) or None; with one, bin_edges (n_bins + 1,) and conf_thresholds
+    (T,) ascending float32 device tensors and the three int64 counters of `kpt_error_buffers` are needed and updated.
+    Shapes are checked first (ValueError), then every tensor's device and type (PoseKernelError); nothing is launched before both."""
+    if pred.dim() != 3 or pred.shape[-1] != 2:
+        raise ValueError(f"pred: expected (N, K, 2), got {tuple(pred.shape)}")
+    N, K, column = int(pred.shape[0]), int(pred.shape[1]), int(column)
+    if gt.shape != pred.shape:
+        raise ValueError(f"gt: expected {tuple(pred.shape)} like pred, got {tuple(gt.shape)}")
+    if tuple(visible.shape) != (N, K):
+        raise ValueError(f"visible: expected {(N, K)}, got {tuple(visible.shape)}")
+    if normalizer is not None and tuple(normalizer.shape) != (N,):
+        raise ValueError(f"normalizer: expected {(N,)}, got {tuple(normalizer.shape)}")
+    if store.dim() != 2 or store.shape[0] != K or column < 0 or column + N > store.shape[1]:
+        raise ValueError(f"store: expected ({K}, at least {column + N}) for {N} columns from column {column}, got {tuple(store.shape)}")
+    if store.shape[1] > 0 and store.stride(1) != 1:
+        raise ValueError("store: the error store is written in place and its rows must be contiguous")
+    n_bins = n_thr = 0
+    if confidence is not None:
+        if tuple(confidence.shape) != (N, K):
+            raise ValueError(f"confidence: expected {(N, K)}, got {tuple(confidence.shape)}")
+        if bin_edges is None or conf_thresholds is None or calib_count is None or calib_hit is None or pr_hist is None:
+            raise ValueError("confidence: needs bin_edges, conf_thresholds and the three counters of kpt_error_buffers")
+        n_bins, n_thr = int(bin_edges.numel()) - 1, int(conf_thresholds.numel())
+        if bin_edges.dim() != 1 or not 1 <= n_bins <= ERR_MAX_BINS:
+            raise ValueError(f"bin_edges: expected the 2 to {ERR_MAX_BINS + 1} edges of 1 to {ERR_MAX_BINS} bins in one dimension, "
+                             f"got {tuple(bin_edges.shape)}")
+        if conf_thresholds.dim() != 1 or not 1 <= n_thr <= ERR_MAX_CONF_THRESHOLDS:
+            raise ValueError(f"conf_thresholds: expected 1 to {ERR_MAX_CONF_THRESHOLDS} values in one dimension, "
+                             f"got {tuple(conf_thresholds.shape)}")
+        if tuple(calib_count.shape) != (K, n_bins) or tuple(calib_hit.shape) != (K, n_bins) or tuple(pr_hist.shape) != (K, 2, n_thr + 1):
+            raise ValueError(f"counters: expected {(K, n_bins)}, {(K, n_bins)}, {(K, 2, n_thr + 1)}, got {tuple(calib_count.shape)}, "
+                             f"{tuple(calib_hit.shape)}, {tuple(pr_hist.shape)}")
+        for t, name in ((calib_count, "calib_count"), (calib_hit, "calib_hit"), (pr_hist, "pr_hist")):
+            if not t.is_contiguous():
+                raise ValueError(f"{name}: the counters are updated in place and must be contiguous")
+    pred, gt, vis = _chk(pred, name="pred"), _chk(gt, name="gt"), _chk(visible, name="visible")
+    norm = None if normalizer is None else _chk(normalizer, name="normalizer")
+    if not (isinstance(store, torch.Tensor) and store.is_cuda and store.dtype == F32):
+        raise _lib.PoseKernelError("store: expected a float32 CUDA(HIP) tensor; the hot path has no CPU implementation")
+    conf = edges = thr = None
+    if confidence is not None:
+        conf, edges, thr = _chk(confidence, name="confidence"), _chk(bin_edges, name="bin_edges"), _chk(conf_thresholds, name="conf_thresholds")
+        calib_count, calib_hit, pr_hist = _chk(calib_count, I64, "calib_count"), _chk(calib_hit, I64, "calib_hit"), _chk(pr_hist, I64, "pr_hist")
+    else:
+        calib_count = calib_hit = pr_hist = None
+    if N * K > 0:
+        first = store.data_ptr() + 4 * column                     # the first free column of row 0; row k starts ld floats further
+        call("pk_kpt_error", pred, gt, vis, conf, norm, float(pixel_threshold), edges, n_bins, thr, n_thr, first, int(store.stride(0)),
+             calib_count, calib_hit, pr_hist, N, K, stream_ptr())
+
+
+def kpt_error_quantiles(store, n_cols, q):
+    """Exact order statistics of the first n_cols columns of every row of the (K, capacity) float32 error store (pk_kpt_error_quantiles;
+    no synchronisation).  q (Q,) float64 device tensor, each in [0, 1].  -> order (K,Q,2) float32: the values v[lo], v[hi] around position
+    q (n - 1) of the row's n non-NaN values in ascending order; summary (K,4) float64: n, sum, min, max.  All zero for a row without a value
+    and for n_cols = 0 (nothing launched)."""
+    n_cols = int(n_cols)
+    if store.dim() != 2 or not 0 <= n_cols <= store.shape[1]:
+        raise ValueError(f"store: expected (K, at least {n_cols}), got {tuple(store.shape)}")
+    if n_cols > ERR_MAX_COLS:
+        raise ValueError(f"store: {n_cols} columns (at most {ERR_MAX_COLS})")
+    if store.shape[1] > 0 and store.stride(1) != 1:
+        raise ValueError("store: the rows of the error store must be contiguous")
+    if q.dim() != 1 or not 1 <= q.numel() <= ERR_MAX_QUANTILES:
+        raise ValueError(f"q: expected 1 to {ERR_MAX_QUANTILES} quantiles in one dimension, got {tuple(q.shape)}")
+    if not (isinstance(store, torch.Tensor) and store.is_cuda and store.dtype == F32):
+        raise _lib.PoseKernelError("store: expected a float32 CUDA(HIP) tensor; the hot path has no CPU implementation")
+    q = _chk(q, F64, "q")
+    K, Q = int(store.shape[0]), int(q.numel())
+    order = torch.zeros(K, Q, 2, dtype=F32, device=store.device)
+    summary = torch.zeros(K, 4, dtype=F64, device=store.device)
+    _call_if(K * n_cols, "pk_kpt_error_quantiles", store, int(store.stride(0)), n_cols, K, q, Q, order, summary, stream_ptr())
+    return order, summary
+
+
 # ------------------------------------------------------------------------------------------------ overlays
 U8 = torch.uint8
 

@@ -1,6 +1,7 @@
 """Utils module."""
-from .metrics import (AverageMeter, COCOEvaluator, MetricLogger, PCKAccumulator, calculate_movement_amplitude, calculate_pck,
-                      calculate_temporal_consistency, movement_heatmap, movement_report, movement_spectrum)
+from .metrics import (AverageMeter, COCOEvaluator, KeypointErrorAnalyzer, MetricLogger, PCKAccumulator, calculate_movement_amplitude,
+                      calculate_pck, calculate_temporal_consistency, keypoint_error_report, movement_heatmap, movement_report,
+                      movement_spectrum)
 from . import postprocess
 from .postprocess import oks_nms, soft_oks_nms
 from . import tensor_stats
@@ -13,4 +14,5 @@ __all__ = ['AverageMeter', 'COCOEvaluator', 'MetricLogger', 'postprocess', 'visu
            'draw_poses', 'draw_person_heatmaps', 'create_grid_image', 'save_visualization', 'save_person_visualization', 'COCO_SKELETON',
            'COCO_COLORS', 'PCKAccumulator', 'calculate_movement_amplitude', 'calculate_pck', 'calculate_temporal_consistency',
            'movement_heatmap', 'movement_report', 'movement_spectrum', 'oks_nms', 'soft_oks_nms', 'tensor_stats', 'tensor_statistics',
-           'gradient_statistics', 'gradient_flow', 'weight_statistics']
+           'gradient_statistics', 'gradient_flow', 'weight_statistics', 'KeypointErrorAnalyzer',
+           'keypoint_error_report']

@@ -450,3 +450,186 @@ def calculate_pck(pred, gt, visible, normalizer, thresholds=(0.2,)) -> Dict:
     acc = PCKAccumulator(int(pred.shape[1]), thresholds)
     acc.update(pred, gt, visible, normalizer)
     return acc.compute()
+
+
+# ---------------------------------------------------------------------------------------------- localisation error analysis
+# The numbers behind the reference's PerformanceAnalyzer (analysis/nn_quantitative_viz.py:105-252: error distribution per joint,
+# confidence against accuracy, precision / recall over a confidence threshold), which it gathers in three Python loops over every
+# prediction.  Here two kernels (pk_kpt_error, pk_kpt_error_quantiles: DESIGN.md "Localisation error analysis"); what is left on the
+# host is arithmetic on the few arrays that come back.
+def default_confidence_edges(conf_bins: int = 10) -> np.ndarray:
+    """np.linspace(0, 1, conf_bins + 1) as float32 with the last edge one float32 above 1: a confidence of exactly 1.0 counts in the last
+    bin (the reference's half-open bins lose it)."""
+    edges = np.linspace(0, 1, int(conf_bins) + 1).astype(np.float32)
+    edges[-1] = np.nextafter(np.float32(1), np.float32(np.inf))
+    return edges
+
+
+def _trapezoid(y, x) -> float:
+    """np.trapz(y, x), written out (numpy renamed it): sum of (x[i+1] - x[i]) (y[i+1] + y[i]) / 2."""
+    y, x = np.asarray(y, np.float64), np.asarray(x, np.float64)
+    return float((np.diff(x) * (y[1:] + y[:-1]) / 2.0).sum())
+
+
+def _calibration(edges: np.ndarray, count: np.ndarray, hit: np.ndarray) -> Dict:
+    """{edges, count, accuracy, ece} from the counts of one joint (or of all): an empty bin has accuracy 0; ece = sum_b count_b
+    |accuracy_b - centre_b| / sum_b count_b (0 without a counted pair), centre_b = (edges[b] + edges[b+1]) / 2 in float64."""
+    count, hit = np.asarray(count, np.int64), np.asarray(hit, np.int64)
+    acc = np.where(count > 0, hit / np.maximum(count, 1), 0.0)
+    e = np.asarray(edges, np.float64)
+    centre = (e[:-1] + e[1:]) / 2
+    total = int(count.sum())
+    return {"edges": np.asarray(edges), "count": count, "accuracy": acc,
+            "ece": float((count * np.abs(acc - centre)).sum() / total) if total > 0 else 0.0}
+
+
+def _pr_counts(hist: np.ndarray):
+    """pr_hist (..., 2, T + 1) -> tp, fp, fn (..., T) of the reference's loop at every threshold: a pair with m thresholds below its
+    confidence is detected at thresholds 0 .. m - 1, so tp_i = sum_{m > i} hist[0, m], fp_i likewise from hist[1], fn_i = the correct pairs
+    that are not detected."""
+    hist = np.asarray(hist, np.int64)
+    above = np.flip(np.cumsum(np.flip(hist, -1), -1), -1)         # above[..., m] = sum_{m' >= m}
+    tp, fp = above[..., 0, 1:], above[..., 1, 1:]
+    return tp, fp, above[..., 0, :1] - tp
+
+
+def _precision_recall(thresholds: np.ndarray, hist: np.ndarray) -> Dict:
+    """{thresholds, precision, recall, ap} of one joint (or of all): 0 where the denominator is 0, as in the reference;
+    ap = -trapz(precision, recall), positive because recall falls as the threshold rises (the reference reports the negative area)."""
+    tp, fp, fn = _pr_counts(hist)
+    precision = np.where(tp + fp > 0, tp / np.maximum(tp + fp, 1), 0.0)
+    recall = np.where(tp + fn > 0, tp / np.maximum(tp + fn, 1), 0.0)
+    return {"thresholds": np.asarray(thresholds), "precision": precision, "recall": recall, "ap": -_trapezoid(precision, recall)}
+
+
+def _quantile_values(order: np.ndarray, n: np.ndarray, q: np.ndarray) -> np.ndarray:
+    """numpy's linear rule on the two order statistics: pos = q (n - 1), g = pos - floor(pos), value = lo + (hi - lo) g computed as
+    np.percentile does (its _lerp: from the upper end when g >= 0.5).  order (K,Q,2), n (K,), q (Q,) -> (K,Q) float64; NaN where n = 0."""
+    lo, hi = order[..., 0].astype(np.float64), order[..., 1].astype(np.float64)
+    pos = q[None, :] * (np.maximum(n, 1)[:, None] - 1).astype(np.float64)
+    g = pos - np.floor(pos)
+    with np.errstate(invalid="ignore"):
+        d = hi - lo
+        val = np.where(g >= 0.5, hi - d * (1 - g), lo + d * g)
+        val = np.where(g == 0, lo, val)                           # an exact position is the order statistic itself (inf - inf never arises)
+    return np.where(n[:, None] > 0, val, np.nan)
+
+
+class KeypointErrorAnalyzer:
+    """Where and how the keypoints are wrong, over any number of batches: per joint the distribution of the localisation error (n, mean,
+    min, max and exact quantiles), and per joint and pooled the calibration of the confidence (accuracy and count per confidence bin,
+    expected calibration error) and precision / recall of "within `pixel_threshold`" over a confidence threshold with its AP.
+    Holds a (K, capacity) float32 device store of every error, which grows by doubling with one device copy, and three int64 device
+    counters; `update` only launches, `compute` is the one synchronising call."""
+
+    def __init__(self, num_keypoints: int, pixel_threshold: float = 10.0, quantiles=(0.05, 0.25, 0.5, 0.75, 0.95), conf_bins=10,
+                 conf_thresholds=None, capacity: int = 1024):
+        """conf_bins: a number of equal bins over [0, 1] (`default_confidence_edges`) or the ascending edges themselves;
+        conf_thresholds: ascending thresholds (default np.linspace(0, 1, 100), the reference's).  Edges and thresholds are rounded to
+        float32 once, the type of the confidences they are compared with.  capacity: the first size of the store in samples."""
+        from .. import hipops
+        self.num_keypoints, self.pixel_threshold = int(num_keypoints), float(pixel_threshold)
+        self.quantiles = np.asarray(list(quantiles), np.float64).reshape(-1)
+        if not 1 <= self.quantiles.size <= hipops.ERR_MAX_QUANTILES or not ((self.quantiles >= 0) & (self.quantiles <= 1)).all():
+            raise ValueError(f"quantiles: expected 1 to {hipops.ERR_MAX_QUANTILES} values in [0, 1], got {list(quantiles)}")
+        self.edges = default_confidence_edges(conf_bins) if np.ndim(conf_bins) == 0 else np.asarray(conf_bins, np.float32).reshape(-1)
+        if not 1 <= self.edges.size - 1 <= hipops.ERR_MAX_BINS or not (np.diff(self.edges) >= 0).all():
+            raise ValueError(f"conf_bins: expected 1 to {hipops.ERR_MAX_BINS} bins with ascending edges, got {self.edges.size - 1}")
+        thr = np.linspace(0, 1, 100) if conf_thresholds is None else np.asarray(conf_thresholds)
+        self.conf_thresholds = thr.astype(np.float32).reshape(-1)
+        if not 1 <= self.conf_thresholds.size <= hipops.ERR_MAX_CONF_THRESHOLDS or not (np.diff(self.conf_thresholds) >= 0).all():
+            raise ValueError(f"conf_thresholds: expected 1 to {hipops.ERR_MAX_CONF_THRESHOLDS} ascending values, "
+                             f"got {self.conf_thresholds.size}")
+        if int(capacity) < 1:
+            raise ValueError(f"capacity: expected at least 1, got {capacity}")
+        self._capacity0 = int(capacity)
+        self.reset()
+
+    def reset(self):
+        self._store, self._n, self._buf, self._dev = None, 0, None, None
+
+    def update(self, pred, gt, visible, confidence=None, normalizer=None):
+        """pred, gt (N,K,2) in the same space, visible (N,K) (> 0 counts), confidence (N,K) or None (the batch then enters the error
+        distribution only), normalizer (N,) lengths or None (errors in the unit of the coordinates): numpy arrays or device tensors."""
+        import torch
+        from .. import hipops
+        pred, gt, vis = _device_f32(pred, "pred")[0], _device_f32(gt, "gt")[0], _device_f32(visible, "visible")[0]
+        K, dev = self.num_keypoints, pred.device
+        if pred.dim() != 3 or pred.shape[1] != K:
+            raise ValueError(f"pred: expected (N, {K}, 2), got {tuple(pred.shape)}")
+        N = int(pred.shape[0])
+        conf = None if confidence is None else _device_f32(confidence, "confidence")[0].to(dev).reshape(N, K)
+        norm = None if normalizer is None else _device_f32(normalizer, "normalizer")[0].to(dev)
+        if self._dev is None:
+            self._dev = (torch.from_numpy(self.edges).to(dev), torch.from_numpy(self.conf_thresholds).to(dev))
+            self._buf = hipops.kpt_error_buffers(K, self.edges.size - 1, self.conf_thresholds.size, dev)
+        if self._store is None or self._n + N > self._store.shape[1]:
+            cap = self._capacity0 if self._store is None else int(self._store.shape[1])
+            while cap < self._n + N:
+                cap *= 2
+            grown = torch.empty(K, cap, dtype=torch.float32, device=dev)
+            if self._n:
+                grown[:, :self._n].copy_(self._store[:, :self._n])     # one device copy, no host round trip
+            self._store = grown
+        if conf is None:
+            hipops.kpt_error_accumulate(pred, gt, vis.to(dev), self._store, self._n, self.pixel_threshold, normalizer=norm)
+        else:
+            hipops.kpt_error_accumulate(pred, gt, vis.to(dev), self._store, self._n, self.pixel_threshold, conf, norm, *self._dev, *self._buf)
+        self._n += N
+
+    def compute(self) -> Dict:
+        """{'pixel_threshold', 'quantiles': the requested q,
+            'joints': [{'joint', 'n', 'mean', 'min', 'max', 'quantiles': (Q,) values (numpy's linear rule; NaN like mean / min / max for a
+                        joint without a counted pair), 'calibration': {edges, count, accuracy, ece}, 'pr': {thresholds, precision, recall,
+                        ap}}, ...],
+            'calibration', 'pr': the same two over all joints, 'ece', 'ap': the pooled ones again, 'n': all counted pairs}."""
+        K, Q, nb, T = self.num_keypoints, self.quantiles.size, self.edges.size - 1, self.conf_thresholds.size
+        if self._store is None or self._n == 0:
+            order, summary = np.zeros((K, Q, 2), np.float32), np.zeros((K, 4))
+            count = hit = np.zeros((K, nb), np.int64)
+            hist = np.zeros((K, 2, T + 1), np.int64)
+        else:
+            import torch
+            from .. import hipops
+            order, summary = hipops.kpt_error_quantiles(self._store, self._n, torch.from_numpy(self.quantiles).to(self._store.device))
+            counters = torch.cat([b.reshape(-1) for b in self._buf])
+            order, summary, counters = order.cpu().numpy(), summary.cpu().numpy(), counters.cpu().numpy()
+            count, hit = counters[:K * nb].reshape(K, nb), counters[K * nb:2 * K * nb].reshape(K, nb)
+            hist = counters[2 * K * nb:].reshape(K, 2, T + 1)
+        n = summary[:, 0].astype(np.int64)
+        qv = _quantile_values(order, n, self.quantiles)
+        joints = []
+        for k in range(K):
+            some = n[k] > 0
+            joints.append({"joint": k, "n": int(n[k]), "mean": float(summary[k, 1] / n[k]) if some else float("nan"),
+                           "min": float(summary[k, 2]) if some else float("nan"), "max": float(summary[k, 3]) if some else float("nan"),
+                           "quantiles": qv[k], "calibration": _calibration(self.edges, count[k], hit[k]),
+                           "pr": _precision_recall(self.conf_thresholds, hist[k])})
+        calibration = _calibration(self.edges, count.sum(0), hit.sum(0))
+        pr = _precision_recall(self.conf_thresholds, hist.sum(0))
+        return {"pixel_threshold": self.pixel_threshold, "quantiles": self.quantiles, "n": int(n.sum()), "joints": joints,
+                "calibration": calibration, "pr": pr, "ece": calibration["ece"], "ap": pr["ap"]}
+
+
+def keypoint_error_report(pred, gt, visible, confidence=None, normalizer=None, **kwargs) -> Dict:
+    """Error analysis of one set of predictions: `KeypointErrorAnalyzer(K, **kwargs)` with one update."""
+    acc = KeypointErrorAnalyzer(int(pred.shape[1]), **kwargs)
+    acc.update(pred, gt, visible, confidence, normalizer)
+    return acc.compute()
+
+
+def error_report_json(report: Dict) -> Dict:
+    """`KeypointErrorAnalyzer.compute()` with every array as a list and every NaN as None: what `validate.py --error_report` writes."""
+    def plain(v):
+        if isinstance(v, dict):
+            return {k: plain(x) for k, x in v.items()}
+        if isinstance(v, (list, tuple)):
+            return [plain(x) for x in v]
+        if isinstance(v, np.ndarray):
+            return plain(v.tolist())
+        if isinstance(v, (float, np.floating)):
+            return float(v) if np.isfinite(v) else None
+        if isinstance(v, np.integer):
+            return int(v)
+        return v
+    return plain(report)

@@ -6,7 +6,9 @@ plus --bbox_file / --det_score_thr / --oks_nms THR / --soft_nms / --in_vis_thr f
 file instead of the ground-truth boxes, every pose rescored as box score x mean confident keypoint score, duplicate poses removed per image
 by OKS-NMS on the device, then AP; plus --decode {shift,unbiased} / --modulate_kernel K for the heatmap decode of the heatmap-head models:
 the quarter-pixel shift (the default) or the unbiased, distribution-aware step on the log of the smoothed map); plus --ema to score the
-averaged weights of a checkpoint written by `train.py --ema`).
+averaged weights of a checkpoint written by `train.py --ema`; plus --error_report PATH / --error_px T for the localisation error
+analysis: per joint the quantiles of the error in image pixels, the calibration of the confidence and precision / recall of "within T
+pixels" over a confidence threshold, gathered on the device and written as JSON).
 
 Flip-test inference + decode run entirely on the GPU (`PoseEstimator.inference`: two forwards, one flip-merge kernel, one
 decode kernel); the heat-px -> image transform of validate.py:100-117 is one kernel (`heatmap_to_image_coords`) instead of a
@@ -34,7 +36,7 @@ from infantposeestimation_gaussianbias_amd.utils.postprocess import heatmap_to_i
 
 @torch.no_grad()
 def validate(model, loader, device, cfg, logger, flip_test=True, scales=None, pck_thresholds=None, evaluator=None, decode=None,
-             modulate_kernel=None):
+             modulate_kernel=None, error_analysis=None, error_report=None):
     """train.py:231-325 == validate.py:39-140 of the reference: loss + decode + image-space transform + COCOEvaluator.update per batch,
     then AP.  Decode, flip merge, the heat-px -> image transform and the evaluator's record arrays are kernels (no B x K Python loops, one
     device->host copy per batch).  AP / AR come from COCOKeypointEval when the loader's dataset has an annotation file; otherwise AP is the
@@ -48,7 +50,11 @@ def validate(model, loader, device, cfg, logger, flip_test=True, scales=None, pc
     and removes duplicates per image by OKS-NMS on the device before AP (`COCOEvaluator.kept`).  `evaluator`: the COCOEvaluator to fill
     (default: one built from the loader's annotation file and the config's NMS settings).
     `decode` / `modulate_kernel`: the heatmap decode ('shift', 'unbiased') and its smoothing size; None takes the config's `decode` /
-    `modulate_kernel`, and a config that names none keeps the quarter-pixel shift."""
+    `modulate_kernel`, and a config that names none keeps the quarter-pixel shift.
+    `error_analysis`: None (nothing added: no metric key, no launch), or a `KeypointErrorAnalyzer` to fill in image space with the
+    predictions, ground truth and visibility that PCK gets and the per-joint scores that the evaluator gets, in pixels (no normaliser).
+    After the last batch its report goes to the log (median and 95th percentile per joint when it holds those quantiles, pooled ECE and AP)
+    and, with `error_report` (a path), to that file as JSON.  Like PCK it raises on a loader of detector boxes.  The metrics are unchanged."""
     from infantposeestimation_gaussianbias_amd.utils import COCOEvaluator
     from infantposeestimation_gaussianbias_amd.utils import metrics as metrics_mod
     pck = metrics_mod.PCKAccumulator(cfg.data.num_keypoints, pck_thresholds) if pck_thresholds is not None else None
@@ -79,6 +85,8 @@ def validate(model, loader, device, cfg, logger, flip_test=True, scales=None, pc
         if box_scores is not None:          # detector boxes: the batch's keypoints and targets are placeholders, not ground truth
             if pck is not None:
                 raise RuntimeError("validate: PCK needs ground-truth keypoints; a loader of detector boxes (bbox_file) carries none")
+            if error_analysis is not None:
+                raise RuntimeError("validate: the error analysis needs ground-truth keypoints; a loader of detector boxes (bbox_file) carries none")
             no_gt, gt_kp = True, None
         else:
             gt_kp = batch["keypoints"].to(device) if batch.get("keypoints") is not None else None
@@ -92,14 +100,19 @@ def validate(model, loader, device, cfg, logger, flip_test=True, scales=None, pc
             evaluator.update(img_kp, sc, meta["image_id"], meta["ann_id"], center, scale, meta["area"], meta["bbox"])
         if pck is not None and gt_kp is None:
             raise RuntimeError("validate: PCK needs a loader that yields batch['keypoints'] and batch['keypoints_visible']; this one does not")
+        if error_analysis is not None and gt_kp is None:
+            raise RuntimeError("validate: the error analysis needs a loader that yields batch['keypoints'] and batch['keypoints_visible']; "
+                               "this one does not")
         # ground truth in image space: the same inverse crop transform, applied to the input-pixel keypoints (heatmap size == input size)
         gimg_dev = None
-        if gt_kp is not None and (pck is not None or ann is None):
+        if gt_kp is not None and (pck is not None or error_analysis is not None or ann is None):
             gimg_dev = heatmap_to_image_coords(gt_kp.float(), center, scale, cfg.data.input_size, cfg.data.input_size)
         if pck is not None:
             bb = torch.as_tensor(meta["bbox"]).float().reshape(-1, 4).cpu()
             norm = torch.maximum(bb[:, 2] - bb[:, 0], bb[:, 3] - bb[:, 1])          # host arithmetic on the loader's metadata, then one upload
             pck.update(img_kp, gimg_dev, batch["keypoints_visible"].to(device).float(), norm.to(device))
+        if error_analysis is not None:
+            error_analysis.update(img_kp, gimg_dev, batch["keypoints_visible"].to(device).float(), sc.reshape(sc.shape[0], -1))
         if ann is None and gt_kp is not None:
             gimg = gimg_dev.cpu().numpy()
             vis = batch["keypoints_visible"].cpu().numpy()
@@ -116,7 +129,26 @@ def validate(model, loader, device, cfg, logger, flip_test=True, scales=None, pc
         metrics["PCK_mean_error"] = res["mean_error"]
     logger.info(f"Validation Loss: {loss_meter.avg:.4f}  " + "  ".join(f"{k}: {v:.4f}" for k, v in metrics.items() if k != "loss")
                 + ("" if ann else "  (reference OKS matching against the loader's ground truth: the loader has no annotation file)"))
+    if error_analysis is not None:
+        log_error_report(error_analysis, logger, error_report)
     return metrics, evaluator.predictions
+
+
+def log_error_report(analyzer, logger, path=None):
+    """The report of a filled `KeypointErrorAnalyzer`: one log line per joint, the pooled ECE and AP, and the whole of it as JSON to `path`."""
+    import json
+    from infantposeestimation_gaussianbias_amd.utils.metrics import error_report_json
+    report = analyzer.compute()
+    q = [float(v) for v in report["quantiles"]]
+    pick = lambda joint, v: f"{joint['quantiles'][q.index(v)]:.2f}" if v in q and joint["n"] else "n/a"
+    for joint in report["joints"]:
+        logger.info(f"  joint {joint['joint']}: n {joint['n']}  median {pick(joint, 0.5)} px  p95 {pick(joint, 0.95)} px")
+    logger.info(f"Error analysis at {report['pixel_threshold']:g} px over {report['n']} keypoints: ECE {report['ece']:.4f}  AP {report['ap']:.4f}")
+    if path:
+        with open(path, "w") as f:
+            json.dump(error_report_json(report), f)
+        logger.info(f"Error report written to {path}")
+    return report
 
 
 def main(args):
@@ -146,7 +178,12 @@ def main(args):
         pck_thresholds = tuple(args.pck) or (cfg.pck_threshold,)
     elif "PCK" in cfg.eval_metrics and cfg.bbox_file is None:      # detector boxes carry no ground truth: only an explicit --pck insists
         pck_thresholds = (cfg.pck_threshold,)
-    metrics, _ = validate(model, loader, device, cfg, logger, flip_test=not args.no_flip, scales=cfg.test_scales, pck_thresholds=pck_thresholds)
+    error_analysis = None
+    if getattr(args, "error_report", None):
+        from infantposeestimation_gaussianbias_amd.utils import KeypointErrorAnalyzer
+        error_analysis = KeypointErrorAnalyzer(cfg.data.num_keypoints, pixel_threshold=getattr(args, "error_px", 10.0))
+    metrics, _ = validate(model, loader, device, cfg, logger, flip_test=not args.no_flip, scales=cfg.test_scales, pck_thresholds=pck_thresholds,
+                          error_analysis=error_analysis, error_report=getattr(args, "error_report", None))
     logger.info(f"Loss: {metrics['loss']:.4f}")
     return metrics
 
@@ -180,6 +217,12 @@ def build_parser():
     p.add_argument("--pck", type=float, nargs="*", default=None,
                    help="also report PCK at these thresholds (fractions of the longer box side; no value: the config's pck_threshold, 0.2); "
                         "default: only when the config's yaml names 'PCK' in EVAL.METRICS")
+    p.add_argument("--error_report", type=str, default=None, metavar="PATH",
+                   help="also analyse the localisation error on the device and write the report to PATH as JSON: per joint n, mean, min, max "
+                        "and quantiles of the error in image pixels, calibration of the keypoint scores (accuracy per confidence bin, ECE) and "
+                        "precision / recall of 'within --error_px' over a confidence threshold with its AP (default: nothing)")
+    p.add_argument("--error_px", type=float, default=10.0, metavar="T",
+                   help="--error_report: a keypoint is correct when it lies less than T image pixels from its ground truth (default 10)")
     p.add_argument("--bbox_file", type=str, default=None,
                    help="validate on detector boxes: a COCO-style person-detection file [{image_id, category_id, bbox, score}], relative to "
                         "data_root (default: the config's bbox_file; none: crops from the ground-truth boxes)")
