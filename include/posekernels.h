@@ -269,6 +269,38 @@ int pk_kpt_error(const float* pred, const float* gt, const float* vis, const flo
 int pk_kpt_error_quantiles(const float* err, int64_t ld, int64_t n_cols, int K, const double* q /* (Q) device, each in [0,1] */, int Q,
                            float* order /* (K,Q,2) */, double* summary /* (K,4) */, void* stream);
 
+/* ---- occlusion sensitivity (this project's own specification, DESIGN.md "Occlusion sensitivity": the map of the reference's
+ * SensitivityAnalyzer.occlusion_sensitivity, analysis/advanced_analysis.py:387-427, for every joint from one batched sweep).  No atomics;
+ * the one floating-point sum is taken in a fixed order, so the same input gives the same bits.
+ * Grid: patch rows start at range(0, H - patch, stride), columns likewise: per axis n(extent) = ceil((extent - patch) / stride) positions
+ *   when extent > patch, else none; the position extent - patch itself is NOT taken (the reference's rule, kept).  ny = n(H), nx = n(W);
+ *   copy p = a nx + b blanks rows a stride .. a stride + patch - 1 and columns b stride .. b stride + patch - 1.  An empty grid is
+ *   PK_ERR_INVALID in every entry below.
+ * pk_occlusion_positions: host only, returns n(extent) >= 0; PK_ERR_INVALID (with the error text set) for extent, patch or stride < 1.
+ * pk_occlude_batch: x (H,W,8) bf16, the stem's packed image; out (n,H,W,8) bf16 receives copies first .. first + n - 1: the image with
+ *   the patch's pixels replaced by the fill.  fill_host: HOST pointer to 3 floats (read before the call returns, rounded to bf16 to nearest
+ *   even as pk_nchw_f32_to_nhwc_bf16 rounds, carried in the kernel's arguments) or NULL = 0, the mean in normalised space; channels 3..7
+ *   of a filled pixel are 0.  One 16-byte load and one 16-byte store per pixel.  Refused before the launch: a null or misaligned pointer,
+ *   first < 0, n < 1, first + n > ny nx, n H W >= 2^32 - 1, and a source that overlaps the destination.
+ * pk_heatmap_summary: heatmaps (M,h,w) fp32; out (M,4) float64 = sum, max, argmax x, argmax y.  One 256-thread workgroup per map
+ *   (workgroups stride over the maps when M exceeds the grid).  Sum: thread t adds elements t, t + 256, ... in ascending order to 0.0 in
+ *   float64; then the xor butterfly 32, 16, ..., 1 inside each wave, then wave 0 + wave 1 + wave 2 + wave 3.  Maximum: a candidate is
+ *   replaced iff v > best in float32, starting from -inf without an index; among equal values (-0 = +0) the smallest flat index wins; a
+ *   NaN never wins and makes the sum NaN; a map with no value above -inf reports max = -inf at index 0.  max is the element at the winning
+ *   index, widened; x = idx % w, y = idx / w, exact.
+ * pk_occlusion_paint: base (K,4) and table (P = ny nx, K, 4) rows of pk_heatmap_summary; maps (K,H,W) float64, every element written once.
+ *   The reference writes map[i : i + patch, j : j + patch] = base - score in loop order, the last writer wins; in closed form pixel (y, x)
+ *   has a = min(y / stride, ny - 1), b = min(x / stride, nx - 1), is covered iff y < a stride + patch and x < b stride + patch, and then takes
+ *   the value of copy a nx + b; an uncovered pixel is 0.  measure 0: base.sum - t.sum; 1: base.max - t.max; 2: sqrt(dx dx + dy dy) of the
+ *   two argmax positions, in float64 without FMA.                                                                                   */
+int pk_occlusion_positions(int extent, int patch, int stride);
+int pk_occlude_batch(const void* x /* (H,W,8) bf16 */, void* out /* (n,H,W,8) bf16 */, int H, int W, int patch, int stride, int first, int n,
+                     const float* fill_host /* 3 floats or NULL */, void* stream);
+int pk_heatmap_summary(const float* heatmaps /* (M,h,w) */, double* out /* (M,4): sum, max, argmax x, argmax y */, int64_t M, int h, int w,
+                       void* stream);
+int pk_occlusion_paint(const double* base /* (K,4) */, const double* table /* (P,K,4) */, double* maps /* (K,H,W) */, int measure, int K,
+                       int H, int W, int patch, int stride, void* stream);
+
 /* ---- L1/L2: FusionPoseLoss.forward (models/fusion_head.py:745-806 with :405-559, :637-743) ---------------
  * stats: workspace of B*K*PK_LOSS_STAT floats + B*16*4 floats + 16 floats (see PK_LOSS_WS_FLOATS);
  * losses: 7 floats (heatmap, offset, peak, variance, overlap, shape, total — already multiplied by lambdas).

@@ -794,6 +794,99 @@ def kpt_error_quantiles(store, n_cols, q):
     return order, summary
 
 
+# ------------------------------------------------------------------------------------------------ occlusion sensitivity
+BF16 = torch.bfloat16
+OCCLUSION_MEASURES = {"sum": 0, "max": 1, "shift": 2}
+
+
+def occlusion_positions(extent, patch, stride):
+    """Patch positions along one axis (pk_occlusion_positions; host only): len(range(0, extent - patch, stride)), the reference's grid --
+    the position extent - patch itself is not taken.  0 when extent <= patch."""
+    n = _lib.lib.pk_occlusion_positions(int(extent), int(patch), int(stride))
+    if n < 0:
+        raise _lib.PoseKernelError(f"pk_occlusion_positions failed (code {n}): {_lib.lib.pk_last_error_string().decode()}")
+    return n
+
+
+def occlusion_grid(H, W, patch, stride):
+    """(ny, nx) of an (H, W) image; an empty grid is an error that names the rule."""
+    ny, nx = occlusion_positions(H, patch, stride), occlusion_positions(W, patch, stride)
+    if ny == 0 or nx == 0:
+        raise _lib.PoseKernelError(f"occlusion grid: no patch position: rows and columns start at range(0, extent - patch, stride), which is "
+                                   f"empty for H={int(H)} W={int(W)} patch={int(patch)}")
+    return ny, nx
+
+
+def occlude_batch(x, patch, stride, first=0, n=None, fill=None, out=None):
+    """Occluded copies first .. first + n - 1 of one packed image (pk_occlude_batch; no synchronisation).  x (H,W,8) or (1,H,W,8) bf16, the
+    stem's layout; -> (n,H,W,8) bf16, or `out` when given (contiguous, at least n copies: its first n are written and returned).  Copy
+    p = a nx + b has rows a stride .. a stride + patch - 1 and columns b stride .. b stride + patch - 1 replaced by `fill`: None = 0 in
+    normalised space, or three floats per channel, rounded to bf16 as the input conversion rounds.  n = None: all from `first` on."""
+    x = _chk(x, BF16, "x")
+    if x.dim() == 4 and x.shape[0] == 1:
+        x = x[0]
+    if x.dim() != 3 or x.shape[-1] != 8:
+        raise _lib.PoseKernelError(f"occlude_batch: x {tuple(x.shape)} is not the packed image (H, W, 8) or (1, H, W, 8)")
+    H, W = int(x.shape[0]), int(x.shape[1])
+    ny, nx = occlusion_grid(H, W, patch, stride)
+    first = int(first)
+    n = ny * nx - first if n is None else int(n)
+    if first < 0 or n < 1 or first + n > ny * nx:
+        raise _lib.PoseKernelError(f"occlude_batch: copies {first} .. {first + n - 1} of {ny * nx} ({ny} x {nx} positions)")
+    fill_ptr = None
+    if fill is not None:
+        fill = np.ascontiguousarray(np.asarray(fill, np.float32).reshape(-1))
+        if fill.size != 3:
+            raise _lib.PoseKernelError(f"occlude_batch: fill takes three floats, one per channel, got {fill.size}")
+        fill_ptr = fill.ctypes.data                               # read before the call returns; carried in the launch
+    if out is None:
+        out = torch.empty(n, H, W, 8, dtype=BF16, device=x.device)
+    else:
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == BF16 and out.is_contiguous() and out.dim() == 4
+                and tuple(out.shape[1:]) == (H, W, 8) and out.shape[0] >= n):
+            raise _lib.PoseKernelError(f"occlude_batch: out must be a contiguous bf16 device tensor (at least {n}, {H}, {W}, 8)")
+        out = out[:n]
+    call("pk_occlude_batch", x, out, H, W, int(patch), int(stride), first, n, fill_ptr, stream_ptr())
+    return out
+
+
+def heatmap_summary(heatmaps, out=None):
+    """(..., h, w) -> (..., 4) float64: sum, max, argmax x, argmax y of every map in one pass (pk_heatmap_summary; no synchronisation).  fp32;
+    a bf16 input is widened first.  The sum is taken in a fixed order and the first of equal maxima wins.  `out`: a contiguous float64
+    device tensor of that shape to write into (a slice of a larger table)."""
+    if isinstance(heatmaps, torch.Tensor) and heatmaps.dtype == BF16:
+        heatmaps = heatmaps.float()
+    hm = _chk(heatmaps, name="heatmaps")
+    if hm.dim() < 2:
+        raise _lib.PoseKernelError(f"heatmap_summary: heatmaps {tuple(hm.shape)} are not (..., h, w)")
+    lead, h, w = tuple(hm.shape[:-2]), int(hm.shape[-2]), int(hm.shape[-1])
+    M = int(np.prod(lead, dtype=np.int64)) if lead else 1
+    if out is None:
+        out = torch.empty(*lead, 4, dtype=F64, device=hm.device)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == F64 and out.is_contiguous() and tuple(out.shape) == lead + (4,)):
+        raise _lib.PoseKernelError(f"heatmap_summary: out must be a contiguous float64 device tensor {lead + (4,)}")
+    _call_if(M * h * w, "pk_heatmap_summary", hm, out, M, h, w, stream_ptr())
+    return out
+
+
+def occlusion_paint(base, table, H, W, patch, stride, measure="sum"):
+    """The reference's sensitivity map of every joint from the score table (pk_occlusion_paint; one launch, no synchronisation).  base (K,4)
+    and table (P,K,4) or (ny,nx,K,4) float64 rows of `heatmap_summary` -> (K,H,W) float64: pixel (y, x) takes the value of the last patch
+    the reference's loops write there, 0 where none does.  measure 'sum': base.sum - sum; 'max': base.max - max; 'shift': the distance of
+    the argmax from the un-occluded one, in heat pixels."""
+    if measure not in OCCLUSION_MEASURES:
+        raise _lib.PoseKernelError(f"occlusion_paint: measure {measure!r} (one of {', '.join(OCCLUSION_MEASURES)})")
+    ny, nx = occlusion_grid(H, W, patch, stride)
+    base, table = _chk(base, F64, "base"), _chk(table, F64, "table")
+    K = int(base.shape[0]) if base.dim() == 2 else -1
+    if K < 1 or tuple(base.shape) != (K, 4) or tuple(table.shape) not in ((ny * nx, K, 4), (ny, nx, K, 4)):
+        raise _lib.PoseKernelError(f"occlusion_paint: base (K,4) and table ({ny * nx},K,4) for {ny} x {nx} positions, got {tuple(base.shape)}, "
+                                   f"{tuple(table.shape)}")
+    maps = torch.empty(K, int(H), int(W), dtype=F64, device=base.device)
+    call("pk_occlusion_paint", base, table, maps, OCCLUSION_MEASURES[measure], K, int(H), int(W), int(patch), int(stride), stream_ptr())
+    return maps
+
+
 # ------------------------------------------------------------------------------------------------ overlays
 U8 = torch.uint8
 

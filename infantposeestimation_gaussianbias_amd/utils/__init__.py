@@ -4,6 +4,8 @@ from .metrics import (AverageMeter, COCOEvaluator, KeypointErrorAnalyzer, Metric
                       movement_spectrum)
 from . import postprocess
 from .postprocess import oks_nms, soft_oks_nms
+from . import sensitivity
+from .sensitivity import SensitivityAnalyzer, occlusion_sensitivity_maps
 from . import tensor_stats
 from .tensor_stats import gradient_flow, gradient_statistics, tensor_statistics, weight_statistics
 from . import visualization
@@ -15,4 +17,4 @@ __all__ = ['AverageMeter', 'COCOEvaluator', 'MetricLogger', 'postprocess', 'visu
            'COCO_COLORS', 'PCKAccumulator', 'calculate_movement_amplitude', 'calculate_pck', 'calculate_temporal_consistency',
            'movement_heatmap', 'movement_report', 'movement_spectrum', 'oks_nms', 'soft_oks_nms', 'tensor_stats', 'tensor_statistics',
            'gradient_statistics', 'gradient_flow', 'weight_statistics', 'KeypointErrorAnalyzer',
-           'keypoint_error_report']
+           'keypoint_error_report', 'sensitivity', 'SensitivityAnalyzer', 'occlusion_sensitivity_maps']

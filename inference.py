@@ -16,6 +16,8 @@ adds the movement spectrum of that band (pk_motion_spectrum) to the report.
 Visualisation is on the device too: `visualize` / `visualize_batch` draw through utils/visualization.py (pk_draw_shapes,
 pk_heatmap_overlay, pk_heatmap_overlay_patches: this project's own integer rasterisation rule, not OpenCV's pixels) and files are written
 with Pillow.
+`occlusion_sensitivity` / `--occlusion_map JOINT` answer which part of a person's crop the network needs: one batched sweep of occluded
+copies on the device gives the map of every joint (utils/sensitivity.py), and the chosen joint's map is drawn where the crop lies.
 """
 import argparse
 import os
@@ -35,7 +37,9 @@ from infantposeestimation_gaussianbias_amd.datasets.transforms import DeviceCrop
 from infantposeestimation_gaussianbias_amd.models import build_model  # noqa: E402
 from infantposeestimation_gaussianbias_amd.utils.metrics import movement_heatmap, movement_report  # noqa: E402
 from infantposeestimation_gaussianbias_amd.utils.postprocess import heatmap_to_image_coords, temporal_smoothing  # noqa: E402
-from infantposeestimation_gaussianbias_amd.utils.visualization import COCO_SKELETON, draw_heatmaps, draw_poses, draw_skeleton, write_image  # noqa: E402
+from infantposeestimation_gaussianbias_amd.utils.sensitivity import occlusion_sensitivity_maps  # noqa: E402
+from infantposeestimation_gaussianbias_amd.utils.visualization import (COCO_SKELETON, crop_heatmap_matrices, draw_heatmaps, draw_person_heatmaps,  # noqa: E402
+                                                                       draw_poses, draw_skeleton, write_image)
 
 
 class PoseInference:
@@ -189,6 +193,20 @@ class PoseInference:
     def predict(self, img: np.ndarray, bbox: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
         return self.predict_batch([img], [bbox])[0]
 
+    def occlusion_sensitivity(self, img: np.ndarray, bbox: Optional[np.ndarray] = None, joints=None, **kw):
+        """Which part of the crop the network needs: the occlusion sensitivity sweep (utils.sensitivity.occlusion_sensitivity_maps; `kw`:
+        patch_size, stride, measure, batch_size, fill) on the crop `predict` takes for this image and box, un-flipped.  -> the sweep's
+        dict (maps (K,H,W) float64 over the crop's pixels, base, table, grid) plus `center` and `scale` of the crop, with which
+        `crop_heatmap_matrices(center, scale, input_size)` places a map in the image.  `joints`: one index or a list of them keeps only
+        those rows of maps, base and table (in that order); None keeps all."""
+        x, center, scale = self.preprocess(img, bbox)
+        out = occlusion_sensitivity_maps(self.model, x, **kw)
+        if joints is not None:
+            sel = torch.as_tensor(np.atleast_1d(np.asarray(joints, np.int64)), device=self.device)
+            out['maps'], out['base'], out['table'] = out['maps'][sel], out['base'][sel], out['table'][:, :, sel]
+        out['center'], out['scale'] = center, scale
+        return out
+
     # ---- inference.py:238-262
     def visualize(self, img, keypoints, scores, score_threshold: float = 0.3, output_path: Optional[str] = None):
         """The skeleton of one prediction on a copy of `img` (BGR); saved too when `output_path` is given."""
@@ -282,10 +300,39 @@ def main_sequence(args, pose):
     return report
 
 
+def main_occlusion(args, pose, img, bbox):
+    """--occlusion_map JOINT: the sweep on the person's crop, that joint's map (clamped at 0) drawn where the crop lies."""
+    k = int(args.occlusion_map)
+    if not 0 <= k < pose.model.num_keypoints:
+        raise SystemExit(f"--occlusion_map: joint {k} outside 0 .. {pose.model.num_keypoints - 1}")
+    res = pose.occlusion_sensitivity(img, bbox, patch_size=args.occlusion_patch, stride=args.occlusion_stride, measure=args.occlusion_measure)
+    ny, nx = res['grid']
+    if args.occlusion_measure == 'shift':
+        t, b = res['table'][:, :, k], res['base'][k]
+        drop = torch.sqrt((t[..., 2] - b[2]) ** 2 + (t[..., 3] - b[3]) ** 2)
+    else:
+        col = 0 if args.occlusion_measure == 'sum' else 1
+        drop = res['base'][k, col] - res['table'][:, :, k, col]
+    worst = int(torch.argmax(drop.reshape(-1)))                   # the one read-back, after the sweep
+    a, b = divmod(worst, nx)
+    print(f'Occlusion sweep: {ny} x {nx} = {ny * nx} patches of {args.occlusion_patch} px at stride {args.occlusion_stride}, '
+          f'measure {args.occlusion_measure}')
+    print(f'  largest drop for joint {k}: {float(drop.reshape(-1)[worst]):.6g} with crop rows {a * args.occlusion_stride} .. '
+          f'{a * args.occlusion_stride + args.occlusion_patch - 1}, columns {b * args.occlusion_stride} .. '
+          f'{b * args.occlusion_stride + args.occlusion_patch - 1} covered')
+    heat = res['maps'][k].clamp_min(0).float()[None, None]        # negative = the occlusion helped: not drawn
+    mats = crop_heatmap_matrices(res['center'], res['scale'], pose.input_size)
+    write_image(draw_person_heatmaps(img, heat, matrices=mats), args.output)
+    print(f'Result saved to: {args.output}')
+    return res
+
+
 def main(args):
     from PIL import Image
     if getattr(args, "freq_band", None) is not None and args.fps is None:
         build_parser().error("--freq_band is in Hz and needs --fps")
+    if getattr(args, "occlusion_map", None) is not None and not args.output:
+        build_parser().error("--occlusion_map draws a picture and needs --output")
     pose = PoseInference(checkpoint=args.checkpoint, device=args.device, flip_test=not args.no_flip, config=args.config, scales=args.scales,
                          decode=args.decode, modulate_kernel=args.modulate_kernel, ema=getattr(args, "ema", False))
     if getattr(args, "sequence", False):
@@ -293,6 +340,8 @@ def main(args):
     rgb = np.asarray(Image.open(args.input).convert("RGB"))
     img = rgb[:, :, ::-1].copy()                          # the reference hands BGR (cv2.imread) to PoseInference
     bboxes = [np.array(args.bbox)] if args.bbox else detect_persons(img)
+    if getattr(args, "occlusion_map", None) is not None:
+        return main_occlusion(args, pose, img, bboxes[0])
     whole = len(bboxes) == 1 and np.array_equal(np.asarray(bboxes[0], np.float64), [0, 0, img.shape[1], img.shape[0]])
     want_hm = bool(args.output and args.draw_heatmaps)
     t0 = time.time()
@@ -350,6 +399,17 @@ def build_parser():
                    help='--decode unbiased: taps of the Gaussian smoothing, odd, 3 to 31 (default: the config\'s modulate_kernel, 11)')
     p.add_argument('--ema', action='store_true',
                    help='load the averaged weights (the checkpoint\'s ema_state_dict, saved by train.py --ema) instead of model_state_dict')
+    p.add_argument('--occlusion_map', type=int, default=None, metavar='JOINT',
+                   help='occlusion sensitivity of this joint instead of the pose overlay (needs --output): the crop is occluded patch by '
+                        'patch in one batched sweep on the device, and the map of the score drop is drawn where the crop lies in the image. '
+                        'Values are clamped at 0 before drawing: a negative value means the occlusion helped, and the overlay normalises '
+                        'to its own range, so the picture shows where the joint needs the image, not by how much. Prints the patch with '
+                        'the largest drop')
+    p.add_argument('--occlusion_patch', type=int, default=16, help='--occlusion_map: side of the occluding patch in crop pixels')
+    p.add_argument('--occlusion_stride', type=int, default=8, help='--occlusion_map: step between patch positions in crop pixels')
+    p.add_argument('--occlusion_measure', type=str, choices=('sum', 'max', 'shift'), default='sum',
+                   help='--occlusion_map: sum = drop of the heat map\'s sum (the reference\'s measure), max = drop of its peak (the keypoint '
+                        'score), shift = distance in heat pixels the peak moved')
     return p
 
 
