@@ -428,6 +428,49 @@ int pk_tensor_stats(const float* a, const float* b, const uint8_t* flags, const 
                     void* ws, int64_t ws_bytes, void* records, void* stream);
 int pk_tensor_stats_latch(const void* records, int n_tensors, void* latched, int32_t* latch_state, void* stream);
 
+/* ---- activation statistics (this project's own specification, DESIGN.md "Activation statistics": the numbers behind the reference's
+ * ActivationAnalyzer, analysis/advanced_analysis.py:34-125, without its copy of every feature map to the host).  x: bf16, M rows x C
+ * channels, row-major (an NHWC map flattened), 16-byte aligned; C % 8 == 0, 8 <= C <= PK_ACT_MAX_CHANNELS, 1 <= M C <= PK_ACT_MAX_ELEMS
+ * = 2^38; 1 <= c_used <= C: channels >= c_used are padding and take part in nothing.  No global atomics, no float atomics, no last-arriver:
+ * the same input gives the same bits on any stream.
+ * Element rule: exponent bits all ones (inf / NaN) -> counted in n_nonfinite and left out of everything else (pk_tensor_stats' rule).
+ * Record (PK_ACT_RECORD_BYTES each, one per channel < c_used):
+ *   +0 f64 sum x | +8 f64 sum x^2 (squares formed in fp64) | +16 f32 min (+inf if none) | +20 f32 max (-inf if none) | +24 i64 n (all
+ *   elements of the channel, M per call) | +32 i64 +-0 | +40 i64 x < 0 | +48 i64 inf / NaN | +56 i64 0.  min / max read -0 as +0.
+ * Table: PK_ACT_HIST_BINS int64 counts over the finite elements of the channels < c_used.  key = the bf16 bits made sortable (-0 first
+ *   mapped to +0; sign set -> ~bits, else bits | 0x8000), bin = key >> 4: sign, exponent and three mantissa bits, so the edges are exact
+ *   bf16 values and the same for every tensor; +0 lies in bin 2048.
+ * Split: CH = C / 8 threads cover a row, G = 256 / CH rows are read per pass of a 256-thread workgroup, a slab is
+ *   pk_activation_stats_slab(C) = 4 G rows, B = pk_activation_stats_blocks(M, C) = min(512, ceil(M / slab)) workgroups, workgroup b takes
+ *   slabs b, b + B, ...  Order of the two sums, per channel: thread (b, r) adds its rows s slab + u G + r in ascending (s, u) to 0.0; the
+ *   workgroup adds its threads r = 0, 1, ..., G - 1 from left to right; the finalize adds the workgroups g, g + 16, g + 32, ... in ascending
+ *   order to 0.0 in each of 16 groups g, then the groups 0, 1, ..., 15 from left to right.
+ *   +-0 are counted in registers and enter the table in the finalize, never as LDS atomics.
+ * pk_activation_stats: two launches.  ws: pk_activation_stats_ws_bytes(M, C) bytes, 16-byte aligned, as x and records; hist 8-byte.
+ *   accumulate != 0: every field of the records and the table becomes old + new (new computed as above), min / max are combined;
+ *   accumulate == 0 overwrites.
+ * pk_activation_quantiles: exact order statistics of the finite elements of the channels < c_used, three launches.  hist: the table of
+ *   pk_activation_stats of the same x and c_used.  q_host: HOST pointer to Q <= PK_ACT_MAX_QUANTILES doubles in [0, 1], read before the
+ *   call returns.  With the n finite values v[0] <= ... <= v[n-1] (-0 == +0): pos = q (double)(n - 1), lo = floor(pos), hi = min(lo + 1,
+ *   n - 1) (pk_kpt_error_quantiles' rule); order (Q,2) f32 on the device = v[lo], v[hi]; a zero comes out as +0; n == 0: NaN.  A rank's bin
+ *   is found in the table, one more pass over x counts the low four key bits inside the selected bins: bin and sub-bin are all 16 bits.
+ *   ws: pk_activation_quantiles_ws_bytes(M, C) bytes, 16-byte aligned.
+ * Refused before any launch, in this order: a null pointer; C % 8; C outside its range; c_used outside [1, C]; M C outside [1, 2^38]; Q;
+ *   a q outside [0, 1] or NaN; misalignment; a workspace that is too small.  For a refused shape pk_activation_stats_blocks returns 0 (a count), the other queries PK_ERR_INVALID.      */
+#define PK_ACT_RECORD_BYTES 64
+#define PK_ACT_HIST_BINS 4096
+#define PK_ACT_MAX_CHANNELS 2048
+#define PK_ACT_MAX_QUANTILES 16
+#define PK_ACT_MAX_ELEMS 274877906944
+int pk_activation_stats_slab(int C);
+int pk_activation_stats_blocks(int64_t M, int C);
+int pk_activation_stats_ws_bytes(int64_t M, int C);
+int pk_activation_stats(const void* x, int64_t M, int C, int c_used, void* ws, int64_t ws_bytes, void* records, int64_t* hist,
+                        int accumulate, void* stream);
+int pk_activation_quantiles_ws_bytes(int64_t M, int C);
+int pk_activation_quantiles(const void* x, int64_t M, int C, int c_used, const int64_t* hist, const double* q_host, int Q, void* ws,
+                            int64_t ws_bytes, float* order, void* stream);
+
 
 /* ======================= network contractions (bf16 MFMA, fp32 accumulate; NHWC activations) =======================
  * These replace the groups of ATen calls inside the reference's modules; weights are bf16 "compute copies" packed by

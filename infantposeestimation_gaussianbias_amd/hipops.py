@@ -1159,3 +1159,105 @@ def derive_tensor_stats(rec, scale=1.0):
     out["std"] = s * math.sqrt(var)
     out["abs_mean"] = s * float(rec["sumabs"]) / m
     return out
+
+
+# ------------------------------------------------------------------------------------------------ activation statistics
+# pk_activation_stats / pk_activation_quantiles: per-channel records, a 4096-bin table over the bf16 bit patterns and exact order
+# statistics of an NHWC bf16 feature map, on the current stream; nothing is read back.
+ACT_RECORD = np.dtype([("sum", "<f8"), ("sumsq", "<f8"), ("min", "<f4"), ("max", "<f4"), ("n", "<i8"), ("n_zero", "<i8"),
+                       ("n_negative", "<i8"), ("n_nonfinite", "<i8"), ("reserved", "<i8")])
+assert ACT_RECORD.itemsize == _lib.CONSTANTS["PK_ACT_RECORD_BYTES"]
+ACT_HIST_BINS = _lib.CONSTANTS["PK_ACT_HIST_BINS"]
+ACT_MAX_QUANTILES = _lib.CONSTANTS["PK_ACT_MAX_QUANTILES"]
+ACT_MAX_CHANNELS = _lib.CONSTANTS["PK_ACT_MAX_CHANNELS"]
+_ACT_WS = {}           # (device, stream, entry) -> the largest workspace asked for so far
+
+
+def _act_rows(x, c_used, who):
+    if not (isinstance(x, torch.Tensor) and x.is_cuda):
+        raise _lib.PoseKernelError(f"{who}: x: expected a CUDA(HIP) tensor; the hot path has no CPU implementation")
+    if x.dtype != BF16:
+        raise _lib.PoseKernelError(f"{who}: x: expected {BF16}, got {x.dtype}")
+    if x.dim() < 1 or x.numel() == 0:
+        raise ValueError(f"{who}: x: expected a non-empty (..., C) tensor, got {tuple(x.shape)}")
+    C = int(x.shape[-1])
+    if C % 8 or not 8 <= C <= ACT_MAX_CHANNELS:
+        raise ValueError(f"{who}: x: {C} channels (a multiple of 8 from 8 to {ACT_MAX_CHANNELS})")
+    c_used = C if c_used is None else int(c_used)
+    if not 1 <= c_used <= C:
+        raise ValueError(f"{who}: c_used={c_used} outside [1, {C}]")
+    x = x.contiguous()
+    return x, x.numel() // C, C, c_used
+
+
+def _act_ws(x, entry, M, C):
+    # one workspace per (device, stream, entry): launches on one stream are ordered, two streams must not share partials
+    key = (x.device, stream_ptr(), entry)
+    need = _query(f"pk_activation_{entry}_ws_bytes", M, C)
+    ws = _ACT_WS.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _ACT_WS[key] = torch.empty(need, dtype=torch.uint8, device=x.device)
+    return ws
+
+
+def activation_stats_blocks(M, C):
+    """Workgroups of the partial kernel for an (M, C) map and the rows of one slab: the split that fixes the order of the sums."""
+    return _query("pk_activation_stats_blocks", int(M), int(C)), _query("pk_activation_stats_slab", int(C))
+
+
+def activation_stats(x, c_used=None, records=None, hist=None):
+    """Per-channel records and the 4096-bin table of a device bf16 (..., C) tensor (pk_activation_stats; two launches on the current stream,
+    no synchronisation).  Channels >= c_used are padding.  -> (records: uint8, c_used x 64 bytes, see ACT_RECORD; hist: (4096,) int64).
+    With `records` and `hist` of an earlier call given, that call's numbers are added to in place (old + new per field, min / max
+    combined): several batches of one layer."""
+    x, M, C, c_used = _act_rows(x, c_used, "activation_stats")
+    if (records is None) != (hist is None):
+        raise ValueError("activation_stats: pass both records and hist of the earlier call, or neither")
+    accumulate = records is not None
+    if accumulate:
+        if _chk(records, torch.uint8, "records").numel() != c_used * ACT_RECORD.itemsize or not records.is_contiguous():
+            raise _lib.PoseKernelError(f"activation_stats: records must be {c_used * ACT_RECORD.itemsize} contiguous bytes")
+        if _chk(hist, I64, "hist").numel() != ACT_HIST_BINS or not hist.is_contiguous():
+            raise _lib.PoseKernelError(f"activation_stats: hist must be {ACT_HIST_BINS} contiguous int64 counts")
+    else:
+        records = torch.empty(c_used * ACT_RECORD.itemsize, dtype=torch.uint8, device=x.device)
+        hist = torch.empty(ACT_HIST_BINS, dtype=I64, device=x.device)
+    ws = _act_ws(x, "stats", M, C)
+    call("pk_activation_stats", x, M, C, c_used, ws, ws.numel(), records, hist, 1 if accumulate else 0, stream_ptr())
+    return records, hist
+
+
+def activation_quantiles(x, hist, q, c_used=None):
+    """Exact order statistics of the finite elements of the channels < c_used of x (pk_activation_quantiles; three launches on the current
+    stream, no synchronisation).  hist: the table `activation_stats` returned for the same x and c_used.  q: up to 16 host floats in [0, 1].
+    -> (Q,2) float32 on the device: v[lo], v[hi] around position q (n - 1) of the n values in ascending order; NaN when there is none."""
+    x, M, C, c_used = _act_rows(x, c_used, "activation_quantiles")
+    qs = np.ascontiguousarray(np.asarray(q, np.float64).reshape(-1))
+    if not 1 <= qs.size <= ACT_MAX_QUANTILES:
+        raise ValueError(f"activation_quantiles: q: expected 1 to {ACT_MAX_QUANTILES} quantiles, got {qs.size}")
+    if not bool(np.all((qs >= 0.0) & (qs <= 1.0))):
+        raise ValueError(f"activation_quantiles: q: every quantile must lie in [0, 1], got {qs.tolist()}")
+    if _chk(hist, I64, "hist").numel() != ACT_HIST_BINS or not hist.is_contiguous():
+        raise _lib.PoseKernelError(f"activation_quantiles: hist must be {ACT_HIST_BINS} contiguous int64 counts")
+    order = torch.empty(qs.size, 2, dtype=F32, device=x.device)
+    ws = _act_ws(x, "quantiles", M, C)
+    call("pk_activation_quantiles", x, M, C, c_used, hist, qs.ctypes.data, int(qs.size), ws, ws.numel(), order, stream_ptr())
+    return order
+
+
+def activation_records(records):
+    """The records tensor as a numpy structured array (ONE device read)."""
+    return records.cpu().numpy().view(ACT_RECORD)
+
+
+def activation_bin_edges():
+    """The 4097 edges of the table as float64: bin b holds lo[b] <= x < lo[b + 1], the same for every tensor.  Edge b is the smallest
+    value of bin b -- the bf16 whose key is 16 b -- except inside the two NaN ranges at either end, where it is -inf / +inf."""
+    keys = (np.arange(ACT_HIST_BINS + 1, dtype=np.int64) << 4)
+    keys[-1] = 0xffff
+    bits = np.where(keys & 0x8000, keys & 0x7fff, ~keys & 0xffff).astype(np.uint32)
+    with np.errstate(invalid="ignore"):
+        edges = (bits << 16).view(np.float32).astype(np.float64)
+    edges[np.isnan(edges) & (np.arange(ACT_HIST_BINS + 1) < ACT_HIST_BINS // 2)] = -np.inf
+    edges[np.isnan(edges)] = np.inf
+    return edges

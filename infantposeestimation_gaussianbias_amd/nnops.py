@@ -30,6 +30,37 @@ def _e(shape, dtype, dev):
     return torch.empty(shape, dtype=dtype, device=dev)
 
 
+# Activation observer (utils/activations.py): the points where an activation exists in memory in every mode hand it to the installed
+# collector -- the output of conv_bn_act (kind "conv_bn", key: the BatchNorm module), of window_block ("window_block", key: the block)
+# and every output of an exchange unit ("exchange", key: (fuse ModuleDict, output index)).  In eval mode BatchNorm and ReLU sit in the
+# conv's epilogue and the block halves are fused, so there is no nn.ReLU a forward hook could sit on.  Without a collector a tap is one
+# `if`: no C call more or less than before.  A tap runs on the stream of the branch task it is called from, launches there, and never
+# reads back or synchronises.  Not tapped: the tensors inside the grouped exchange launches (exchange.py) and inside the block halves.
+_OBSERVER = [None]
+
+
+class observe:
+    """`with nnops.observe(collector):` -- collector.tap(kind, key, tensor, relu) is called at every tap of the forwards inside."""
+
+    def __init__(self, collector):
+        self.collector = collector
+
+    def __enter__(self):
+        if _OBSERVER[0] is not None:
+            raise RuntimeError("nnops.observe: an activation collector is already installed")
+        _OBSERVER[0] = self.collector
+        return self.collector
+
+    def __exit__(self, *exc):
+        _OBSERVER[0] = None
+
+
+def _tap(kind, key, tensor, relu=True):
+    if _OBSERVER[0] is not None:
+        _OBSERVER[0].tap(kind, key, tensor, relu)
+    return tensor
+
+
 # Optional per-sample DropPath scale of a block half: fp32 for the kernels, an empty tensor in save_for_backward when there is none.
 def _scale(s):
     return None if s is None else s.float().contiguous()
@@ -586,8 +617,8 @@ class _ConvBnAct(torch.autograd.Function):
 
 def conv_bn_act(x, conv, bn, relu=False, residual=None, training=False, skip_out=None, skip_in=None):
     # (grad mode is always off INSIDE an autograd Function's forward: whether nothing will be differentiated is decided here)
-    return _ConvBnAct.apply(x, conv.weight, bn.weight, bn.bias, residual, bn, conv.stride[0], relu, training, skip_out, skip_in,
-                            not torch.is_grad_enabled())
+    return _tap("conv_bn", bn, _ConvBnAct.apply(x, conv.weight, bn.weight, bn.bias, residual, bn, conv.stride[0], relu, training, skip_out,
+                                                skip_in, not torch.is_grad_enabled()), relu)
 
 
 def residual_block(x, first, middle, last, training):
@@ -1165,6 +1196,10 @@ class _AttnHalfFused(torch.autograd.Function):
 
 
 def window_block(x, blk, heads, scale1=None, scale2=None):
+    return _tap("window_block", blk, _window_block(x, blk, heads, scale1, scale2), False)
+
+
+def _window_block(x, blk, heads, scale1, scale2):
     a = blk.attn
     c_real, attn_scale = getattr(blk, "c_real", 0), getattr(blk, "attn_scale", 0.0)      # set on padded twins (models/padded.py)
     needs_grad = torch.is_grad_enabled() and (x.requires_grad or blk.norm1.weight.requires_grad)
@@ -1247,6 +1282,13 @@ def fuse_sum(xs, relu=True):
     return _FuseSum.apply(relu, *xs)
 
 
+def _tap_outputs(fuse, outs, ys):
+    if _OBSERVER[0] is not None:
+        for i, y in zip(outs, ys):
+            _tap("exchange", (fuse, i), y)
+    return ys
+
+
 def exchange(xs, fuse, training, n_out=None, first_only=False):
     """Exchange unit (hrformer.py:462-491 == hrnet.py:198-227): out_i = relu(sum_j route_{j->i}(x_j)).
 
@@ -1261,12 +1303,13 @@ def exchange(xs, fuse, training, n_out=None, first_only=False):
     if xg.usable(training, xs) and 1 < n <= 4 and (first_only or xg.whole_unit()):
         # grouped launches: one launch per kernel family and dependency level of the unit (exchange.py)
         if first_only:
-            y0 = xg.unit(xs, fuse, training, outs=[0])
+            y0 = _tap_outputs(fuse, [0], xg.unit(xs, fuse, training, outs=[0]))
             if training:        # the unused outputs (see below): BatchNorm running statistics only, off the critical path
                 det = [t.detach() for t in xs]
                 dispatch.run_detached(lambda: xg.unit(det, fuse, training, outs=range(1, n)), det)
             return y0
-        return xg.unit(xs, fuse, training, outs=range(n if n_out is None else n_out))
+        outs = range(n if n_out is None else n_out)
+        return _tap_outputs(fuse, outs, xg.unit(xs, fuse, training, outs=outs))
     if first_only and n > 1:
         # Last module of the network: only output 0 is consumed (hrformer.py:776 / hrnet.py:441).  The reference still computes outputs
         # 1..n-1; their only lasting effect is the running-statistics update of their BatchNorm layers in training mode.  They leave the
@@ -1287,7 +1330,7 @@ def exchange_output(i, xs, fuse, training):
     from . import exchange as xg
     if xg.usable(training, xs) and 1 < len(xs) <= 4:
         # the routes into output i as grouped launches: one launch per kernel family and chain level (exchange.py)
-        return xg.unit(list(xs), fuse, training, outs=[i])[0]
+        return _tap_outputs(fuse, [i], xg.unit(list(xs), fuse, training, outs=[i]))[0]
     terms = []
     for j in range(len(xs)):
         if j == i:
@@ -1301,7 +1344,7 @@ def exchange_output(i, xs, fuse, training):
             for s, (conv, bn) in enumerate(chain):
                 t = conv_bn_act(t, conv, bn, s != len(chain) - 1, None, training)
             terms.append(t)
-    return fuse_sum(terms, True)
+    return _tap("exchange", (fuse, i), fuse_sum(terms, True))
 
 
 def drop_scales(n_draws, batch, drop_prob, device):

@@ -2,6 +2,8 @@
 from .metrics import (AverageMeter, COCOEvaluator, KeypointErrorAnalyzer, MetricLogger, PCKAccumulator, calculate_movement_amplitude,
                       calculate_pck, calculate_temporal_consistency, keypoint_error_report, movement_heatmap, movement_report,
                       movement_spectrum)
+from . import activations
+from .activations import ActivationAnalyzer, ActivationCollector, activation_report
 from . import postprocess
 from .postprocess import oks_nms, soft_oks_nms
 from . import sensitivity
@@ -17,4 +19,5 @@ __all__ = ['AverageMeter', 'COCOEvaluator', 'MetricLogger', 'postprocess', 'visu
            'COCO_COLORS', 'PCKAccumulator', 'calculate_movement_amplitude', 'calculate_pck', 'calculate_temporal_consistency',
            'movement_heatmap', 'movement_report', 'movement_spectrum', 'oks_nms', 'soft_oks_nms', 'tensor_stats', 'tensor_statistics',
            'gradient_statistics', 'gradient_flow', 'weight_statistics', 'KeypointErrorAnalyzer',
-           'keypoint_error_report', 'sensitivity', 'SensitivityAnalyzer', 'occlusion_sensitivity_maps']
+           'keypoint_error_report', 'sensitivity', 'SensitivityAnalyzer', 'occlusion_sensitivity_maps', 'activations',
+           'ActivationAnalyzer', 'ActivationCollector', 'activation_report']

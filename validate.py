@@ -8,7 +8,8 @@ by OKS-NMS on the device, then AP; plus --decode {shift,unbiased} / --modulate_k
 the quarter-pixel shift (the default) or the unbiased, distribution-aware step on the log of the smoothed map); plus --ema to score the
 averaged weights of a checkpoint written by `train.py --ema`; plus --error_report PATH / --error_px T for the localisation error
 analysis: per joint the quantiles of the error in image pixels, the calibration of the confidence and precision / recall of "within T
-pixels" over a confidence threshold, gathered on the device and written as JSON).
+pixels" over a confidence threshold, gathered on the device and written as JSON; plus --activation_report PATH / --activation_batches N for
+the activation statistics and dead channels of every tapped layer, likewise).
 
 Flip-test inference + decode run entirely on the GPU (`PoseEstimator.inference`: two forwards, one flip-merge kernel, one
 decode kernel); the heat-px -> image transform of validate.py:100-117 is one kernel (`heatmap_to_image_coords`) instead of a
@@ -185,7 +186,29 @@ def main(args):
     metrics, _ = validate(model, loader, device, cfg, logger, flip_test=not args.no_flip, scales=cfg.test_scales, pck_thresholds=pck_thresholds,
                           error_analysis=error_analysis, error_report=getattr(args, "error_report", None))
     logger.info(f"Loss: {metrics['loss']:.4f}")
+    if getattr(args, "activation_report", None):
+        log_activation_report(model, loader, device, logger, args.activation_report, getattr(args, "activation_batches", 1))
     return metrics
+
+
+def log_activation_report(model, loader, device, logger, path=None, max_batches=1):
+    """Activation statistics of every tapped layer over the first `max_batches` batches of `loader` (utils/activations.py), gathered on
+    the device: one log line per layer more than half of whose channels are dead, and the whole report as JSON to `path`."""
+    import json
+    from infantposeestimation_gaussianbias_amd.utils.activations import activation_report, activation_report_json
+    model.eval()
+    batches = (batch["img"].to(device) for batch in loader)
+    report = activation_report(model, batches, max_batches=max_batches)
+    for name, r in report.items():
+        if r["dead_ratio"] > 0.5:
+            logger.info(f"  {name}: {100 * r['dead_ratio']:.1f} % of {len(r['channel_mean'])} channels dead "
+                        f"(zero fraction {r['zero_fraction']:.3f})")
+    logger.info(f"Activation statistics of {len(report)} layers over {max(r['batches'] for r in report.values()) if report else 0} batches")
+    if path:
+        with open(path, "w") as f:
+            json.dump(activation_report_json(report), f)
+        logger.info(f"Activation report written to {path}")
+    return report
 
 
 def apply_detector_box_args(cfg, args):
@@ -223,6 +246,11 @@ def build_parser():
                         "precision / recall of 'within --error_px' over a confidence threshold with its AP (default: nothing)")
     p.add_argument("--error_px", type=float, default=10.0, metavar="T",
                    help="--error_report: a keypoint is correct when it lies less than T image pixels from its ground truth (default 10)")
+    p.add_argument("--activation_report", type=str, default=None, metavar="PATH",
+                   help="after validation, also gather activation statistics of every tapped layer on the device and write them to PATH as "
+                        "JSON: mean, std, min, max, quantiles, zero / negative fractions and the dead channels per layer (default: nothing)")
+    p.add_argument("--activation_batches", type=int, default=1, metavar="N",
+                   help="--activation_report: how many batches of the loader to run (default 1, as the reference's dead-neuron analysis)")
     p.add_argument("--bbox_file", type=str, default=None,
                    help="validate on detector boxes: a COCO-style person-detection file [{image_id, category_id, bbox, score}], relative to "
                         "data_root (default: the config's bbox_file; none: crops from the ground-truth boxes)")
