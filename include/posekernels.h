@@ -471,6 +471,36 @@ int pk_activation_quantiles_ws_bytes(int64_t M, int C);
 int pk_activation_quantiles(const void* x, int64_t M, int C, int c_used, const int64_t* hist, const double* q_host, int Q, void* ws,
                             int64_t ws_bytes, float* order, void* stream);
 
+/* ---- stochastic-depth ensembles (this project's own specification, DESIGN.md "Predictive uncertainty"): what S stacked outputs of one
+ * input say together.  No atomics; every floating-point sum is taken in a fixed order, so the same input gives the same bits.
+ * pk_ensemble_moments: element i of member s is stack[s member_stride + i], i < L, member_stride >= L.  Per element, in float64 and
+ *   without FMA: m = (((0.0 + v_0) + v_1) + ... + v_{S-1}) / S; q = (((0.0 + (v_0 - m)^2) + (v_1 - m)^2) + ...), ascending s;
+ *   mean[i] = m and std[i] = sqrt(q / (S - ddof)), each narrowed to fp32 round to nearest even.  NaN and inf propagate (an inf member gives
+ *   mean inf and std NaN).  ddof 0 (np.std) or 1.  One thread per 16-byte group of four elements when L and member_stride are multiples of
+ *   4 and the three pointers are 16-byte aligned, else one thread per element; a grid-stride loop over at most PK_ENS_GRID_CAP workgroups
+ *   of 256.  S <= PK_ENS_REG_MEMBERS: the stack is read once, the members held in registers; above: two reads, sum then squares.  Both
+ *   forms are the arithmetic above, bit for bit.  Refused before the launch: a null pointer; S < 1 + ddof; ddof outside 0..1; L < 1;
+ *   member_stride < L; an output that overlaps the stack or the other output.
+ * pk_ensemble_points: coords (S,M,2) fp32, conf (S,M) fp32 or NULL, centre (M,2) float64 or NULL, out (M,12) float64.  One 256-thread
+ *   workgroup per point m (workgroups stride over m beyond PK_ENS_POINT_GRID_CAP).  Member s is valid iff both coordinates are finite and
+ *   (conf == NULL or conf is finite and >= min_conf).  Every reduction is pk_heatmap_summary's: thread t takes the valid members among
+ *   t, t + 256, ... in ascending order, starting from 0.0 (+inf for the minimum), then the xor butterfly 32, 16, ..., 1 inside each wave,
+ *   then wave 0 op wave 1 op wave 2 op wave 3.  All arithmetic float64 without FMA.  First pass: n, sum x, sum y, sum conf, min conf;
+ *   mx = sum x / n, my = sum y / n, mc = sum conf / n.  (cx, cy) = centre[m], or (mx, my) when centre == NULL.  Second pass, per valid
+ *   member: dx = x - mx, dy = y - my, dc = conf - mc; the sums of dx dx, dy dy, dx dy, dc dc; and the count of members with
+ *   (x - cx)(x - cx) + (y - cy)(y - cy) <= radius radius.  Columns: 0 n; 1, 2 mx, my; 3, 4, 5 vx, vy, c = those sums / (n - ddof);
+ *   6, 7 the eigenvalues of [[vx, c], [c, vy]] (squared semi-axes of the 1-sigma ellipse): h = (vx + vy) 0.5, d = (vx - vy) 0.5,
+ *   r = sqrt(d d + c c), l1 = h + r, l2 = h - r if that is > 0, else 0; 8, 9, 10 mc, sqrt(sum dc dc / (n - ddof)), min conf (all three 0
+ *   when conf == NULL); 11 the agreement count.  n < 1 + ddof: the whole row is 0.  Refused before the launch: a null coords or out;
+ *   S < 1 or M < 1; S M >= 2^61; a radius that is negative or not finite; ddof outside 0..1.                                        */
+#define PK_ENS_REG_MEMBERS 32
+#define PK_ENS_GRID_CAP 4096
+#define PK_ENS_POINT_GRID_CAP 65536
+#define PK_ENS_POINT_COLS 12
+int pk_ensemble_moments(const float* stack, int64_t member_stride, int S, int64_t L, int ddof, float* mean, float* std, void* stream);
+int pk_ensemble_points(const float* coords /* (S,M,2) */, const float* conf /* (S,M) or NULL */, const double* centre /* (M,2) or NULL */,
+                       double* out /* (M,12) */, int S, int64_t M, float min_conf, double radius, int ddof, void* stream);
+
 
 /* ======================= network contractions (bf16 MFMA, fp32 accumulate; NHWC activations) =======================
  * These replace the groups of ATen calls inside the reference's modules; weights are bf16 "compute copies" packed by

@@ -887,6 +887,78 @@ def occlusion_paint(base, table, H, W, patch, stride, measure="sum"):
     return maps
 
 
+# ------------------------------------------------------------------------------------------------ ensembles
+ENSEMBLE_POINT_COLUMNS = ("n", "mean_x", "mean_y", "var_x", "var_y", "cov_xy", "axis_major_sq", "axis_minor_sq", "conf_mean", "conf_std",
+                          "conf_min", "agreement")
+
+
+def _ddof(who, ddof):
+    if ddof not in (0, 1):
+        raise _lib.PoseKernelError(f"{who}: ddof {ddof!r} (0 or 1)")
+    return int(ddof)
+
+
+def ensemble_moments(stack, ddof=0, out=None):
+    """(S, ...) fp32 -> mean, std (...) fp32 over the S members, per element in float64 in ascending member order (pk_ensemble_moments; one
+    launch, no synchronisation).  ddof 0 is np.std.  The stack may be a view whose member stride exceeds the member's size (a slice of a
+    wider buffer); each member itself must be contiguous.  `out`: a pair of contiguous fp32 device tensors (...) to write into."""
+    ddof = _ddof("ensemble_moments", ddof)
+    if not (isinstance(stack, torch.Tensor) and stack.is_cuda):
+        raise _lib.PoseKernelError("stack: expected a CUDA(HIP) tensor; the hot path has no CPU implementation")
+    if stack.dtype != F32:
+        raise _lib.PoseKernelError(f"stack: expected {F32}, got {stack.dtype}")
+    if stack.dim() < 1:
+        raise _lib.PoseKernelError(f"ensemble_moments: stack {tuple(stack.shape)} is not (S, ...)")
+    S, rest = int(stack.shape[0]), tuple(stack.shape[1:])
+    L = int(np.prod(rest, dtype=np.int64)) if rest else 1
+    if S < 1 + ddof:
+        raise _lib.PoseKernelError(f"ensemble_moments: {S} members with ddof={ddof} (at least {1 + ddof})")
+    if L and not (stack[0].is_contiguous() and (S == 1 or stack.stride(0) >= L)):
+        stack = stack.contiguous()
+    stride = int(stack.stride(0)) if S > 1 and L else max(L, 1)
+    if out is None:
+        mean, std = torch.empty(rest, dtype=F32, device=stack.device), torch.empty(rest, dtype=F32, device=stack.device)
+    else:
+        mean, std = out
+        for t in (mean, std):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == F32 and t.is_contiguous() and tuple(t.shape) == rest):
+                raise _lib.PoseKernelError(f"ensemble_moments: out must be two contiguous fp32 device tensors {rest}")
+    _call_if(L, "pk_ensemble_moments", stack, stride, S, L, ddof, mean, std, stream_ptr())
+    return mean, std
+
+
+def ensemble_points(coords, conf=None, centre=None, min_conf=0.0, radius=1.0, ddof=0, out=None):
+    """coords (S,M,2) fp32, conf (S,M) fp32 or None, centre (M,2) float64 or None -> (M,12) float64, the columns of
+    ENSEMBLE_POINT_COLUMNS (pk_ensemble_points; one launch, no synchronisation): the number of valid members (finite, conf >= min_conf),
+    their mean position, variances and covariance, the squared semi-axes of the 1-sigma ellipse, mean / std / min of conf, and how many
+    lie within `radius` of `centre` (None: of the mean).  Fewer than 1 + ddof valid members: a row of zeros."""
+    ddof = _ddof("ensemble_points", ddof)
+    coords = _chk(coords, name="coords")
+    if coords.dim() != 3 or coords.shape[-1] != 2:
+        raise _lib.PoseKernelError(f"ensemble_points: coords {tuple(coords.shape)} are not (S, M, 2)")
+    S, M = int(coords.shape[0]), int(coords.shape[1])
+    if conf is not None:
+        conf = _chk(conf, name="conf")
+        if tuple(conf.shape) != (S, M):
+            raise _lib.PoseKernelError(f"ensemble_points: conf {tuple(conf.shape)} is not ({S}, {M})")
+    if centre is not None:
+        centre = _chk(centre, F64, "centre")
+        if tuple(centre.shape) != (M, 2):
+            raise _lib.PoseKernelError(f"ensemble_points: centre {tuple(centre.shape)} is not ({M}, 2)")
+    radius = float(radius)
+    if not (radius >= 0.0 and math.isfinite(radius)):
+        raise _lib.PoseKernelError(f"ensemble_points: radius {radius} (finite, at least 0)")
+    if S < 1:
+        raise _lib.PoseKernelError("ensemble_points: no members")
+    if out is None:
+        out = torch.empty(M, len(ENSEMBLE_POINT_COLUMNS), dtype=F64, device=coords.device)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == F64 and out.is_contiguous()
+              and tuple(out.shape) == (M, len(ENSEMBLE_POINT_COLUMNS))):
+        raise _lib.PoseKernelError(f"ensemble_points: out must be a contiguous float64 device tensor ({M}, {len(ENSEMBLE_POINT_COLUMNS)})")
+    _call_if(M, "pk_ensemble_points", coords, conf, centre, out, S, M, float(min_conf), radius, ddof, stream_ptr())
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ overlays
 U8 = torch.uint8
 

@@ -115,6 +115,10 @@ class HRFormerBlock(nn.Module):
             if self.training and self.drop_prob > 0:
                 sc = nnops.drop_scales(2, t.shape[0], self.drop_prob, t.device)
                 s1, s2 = sc[0], sc[1]
+            elif not self.training:              # eval mode draws only inside nnops.stochastic_depth
+                sc = nnops.eval_drop_scales(2, t.shape[0], self.drop_prob, t.device)
+                if sc is not None:
+                    s1, s2 = sc[0], sc[1]
             return nnops.to_public(nnops.window_block(t, self, self.heads, s1, s2))
 
 
@@ -216,6 +220,8 @@ class HRFormer(nn.Module):
         scales = None
         if tr and self.drop_path_rate > 0:
             scales = nnops.drop_scales(sum(m.n_draws() for m in mods), x.shape[0], self.drop_path_rate, x.device)
+        elif not tr:                                 # eval mode draws only inside nnops.stochastic_depth (None outside it)
+            scales = nnops.eval_drop_scales(sum(m.n_draws() for m in mods), x.shape[0], self.drop_path_rate, x.device)
         d = 0
         for s in (2, 3, 4):
             trans = getattr(self, f"transition{s - 1}")

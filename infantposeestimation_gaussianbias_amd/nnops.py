@@ -1353,6 +1353,59 @@ def drop_scales(n_draws, batch, drop_prob, device):
     return torch.floor(keep + torch.rand(n_draws, batch, device=device)) / keep
 
 
+_STOCHASTIC_DEPTH = []
+
+
+class stochastic_depth:
+    """`with nnops.stochastic_depth(...) as sd:` -- inside it an HRFormer backbone (or a stand-alone HRFormerBlock) in EVAL mode draws
+    DropPath multipliers as it does in training: two per block, branch-major, modules in stage order.  BatchNorm stays on its running
+    statistics; nothing else changes, and nothing at all outside the context (DESIGN.md "Predictive uncertainty").
+    rate: overrides the model's drop_path_rate; 0 = no scales, the plain eval forward bit for bit.
+    generator: a device torch.Generator for the draw, floor(keep + rand(n_draws, B)) / keep in one launch.
+    scales: an explicit (n_draws, B) fp32 device tensor used instead of drawing (replaying members; chunked runs).
+    `.scales` is the tensor the last forward inside the context used (None: it used none); `.uses` counts those forwards."""
+
+    def __init__(self, rate=None, generator=None, scales=None):
+        if rate is not None and not 0.0 <= float(rate) < 1.0:
+            raise ValueError(f"stochastic_depth: rate {rate} outside [0, 1)")
+        if scales is not None and not (isinstance(scales, torch.Tensor) and scales.dim() == 2 and scales.dtype == F32):
+            raise ValueError("stochastic_depth: scales must be an fp32 tensor (n_draws, B)")
+        self.rate, self.generator, self.explicit = (None if rate is None else float(rate)), generator, scales
+        self.scales, self.uses = None, 0
+
+    def __enter__(self):
+        _STOCHASTIC_DEPTH.append(self)
+        return self
+
+    def __exit__(self, *exc):
+        _STOCHASTIC_DEPTH.remove(self)
+        return False
+
+    def draw(self, n_draws, batch, drop_prob, device):
+        """The (n_draws, B) multipliers of one forward, or None when the effective rate is 0 and no scales were given."""
+        self.uses += 1
+        if self.explicit is not None:
+            if tuple(self.explicit.shape) != (n_draws, batch) or self.explicit.device != device:
+                raise ValueError(f"stochastic_depth: scales {tuple(self.explicit.shape)} on {self.explicit.device}, but this forward takes "
+                                 f"({n_draws}, {batch}) on {device}")
+            self.scales = self.explicit.contiguous()
+        else:
+            rate = float(drop_prob) if self.rate is None else self.rate
+            if rate <= 0.0 or n_draws == 0:
+                self.scales = None
+            else:
+                keep = 1.0 - rate
+                self.scales = torch.floor(keep + torch.rand(n_draws, batch, device=device, generator=self.generator)) / keep
+        return self.scales
+
+
+def eval_drop_scales(n_draws, batch, drop_prob, device):
+    """The multipliers of an eval-mode forward: None outside `stochastic_depth`, the innermost context's draw inside it."""
+    if not _STOCHASTIC_DEPTH:
+        return None
+    return _STOCHASTIC_DEPTH[-1].draw(n_draws, batch, drop_prob, device)
+
+
 # ================================================================================================ backend choice
 def supported(model) -> bool:
     """True when every conv / linear of `model` fits the HIP kernels (channels % 8 == 0, head_dim a multiple of 8 up to 64)."""

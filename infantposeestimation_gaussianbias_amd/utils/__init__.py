@@ -10,6 +10,8 @@ from . import sensitivity
 from .sensitivity import SensitivityAnalyzer, occlusion_sensitivity_maps
 from . import tensor_stats
 from .tensor_stats import gradient_flow, gradient_statistics, tensor_statistics, weight_statistics
+from . import uncertainty
+from .uncertainty import UncertaintyAnalyzer, mc_uncertainty
 from . import visualization
 from .visualization import (COCO_COLORS, COCO_SKELETON, create_grid_image, draw_bbox, draw_heatmaps, draw_person_heatmaps, draw_poses,
                             draw_skeleton, save_person_visualization, save_visualization)
@@ -20,4 +22,4 @@ __all__ = ['AverageMeter', 'COCOEvaluator', 'MetricLogger', 'postprocess', 'visu
            'movement_heatmap', 'movement_report', 'movement_spectrum', 'oks_nms', 'soft_oks_nms', 'tensor_stats', 'tensor_statistics',
            'gradient_statistics', 'gradient_flow', 'weight_statistics', 'KeypointErrorAnalyzer',
            'keypoint_error_report', 'sensitivity', 'SensitivityAnalyzer', 'occlusion_sensitivity_maps', 'activations',
-           'ActivationAnalyzer', 'ActivationCollector', 'activation_report']
+           'ActivationAnalyzer', 'ActivationCollector', 'activation_report', 'uncertainty', 'UncertaintyAnalyzer', 'mc_uncertainty']

@@ -18,6 +18,9 @@ pk_heatmap_overlay, pk_heatmap_overlay_patches: this project's own integer raste
 with Pillow.
 `occlusion_sensitivity` / `--occlusion_map JOINT` answer which part of a person's crop the network needs: one batched sweep of occluded
 copies on the device gives the map of every joint (utils/sensitivity.py), and the chosen joint's map is drawn where the crop lies.
+`uncertainty` / `--uncertainty S` answer which joints of a person to distrust: S stochastic-depth members of the model in one batched pass
+(utils/uncertainty.py) give per joint the spread of the predicted position as a 1-sigma ellipse in image pixels, the agreement of the
+members and the spread of the peak, and the std maps are drawn where the crop lies.
 """
 import argparse
 import os
@@ -38,6 +41,7 @@ from infantposeestimation_gaussianbias_amd.models import build_model  # noqa: E4
 from infantposeestimation_gaussianbias_amd.utils.metrics import movement_heatmap, movement_report  # noqa: E402
 from infantposeestimation_gaussianbias_amd.utils.postprocess import heatmap_to_image_coords, temporal_smoothing  # noqa: E402
 from infantposeestimation_gaussianbias_amd.utils.sensitivity import occlusion_sensitivity_maps  # noqa: E402
+from infantposeestimation_gaussianbias_amd.utils.uncertainty import mc_uncertainty  # noqa: E402
 from infantposeestimation_gaussianbias_amd.utils.visualization import (COCO_SKELETON, crop_heatmap_matrices, draw_heatmaps, draw_person_heatmaps,  # noqa: E402
                                                                        draw_poses, draw_skeleton, write_image)
 
@@ -207,6 +211,31 @@ class PoseInference:
         out['center'], out['scale'] = center, scale
         return out
 
+    def uncertainty(self, img: np.ndarray, bbox: Optional[np.ndarray] = None, samples: int = 30, rate: Optional[float] = None, seed: int = 0,
+                    **kw):
+        """Which joints to distrust: `samples` stochastic-depth members (utils.uncertainty.mc_uncertainty; `kw`: batch_size, radius,
+        ddof) on the crop `predict` takes for this image and box, un-flipped, drawn from a device generator seeded with `seed`.  -> the
+        dict of mc_uncertainty (heat-pixel numbers and maps) plus, still on the device, `points_image` (K,12): the rows of `points` in
+        image pixels -- the mean position through the crop's map (`_image_coords`), var x, var y and cov xy times fx fx, fy fy and fx fy with
+        (fx, fy) = scale / heatmap_size, the crop's linear part, and the squared ellipse axes recomputed from them by the kernel's formula
+        (columns 0 and 8..11 do not depend on the frame) -- `factors` (fx, fy), and `center` and `scale` of the crop."""
+        x, center, scale = self.preprocess(img, bbox)
+        gen = torch.Generator(device=self.device)
+        gen.manual_seed(int(seed))
+        out = mc_uncertainty(self.model, x, num_samples=samples, rate=rate, generator=gen, **kw)
+        wh = self.cfg.data.heatmap_size
+        fx, fy = float(scale[0]) / wh[0], float(scale[1]) / wh[1]
+        p = out['points']
+        q = p.clone()
+        q[:, 1:3] = self._image_coords(p[None, :, 1:3].float().contiguous(), center[None], scale[None])[0].double()
+        q[:, 3], q[:, 4], q[:, 5] = p[:, 3] * (fx * fx), p[:, 4] * (fy * fy), p[:, 5] * (fx * fy)
+        h, d = (q[:, 3] + q[:, 4]) * 0.5, (q[:, 3] - q[:, 4]) * 0.5
+        r = torch.sqrt(d * d + q[:, 5] * q[:, 5])
+        q[:, 6], q[:, 7] = h + r, (h - r).clamp_min(0.0)
+        q = torch.where(p[:, :1] == 0, torch.zeros_like(q), q)        # a row without valid members stays a row of zeros
+        out['points_image'], out['factors'], out['center'], out['scale'] = q, (fx, fy), center, scale
+        return out
+
     # ---- inference.py:238-262
     def visualize(self, img, keypoints, scores, score_threshold: float = 0.3, output_path: Optional[str] = None):
         """The skeleton of one prediction on a copy of `img` (BGR); saved too when `output_path` is given."""
@@ -327,6 +356,34 @@ def main_occlusion(args, pose, img, bbox):
     return res
 
 
+def main_uncertainty(args, pose, img, bbox):
+    """--uncertainty S: S stochastic-depth members on the person's crop; one line per joint, the same as JSON with --report, the std maps
+    drawn where the crop lies with --output."""
+    import json
+    res = pose.uncertainty(img, bbox, samples=int(args.uncertainty), rate=args.uncertainty_rate, seed=args.uncertainty_seed)
+    rows = res['points_image'].cpu().numpy()                      # the one read-back, after everything ran
+    S, (fx, fy) = int(res['stack'].shape[0]), res['factors']
+    print(f'Uncertainty: {S} stochastic-depth members, 1-sigma axes in image px (heat px x {fx:.4g}, {fy:.4g})')
+    joints = []
+    for k, r in enumerate(rows):
+        a, b = float(np.sqrt(r[6])), float(np.sqrt(r[7]))
+        print(f'  kpt {k:2d}: ({r[1]:8.2f}, {r[2]:8.2f})  axes {a:7.3f} x {b:7.3f} px  agree {int(r[11]):3d}/{int(r[0]):3d}  '
+              f'peak {r[8]:.3f} +- {r[9]:.3f}')
+        joints.append({'joint': k, 'x': float(r[1]), 'y': float(r[2]), 'axis_major': a, 'axis_minor': b, 'var_x': float(r[3]),
+                       'var_y': float(r[4]), 'cov_xy': float(r[5]), 'agreement': int(r[11]), 'members': int(r[0]),
+                       'peak_mean': float(r[8]), 'peak_std': float(r[9]), 'peak_min': float(r[10])})
+    if args.report:
+        with open(args.report, 'w') as f:
+            json.dump({'samples': S, 'rate': args.uncertainty_rate, 'seed': args.uncertainty_seed, 'joints': joints}, f, indent=2)
+            f.write('\n')
+        print(f'Uncertainty report saved to: {args.report}')
+    if args.output:
+        mats = crop_heatmap_matrices(res['center'], res['scale'], pose.input_size)
+        write_image(draw_person_heatmaps(img, res['std'][None], matrices=mats), args.output)
+        print(f'Result saved to: {args.output}')
+    return res
+
+
 def main(args):
     from PIL import Image
     if getattr(args, "freq_band", None) is not None and args.fps is None:
@@ -342,6 +399,8 @@ def main(args):
     bboxes = [np.array(args.bbox)] if args.bbox else detect_persons(img)
     if getattr(args, "occlusion_map", None) is not None:
         return main_occlusion(args, pose, img, bboxes[0])
+    if getattr(args, "uncertainty", None) is not None:
+        return main_uncertainty(args, pose, img, bboxes[0])
     whole = len(bboxes) == 1 and np.array_equal(np.asarray(bboxes[0], np.float64), [0, 0, img.shape[1], img.shape[0]])
     want_hm = bool(args.output and args.draw_heatmaps)
     t0 = time.time()
@@ -362,8 +421,21 @@ def main(args):
         print(f'Result saved to: {args.output}')
 
 
+class _Parser(argparse.ArgumentParser):
+    """--uncertainty excludes --occlusion_map and --sequence: refused while parsing, like any other bad combination of switches."""
+
+    def parse_args(self, args=None, namespace=None):
+        ns = super().parse_args(args, namespace)
+        if ns.uncertainty is not None:
+            if ns.uncertainty < 1:
+                self.error("--uncertainty takes the number of members, at least 1")
+            if ns.occlusion_map is not None or ns.sequence:
+                self.error("--uncertainty cannot be combined with --occlusion_map or --sequence")
+        return ns
+
+
 def build_parser():
-    p = argparse.ArgumentParser(description='Pose Estimation Inference')
+    p = _Parser(description='Pose Estimation Inference')
     p.add_argument('--checkpoint', type=str, default=None)
     p.add_argument('--input', type=str, required=True)
     p.add_argument('--output', type=str, default=None)
@@ -390,7 +462,8 @@ def build_parser():
                    help='--sequence with --fps: add the movement spectrum of the band LO to HI Hz to the report (per joint the dominant '
                         'frequency, its amplitude and the band power; per left/right pair the frequency difference); default: the '
                         'config\'s frequency_band')
-    p.add_argument('--report', type=str, default=None, help='--sequence: write the movement report (JSON) here instead of printing it')
+    p.add_argument('--report', type=str, default=None, help='--sequence: write the movement report (JSON) here instead of printing it; --uncertainty: write the per-joint numbers '
+                                                               '(JSON) here as well')
     p.add_argument('--decode', type=str, choices=('shift', 'unbiased'), default=None,
                    help='heatmap decode of a heatmap-head model, for single images, --scales and --sequence alike: shift = argmax + '
                         'quarter-pixel shift, unbiased = argmax + one Newton step on the log of the smoothed map (default: the config\'s '
@@ -410,6 +483,16 @@ def build_parser():
     p.add_argument('--occlusion_measure', type=str, choices=('sum', 'max', 'shift'), default='sum',
                    help='--occlusion_map: sum = drop of the heat map\'s sum (the reference\'s measure), max = drop of its peak (the keypoint '
                         'score), shift = distance in heat pixels the peak moved')
+    p.add_argument('--uncertainty', type=int, default=None, metavar='S',
+                   help='predictive uncertainty of the person in --bbox instead of the pose overlay: S members of the model that differ by '
+                        'stochastic depth (DropPath in an eval-mode forward) run as one batch on the device; prints per joint the ensemble '
+                        'position, the major and minor 1-sigma axes of the members\' peak positions in image pixels, how many members agree '
+                        'with the ensemble peak and the mean and std of the peak; --report writes the same as JSON, --output draws the std '
+                        'maps where the crop lies.  The spread is that of the model (epistemic), quantised to heat pixels; not with '
+                        '--occlusion_map or --sequence')
+    p.add_argument('--uncertainty_rate', type=float, default=None, metavar='R',
+                   help='--uncertainty: the stochastic-depth rate of the members (default: the model\'s drop_path_rate)')
+    p.add_argument('--uncertainty_seed', type=int, default=0, metavar='N', help='--uncertainty: seed of the device generator that draws the members')
     return p
 
 
