@@ -501,6 +501,37 @@ int pk_ensemble_moments(const float* stack, int64_t member_stride, int S, int64_
 int pk_ensemble_points(const float* coords /* (S,M,2) */, const float* conf /* (S,M) or NULL */, const double* centre /* (M,2) or NULL */,
                        double* out /* (M,12) */, int S, int64_t M, float min_conf, double radius, int ddof, void* stream);
 
+/* ---- gradient attribution (this project's own specification, DESIGN.md "Gradient attribution": input saliency and Grad-CAM of every
+ * joint from one batched backward; the reference's SensitivityAnalyzer.compute_input_sensitivity, analysis/advanced_analysis.py:317-342,
+ * and GradCAMVisualizer.generate_cam, analysis/nn_quantitative_viz.py:358-415).  No atomics; every reduction runs in a fixed order
+ * (per thread ascending, then the block reduction of pk_heatmap_summary), so the same input gives the same bits.
+ * pk_stem_dgrad: data gradient of the stem's 3x3, stride-2, pad-1 convolution.  g (B,Ho,Wo,Cout) bf16; w the FORWARD pack [Cout][9][8]
+ *   bf16 (mode 0 of pk_pack_weights); dx (B,Hs,Ws,8) bf16.  dx[b,y,x,c] = sum over the taps t = ky 3 + kx ascending with y + 1 - ky and
+ *   x + 1 - kx even and oy = (y + 1 - ky) / 2 < Ho, ox likewise < Wo (1, 2 or 4 taps per pixel), inside a tap over n ascending, of
+ *   g[b,oy,ox,n] w[n][t][c]: fp32 products (exact) and additions, one rounding to bf16 at the end; channels >= c_real are exactly 0.
+ *   One thread per input pixel, the pack staged once per workgroup in LDS.  Refused before the launch: a null or misaligned pointer;
+ *   Cout not a multiple of 8 or above PK_STEM_DGRAD_MAX_COUT; c_real outside 1..8; Ho != (Hs - 1) / 2 + 1 or Wo likewise;
+ *   B Hs Ws >= 2^31.
+ * pk_nhwc_bf16_to_nchw_f32: g (B,H,W,Cpad) bf16 -> out (B,C,H,W) fp32, C <= Cpad, Cpad a multiple of 8: out[b,c,y,x] = g[b,y,x,c]
+ *   widened (exact).  The backward of pk_nchw_f32_to_nhwc_bf16.
+ * pk_saliency_reduce: g (B,H,W,8) bf16 -> out (B,H,W) fp32 = max over c < c_real of |g_c| (exact; -0 gives +0).  A NaN in a real channel
+ *   gives NaN, as torch.max does; channels >= c_real are not looked at.
+ * pk_gradcam: A and G (B,h,w,C) bf16, C a multiple of 8, 1 <= c_used <= C (channels >= c_used are ignored).  Per sample b, in float64
+ *   without FMA: weight[c] = S_c / (h w), S_c the sum of G[b,p,c] over the pixels p in the order of pk_heatmap_summary's sum;
+ *   raw[p] = max(0, ((0.0 + weight[0] A[b,p,0]) + weight[1] A[b,p,1]) + ... over c < c_used), a NaN staying NaN; lo, hi = minimum and
+ *   maximum of raw; cam[b,p] = (raw[p] - lo) / ((hi - lo) + 1e-8) rounded once to fp32; weights (B,c_used) = weight rounded to fp32;
+ *   range (B,2) = lo, hi.  A NaN in any raw value makes lo, hi and the sample's whole map NaN.  Two launches: one workgroup per
+ *   (sample, 8-channel chunk) for the weights, one workgroup per sample for the map.  ws: float64 workspace of pk_gradcam_ws_floats
+ *   4-byte floats (per sample the weights of 8 ceil(c_used / 8) channels and the h w raw values; 0 for an empty problem).            */
+#define PK_STEM_DGRAD_MAX_COUT 256
+int pk_stem_dgrad(const void* g /* (B,Ho,Wo,Cout) bf16 */, const void* w /* [Cout][9][8] bf16 */, void* dx /* (B,Hs,Ws,8) bf16 */, int B, int Hs,
+                  int Ws, int Ho, int Wo, int Cout, int c_real, void* stream);
+int pk_nhwc_bf16_to_nchw_f32(const void* g /* (B,H,W,Cpad) bf16 */, float* out /* (B,C,H,W) */, int B, int C, int H, int W, int Cpad, void* stream);
+int pk_saliency_reduce(const void* g /* (B,H,W,8) bf16 */, float* out /* (B,H,W) */, int B, int H, int W, int c_real, void* stream);
+int pk_gradcam_ws_floats(int B, int h, int w, int c_used);
+int pk_gradcam(const void* A, const void* G /* (B,h,w,C) bf16 */, double* ws, float* cam /* (B,h,w) */, float* weights /* (B,c_used) */,
+               double* range /* (B,2): min, max of raw */, int B, int h, int w, int C, int c_used, void* stream);
+
 
 /* ======================= network contractions (bf16 MFMA, fp32 accumulate; NHWC activations) =======================
  * These replace the groups of ATen calls inside the reference's modules; weights are bf16 "compute copies" packed by

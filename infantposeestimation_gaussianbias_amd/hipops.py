@@ -959,6 +959,91 @@ def ensemble_points(coords, conf=None, centre=None, min_conf=0.0, radius=1.0, dd
     return out
 
 
+# ------------------------------------------------------------------------------------------------ gradient attribution
+STEM_DGRAD_MAX_COUT = _lib.CONSTANTS["PK_STEM_DGRAD_MAX_COUT"]
+
+
+def stem_dgrad(g, w_packed, in_hw, c_real=3):
+    """Data gradient of the stem's 3x3, stride-2, pad-1 conv (pk_stem_dgrad; one launch, no synchronisation).  g (B,Ho,Wo,Cout) bf16;
+    w_packed [Cout][9][8] bf16, the FORWARD weight pack; in_hw = (Hs, Ws) -> dx (B,Hs,Ws,8) bf16, the packed pixel's gradient: fp32 sums,
+    taps ascending then output channels ascending, one rounding; channels >= c_real exactly 0."""
+    g, w_packed = _chk(g, BF16, "g"), _chk(w_packed, BF16, "w_packed")
+    Hs, Ws = int(in_hw[0]), int(in_hw[1])
+    if g.dim() != 4:
+        raise _lib.PoseKernelError(f"stem_dgrad: g {tuple(g.shape)} is not (B, Ho, Wo, Cout)")
+    B, Ho, Wo, Cout = (int(s) for s in g.shape)
+    if Cout % 8 or not 0 < Cout <= STEM_DGRAD_MAX_COUT:
+        raise _lib.PoseKernelError(f"stem_dgrad: Cout={Cout} (a multiple of 8 up to {STEM_DGRAD_MAX_COUT})")
+    if tuple(w_packed.shape) != (Cout, 9, 8):
+        raise _lib.PoseKernelError(f"stem_dgrad: w_packed {tuple(w_packed.shape)} is not the forward pack ({Cout}, 9, 8)")
+    if not 1 <= int(c_real) <= 8:
+        raise _lib.PoseKernelError(f"stem_dgrad: c_real={c_real} (1 to 8)")
+    if Hs < 1 or Ws < 1 or (Ho, Wo) != ((Hs - 1) // 2 + 1, (Ws - 1) // 2 + 1):
+        raise _lib.PoseKernelError(f"stem_dgrad: g is {Ho} x {Wo}, a 3x3 stride-2 pad-1 conv of {Hs} x {Ws} gives "
+                                   f"{(Hs - 1) // 2 + 1} x {(Ws - 1) // 2 + 1}")
+    dx = torch.empty(B, Hs, Ws, 8, dtype=BF16, device=g.device)
+    _call_if(B, "pk_stem_dgrad", g, w_packed, dx, B, Hs, Ws, Ho, Wo, Cout, int(c_real), stream_ptr())
+    return dx
+
+
+def _packed_grad(g, who):
+    g = _chk(g, BF16, "g")
+    if g.dim() == 3:
+        g = g[None]
+    if g.dim() != 4 or g.shape[-1] != 8:
+        raise _lib.PoseKernelError(f"{who}: g {tuple(g.shape)} is not a packed gradient (B, H, W, 8) or (H, W, 8)")
+    return g
+
+
+def saliency_reduce(g, c_real=3):
+    """Packed gradient (B,H,W,8) bf16 -> (B,H,W) fp32: max over the c_real real channels of |g| (pk_saliency_reduce; exact, one launch, no
+    synchronisation).  A NaN in a real channel gives NaN, as torch.max does."""
+    g = _packed_grad(g, "saliency_reduce")
+    if not 1 <= int(c_real) <= 8:
+        raise _lib.PoseKernelError(f"saliency_reduce: c_real={c_real} (1 to 8)")
+    B, H, W = (int(s) for s in g.shape[:3])
+    out = torch.empty(B, H, W, dtype=F32, device=g.device)
+    _call_if(B * H * W, "pk_saliency_reduce", g, out, B, H, W, int(c_real), stream_ptr())
+    return out
+
+
+def packed_grad_to_nchw(g, channels=3):
+    """Packed gradient (B,H,W,Cpad) bf16 -> (B,channels,H,W) fp32 (pk_nhwc_bf16_to_nchw_f32: exact, the backward of the input pack)."""
+    g = _chk(g, BF16, "g")
+    C = int(channels)
+    if g.dim() != 4 or g.shape[-1] % 8 or not 1 <= C <= g.shape[-1]:
+        raise _lib.PoseKernelError(f"packed_grad_to_nchw: g {tuple(g.shape)} is not (B, H, W, Cpad) with Cpad a multiple of 8 and {C} <= Cpad")
+    B, H, W, Cp = (int(s) for s in g.shape)
+    out = torch.empty(B, C, H, W, dtype=F32, device=g.device)
+    _call_if(B * H * W, "pk_nhwc_bf16_to_nchw_f32", g, out, B, C, H, W, Cp, stream_ptr())
+    return out
+
+
+def grad_cam(activation, gradient, c_used=None):
+    """Grad-CAM of every sample (pk_gradcam; two launches, no synchronisation).  activation and gradient (B,h,w,C) bf16 in the op layer's
+    layout; channels >= c_used (a padded twin's) are ignored.  Per sample, in float64: weights = mean of the gradient over the pixels;
+    raw = relu(sum_c weights[c] activation[..., c]); cam = (raw - min raw) / (max(raw - min raw) + 1e-8).
+    -> cam (B,h,w) fp32, weights (B,c_used) fp32, range (B,2) float64 = min and max of raw (to undo the normalisation).  A NaN anywhere in
+    a sample makes that sample's map NaN."""
+    A, G = _chk(activation, BF16, "activation"), _chk(gradient, BF16, "gradient")
+    if A.dim() != 4 or tuple(A.shape) != tuple(G.shape) or A.shape[-1] % 8:
+        raise _lib.PoseKernelError(f"grad_cam: activation {tuple(A.shape)} and gradient {tuple(G.shape)} must both be (B, h, w, C), C a multiple of 8")
+    B, h, w, C = (int(s) for s in A.shape)
+    c_used = C if c_used is None else int(c_used)
+    if not 1 <= c_used <= C:
+        raise _lib.PoseKernelError(f"grad_cam: c_used={c_used} (1 to C={C})")
+    cam = torch.empty(B, h, w, dtype=F32, device=A.device)
+    weights = torch.empty(B, c_used, dtype=F32, device=A.device)
+    rng = torch.empty(B, 2, dtype=F64, device=A.device)
+    if B * h * w:
+        n = _lib.lib.pk_gradcam_ws_floats(B, h, w, c_used)
+        if n <= 0:
+            raise _lib.PoseKernelError(f"pk_gradcam_ws_floats failed (code {n}): {_lib.lib.pk_last_error_string().decode()}")
+        ws = torch.empty(n // 2, dtype=F64, device=A.device)
+        call("pk_gradcam", A, G, ws, cam, weights, rng, B, h, w, C, c_used, stream_ptr())
+    return cam, weights, rng
+
+
 # ------------------------------------------------------------------------------------------------ overlays
 U8 = torch.uint8
 

@@ -375,12 +375,35 @@ def to_features(x_nchw_f32, cpad=8):
     """(B,Cin,H,W) fp32 NCHW -> (B,H,W,cpad) bf16 NHWC, channels >= Cin zero (16-byte pixels for the stem conv).
     A bf16 (B,H,W,cpad) tensor is taken as already packed (datasets.transforms.DeviceCropper writes the stem's layout directly)."""
     if x_nchw_f32.dtype == BF16 and x_nchw_f32.dim() == 4 and x_nchw_f32.shape[-1] == cpad:
-        return x_nchw_f32.contiguous()
+        return x_nchw_f32.contiguous()               # (one that requires grad passes through as it is: the stem hands it its gradient)
     x = x_nchw_f32.float().contiguous()
+    if x.requires_grad and torch.is_grad_enabled():
+        return _PackInput.apply(x, cpad)             # input attribution (utils/sensitivity.py): the same launch, plus a backward
+    return _pack_input(x, cpad)
+
+
+def _pack_input(x, cpad):
     B, Cin, H, W = x.shape
     y = _e((B, H, W, max(cpad, _up8(Cin))), BF16, x.device)
     call("pk_nchw_f32_to_nhwc_bf16", x, None, y, B, Cin, H, W, y.shape[-1], stream_ptr())
     return y
+
+
+class _PackInput(torch.autograd.Function):
+    """The input pack with its backward: the packed bf16 gradient widened into (B,Cin,H,W) fp32 planes (exact; pad channels dropped)."""
+
+    @staticmethod
+    def forward(ctx, x, cpad):
+        ctx.shape = tuple(x.shape)
+        return _pack_input(x, cpad)
+
+    @staticmethod
+    def backward(ctx, g):
+        B, Cin, H, W = ctx.shape
+        g = g.contiguous()
+        dx = _e(ctx.shape, F32, g.device)
+        call("pk_nhwc_bf16_to_nchw_f32", g, dx, B, Cin, H, W, g.shape[-1], stream_ptr())
+        return dx, None
 
 
 def _conv_geometry(x, ksize, stride):
@@ -407,6 +430,18 @@ def _conv_dgrad(g, wd, Cin, ksize, stride, in_hw, addend=None):
     Hs, Ws = in_hw
     dx = _e((B, Hs, Ws, Cin), BF16, g.device)
     call("pk_conv2d_nhwc", g, wd, dx, None, None, B, Ho, Wo, Cout, Cin, ksize, 1, 1 if stride == 2 else 0, Hs, Ws, 0, 0, addend, stream_ptr())
+    return dx
+
+
+def _stem_dgrad(g, wf, c_real, ksize, stride, in_hw, recompute=False, addend=None):
+    """g (B,Ho,Wo,Cout) -> dx (B,Hs,Ws,8) of the stem conv with its FORWARD pack `wf` [Cout][9][8] (pk_stem_dgrad); channels >= c_real 0."""
+    if ksize != 3 or stride != 2 or recompute or addend is not None:
+        raise _lib.PoseKernelError(f"data gradient of a stem conv (fewer real input channels than its 8-channel pixels) with kernel {ksize}, "
+                                   f"stride {stride}: only the 3x3, stride-2, pad-1 stem outside a residual block is supported (pk_stem_dgrad)")
+    B, Ho, Wo, Cout = g.shape
+    Hs, Ws = in_hw
+    dx = _e((B, Hs, Ws, 8), BF16, g.device)
+    call("pk_stem_dgrad", g, wf, dx, B, Hs, Ws, Ho, Wo, Cout, c_real, stream_ptr())
     return dx
 
 
@@ -577,7 +612,8 @@ class _ConvBnAct(torch.autograd.Function):
             # ReLU mask as one bit per element (a byte per 16-byte chunk): BatchNorm backward reads it instead of y (1/16 of the bytes)
             mask = _e((M * Cout // 8,), torch.uint8, dev) if (relu and not infer) else None
             y, mean, rstd = _bn_forward(raw, part, gamma, beta, bn, res, relu, training, mask)
-            ctx.save_for_backward(x, raw, y if mask is None else mask, mean, rstd, gamma, wd)
+            # (the stem keeps its FORWARD pack: its data gradient is pk_stem_dgrad, and its data-gradient pack has only the real input rows)
+            ctx.save_for_backward(x, raw, y if mask is None else mask, mean, rstd, gamma, wf if Cin != Cin_real else wd)
         ctx.has_mask = mask is not None
         ctx.meta = (stride, relu, training, residual is not None, Cin_real, ksize, (B, Hs, Ws, Ho, Wo), Cout)
         return y
@@ -601,14 +637,17 @@ class _ConvBnAct(torch.autograd.Function):
                 raise _lib.PoseKernelError("residual block backward out of order: the skip gradient has not been produced yet")
         if ctx.skip_out is not None:
             ctx.skip_out.g, dres = dres, None                # handed to the block's first conv instead of to autograd
-        dx = _conv_dgrad(draw, wd, Cin, ksize, stride, (Hs, Ws), addend) if (ctx.needs_input_grad[0] or addend is not None) else None
         if Cin != Cin_real:                # stem: 3 real input channels inside 8-channel pixels
+            # its data gradient (input attribution only: in training the packed input never requires grad) is NOT the implicit GEMM with
+            # Cin = 8: the data-gradient pack holds the Cin_real real rows only, a launch over 8 would read the next weight's bytes
+            dx = _stem_dgrad(draw, wd, Cin_real, ksize, stride, (Hs, Ws), ctx.recompute, addend) if ctx.needs_input_grad[0] else None
             dw = _wgrad(x, draw, Cout, Cin, ksize, stride, (B, Hs, Ws, Ho, Wo))[:, :Cin_real].contiguous()
             dst = grad_sink_of(w_p)
             if dst is not None:
                 dst.copy_(dw)
                 dw = None
         else:
+            dx = _conv_dgrad(draw, wd, Cin, ksize, stride, (Hs, Ws), addend) if (ctx.needs_input_grad[0] or addend is not None) else None
             w = _Dest(w_p)
             _wgrad(x, draw, Cout, Cin, ksize, stride, (B, Hs, Ws, Ho, Wo), out=w.t, deferred=_deferrable(w))
             dw = w.grad()

@@ -7,7 +7,7 @@ from .activations import ActivationAnalyzer, ActivationCollector, activation_rep
 from . import postprocess
 from .postprocess import oks_nms, soft_oks_nms
 from . import sensitivity
-from .sensitivity import SensitivityAnalyzer, occlusion_sensitivity_maps
+from .sensitivity import GradCAMVisualizer, GradientCollector, SensitivityAnalyzer, attribution_maps, occlusion_sensitivity_maps
 from . import tensor_stats
 from .tensor_stats import gradient_flow, gradient_statistics, tensor_statistics, weight_statistics
 from . import uncertainty
@@ -22,4 +22,5 @@ __all__ = ['AverageMeter', 'COCOEvaluator', 'MetricLogger', 'postprocess', 'visu
            'movement_heatmap', 'movement_report', 'movement_spectrum', 'oks_nms', 'soft_oks_nms', 'tensor_stats', 'tensor_statistics',
            'gradient_statistics', 'gradient_flow', 'weight_statistics', 'KeypointErrorAnalyzer',
            'keypoint_error_report', 'sensitivity', 'SensitivityAnalyzer', 'occlusion_sensitivity_maps', 'activations',
-           'ActivationAnalyzer', 'ActivationCollector', 'activation_report', 'uncertainty', 'UncertaintyAnalyzer', 'mc_uncertainty']
+           'ActivationAnalyzer', 'ActivationCollector', 'activation_report', 'uncertainty', 'UncertaintyAnalyzer', 'mc_uncertainty',
+           'attribution_maps', 'GradCAMVisualizer', 'GradientCollector']

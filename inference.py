@@ -21,6 +21,9 @@ copies on the device gives the map of every joint (utils/sensitivity.py), and th
 `uncertainty` / `--uncertainty S` answer which joints of a person to distrust: S stochastic-depth members of the model in one batched pass
 (utils/uncertainty.py) give per joint the spread of the predicted position as a 1-sigma ellipse in image pixels, the agreement of the
 members and the spread of the peak, and the std maps are drawn where the crop lies.
+`attribution` / `--saliency_map JOINT` / `--grad_cam JOINT` answer what in the crop made the network put a joint there, by gradients: the
+input saliency and the Grad-CAM of every joint from one batched forward and one batched backward (utils/sensitivity.py), drawn where the
+crop lies.
 """
 import argparse
 import os
@@ -40,7 +43,7 @@ from infantposeestimation_gaussianbias_amd.datasets.transforms import DeviceCrop
 from infantposeestimation_gaussianbias_amd.models import build_model  # noqa: E402
 from infantposeestimation_gaussianbias_amd.utils.metrics import movement_heatmap, movement_report  # noqa: E402
 from infantposeestimation_gaussianbias_amd.utils.postprocess import heatmap_to_image_coords, temporal_smoothing  # noqa: E402
-from infantposeestimation_gaussianbias_amd.utils.sensitivity import occlusion_sensitivity_maps  # noqa: E402
+from infantposeestimation_gaussianbias_amd.utils.sensitivity import attribution_maps, occlusion_sensitivity_maps  # noqa: E402
 from infantposeestimation_gaussianbias_amd.utils.uncertainty import mc_uncertainty  # noqa: E402
 from infantposeestimation_gaussianbias_amd.utils.visualization import (COCO_SKELETON, crop_heatmap_matrices, draw_heatmaps, draw_person_heatmaps,  # noqa: E402
                                                                        draw_poses, draw_skeleton, write_image)
@@ -211,6 +214,19 @@ class PoseInference:
         out['center'], out['scale'] = center, scale
         return out
 
+    def attribution(self, img: np.ndarray, bbox: Optional[np.ndarray] = None, joints=None, **kw):
+        """What in the crop made the network put a joint there, by gradients: input saliency and Grad-CAM
+        (utils.sensitivity.attribution_maps; `kw`: target_layers, batch_size) on the crop `predict` takes for this image and box, un-flipped.
+        `joints`: None = all, one index or a list of them.  -> the dict of attribution_maps (saliency (J,H,W) over the crop's pixels, grad,
+        cams {layer: (J,h,w)}, cam_weights, cam_range, base, layers) plus `center` and `scale` of the crop, with which
+        `crop_heatmap_matrices(center, scale, (w, h))` places a map of that size in the image."""
+        x, center, scale = self.preprocess(img, bbox)
+        if joints is not None:
+            joints = [int(j) for j in np.atleast_1d(np.asarray(joints, np.int64))]
+        out = attribution_maps(self.model, x, joints=joints, **kw)
+        out['center'], out['scale'] = center, scale
+        return out
+
     def uncertainty(self, img: np.ndarray, bbox: Optional[np.ndarray] = None, samples: int = 30, rate: Optional[float] = None, seed: int = 0,
                     **kw):
         """Which joints to distrust: `samples` stochastic-depth members (utils.uncertainty.mc_uncertainty; `kw`: batch_size, radius,
@@ -356,6 +372,31 @@ def main_occlusion(args, pose, img, bbox):
     return res
 
 
+def main_attribution(args, pose, img, bbox):
+    """--saliency_map JOINT / --grad_cam JOINT: that joint's gradient map drawn where the crop lies; prints the pixel / cell of its maximum."""
+    cam = args.grad_cam is not None
+    k = int(args.grad_cam if cam else args.saliency_map)
+    flag = '--grad_cam' if cam else '--saliency_map'
+    if not 0 <= k < pose.model.num_keypoints:
+        raise SystemExit(f"{flag}: joint {k} outside 0 .. {pose.model.num_keypoints - 1}")
+    res = pose.attribution(img, bbox, joints=[k], target_layers=args.grad_cam_layer if cam else ())
+    if cam:
+        layer = res['layers'][0]
+        heat = res['cams'][layer][0]
+    else:
+        heat = res['saliency'][0]
+    h, w = int(heat.shape[0]), int(heat.shape[1])
+    top = int(torch.argmax(heat.reshape(-1)))                      # the one read-back, after everything ran
+    if cam:
+        print(f'Grad-CAM of joint {k} at layer {layer}: {h} x {w} cells, maximum at cell (x {top % w}, y {top // w})')
+    else:
+        print(f'Input saliency of joint {k}: {h} x {w} crop pixels, maximum {float(heat.reshape(-1)[top]):.6g} at pixel (x {top % w}, y {top // w})')
+    mats = crop_heatmap_matrices(res['center'], res['scale'], (w, h))
+    write_image(draw_person_heatmaps(img, heat[None, None], matrices=mats), args.output)
+    print(f'Result saved to: {args.output}')
+    return res
+
+
 def main_uncertainty(args, pose, img, bbox):
     """--uncertainty S: S stochastic-depth members on the person's crop; one line per joint, the same as JSON with --report, the std maps
     drawn where the crop lies with --output."""
@@ -401,6 +442,8 @@ def main(args):
         return main_occlusion(args, pose, img, bboxes[0])
     if getattr(args, "uncertainty", None) is not None:
         return main_uncertainty(args, pose, img, bboxes[0])
+    if getattr(args, "saliency_map", None) is not None or getattr(args, "grad_cam", None) is not None:
+        return main_attribution(args, pose, img, bboxes[0])
     whole = len(bboxes) == 1 and np.array_equal(np.asarray(bboxes[0], np.float64), [0, 0, img.shape[1], img.shape[0]])
     want_hm = bool(args.output and args.draw_heatmaps)
     t0 = time.time()
@@ -422,7 +465,8 @@ def main(args):
 
 
 class _Parser(argparse.ArgumentParser):
-    """--uncertainty excludes --occlusion_map and --sequence: refused while parsing, like any other bad combination of switches."""
+    """--uncertainty excludes --occlusion_map and --sequence, and --saliency_map and --grad_cam exclude each other and all three: refused
+    while parsing, like any other bad combination of switches."""
 
     def parse_args(self, args=None, namespace=None):
         ns = super().parse_args(args, namespace)
@@ -431,6 +475,17 @@ class _Parser(argparse.ArgumentParser):
                 self.error("--uncertainty takes the number of members, at least 1")
             if ns.occlusion_map is not None or ns.sequence:
                 self.error("--uncertainty cannot be combined with --occlusion_map or --sequence")
+        for flag, value in (("--saliency_map", ns.saliency_map), ("--grad_cam", ns.grad_cam)):
+            if value is None:
+                continue
+            if ns.saliency_map is not None and ns.grad_cam is not None:
+                self.error("--saliency_map and --grad_cam cannot be combined: one map per picture")
+            if ns.occlusion_map is not None or ns.uncertainty is not None or ns.sequence:
+                self.error(f"{flag} cannot be combined with --occlusion_map, --uncertainty or --sequence")
+            if not ns.output:
+                self.error(f"{flag} draws a picture and needs --output")
+        if ns.grad_cam_layer is not None and ns.grad_cam is None:
+            self.error("--grad_cam_layer names the layer of --grad_cam")
         return ns
 
 
@@ -490,6 +545,17 @@ def build_parser():
                         'with the ensemble peak and the mean and std of the peak; --report writes the same as JSON, --output draws the std '
                         'maps where the crop lies.  The spread is that of the model (epistemic), quantised to heat pixels; not with '
                         '--occlusion_map or --sequence')
+    p.add_argument('--saliency_map', type=int, default=None, metavar='JOINT',
+                   help='input saliency of this joint instead of the pose overlay (needs --output): |d (sum of the joint\'s heat map) / d crop|, '
+                        'maximised over the colour channels, from one backward pass on the device, drawn where the crop lies in the image; '
+                        'prints the crop pixel of the maximum.  Not with --grad_cam, --occlusion_map, --uncertainty or --sequence')
+    p.add_argument('--grad_cam', type=int, default=None, metavar='JOINT',
+                   help='Grad-CAM of this joint instead of the pose overlay (needs --output): the activation of a layer weighted by the mean '
+                        'gradient of the joint\'s heat map, normalised to [0, 1], drawn where the crop lies; prints the cell of the maximum.  '
+                        'Not with --saliency_map, --occlusion_map, --uncertainty or --sequence')
+    p.add_argument('--grad_cam_layer', type=str, default=None, metavar='NAME',
+                   help='--grad_cam: the tapped layer (a qualified module name as the activation report lists them; default: the '
+                        'backbone\'s output, output 0 of the last exchange unit)')
     p.add_argument('--uncertainty_rate', type=float, default=None, metavar='R',
                    help='--uncertainty: the stochastic-depth rate of the members (default: the model\'s drop_path_rate)')
     p.add_argument('--uncertainty_seed', type=int, default=0, metavar='N', help='--uncertainty: seed of the device generator that draws the members')
