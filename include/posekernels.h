@@ -532,6 +532,58 @@ int pk_gradcam_ws_floats(int B, int h, int w, int c_used);
 int pk_gradcam(const void* A, const void* G /* (B,h,w,C) bf16 */, double* ws, float* cam /* (B,h,w) */, float* weights /* (B,c_used) */,
                double* range /* (B,2): min, max of raw */, int B, int h, int w, int C, int c_used, void* stream);
 
+/* ---- feature sheets and heat-map quality (this project's own specification, DESIGN.md "Feature sheets and heat-map quality": the sheet of
+ * colour-mapped channel tiles and the target / prediction / difference panels of the reference's FeatureVisualizer,
+ * analysis/nn_quantitative_viz.py:255-324, and a record of quality numbers per pair of maps).  No atomics, no last-arriver; every
+ * floating-point sum in a fixed order and the colour index a fixed sequence of fp32 operations without FMA, each rounded once (the
+ * division correctly rounded): the same input gives the same bits on any stream.
+ * pk_gather_planes: x (B,H,W,C) bf16 NHWC, C a multiple of 8, 16-byte aligned; channels (n) int32 on the device, 1 <= n <= PK_PANEL_MAX_TILES;
+ *   out (n,H,W) fp32, every element written.  Plane i = channel channels[i] of sample b, widened (exact).  A channel outside [0, c_used)
+ *   gives a plane of quiet NaN (0x7fc00000) and is never turned into an address.  One thread per pixel and run of 8 list entries: it
+ *   loads the pixel's 16-byte channel group once per run of entries that fall into the same group and keeps the wanted lanes.
+ *   Refused before the launch, in this order: a null pointer; B, H, W or C < 1 or H W > PK_PANEL_MAX_PLANE; C not a multiple of 8; b outside
+ *   0..B-1; n outside 1..PK_PANEL_MAX_TILES; c_used outside 1..C; x not 16-byte or channels / out not 4-byte aligned.
+ * pk_plane_sheet_size: host only.  rows = ceil(T / cols); *SH = pad + rows (h zoom + pad), *SW = pad + cols (w zoom + pad).  Refused, in
+ *   this order: a null pointer; T outside 1..PK_PANEL_MAX_TILES; h or w < 1 or h w > PK_PANEL_MAX_PLANE; cols outside 1..PK_PANEL_MAX_TILES; zoom
+ *   outside 1..PK_PANEL_MAX_ZOOM; pad outside 0..PK_PANEL_MAX_PAD; SH or SW above PK_PANEL_MAX_SIDE (the drawing unit's limit).
+ * pk_plane_sheet: a (Na,h,w) fp32; b (Nb,h,w) fp32 or NULL with Nb = 0; tiles (T,3) int32 on the device = {ia, ib, ramp}; luts (L,256,3)
+ *   uint8; ranges (T,2) fp32 and sheet (SH,SW,3) uint8, every element and every byte written (the caller hands over uninitialised memory).
+ *   Element e = (i, j) of tile t has v = a[ia][e] when ib < 0, else fabsf(a[ia][e] - b[ib][e]), in fp32.  lo, hi = minimum and maximum of
+ *   the tile's finite v (+inf, -inf without one) = ranges[t].  Colour index of a finite v, every operation in fp32 in this order:
+ *   u = (v - lo) / ((hi - lo) + 1e-8f), f = floorf(255.0f u), idx = 255 if f >= 255, (int)f if f > 0, else 0 (so a NaN u, inf / inf when
+ *   v - lo overflows, gives 0); a non-finite v has idx 0.  Tile t sits at row t / cols, column t % cols, with origin
+ *   y0 = pad + (t / cols)(h zoom + pad), x0 = pad + (t % cols)(w zoom + pad); sheet pixel (y0 + i, x0 + j), i < h zoom, j < w zoom, takes the
+ *   three bytes luts[ramp][idx(v[i / zoom][j / zoom])].  Every other pixel (gutters, the empty cells of the last row) takes the three
+ *   background bytes.  A tile with ia outside 0..Na-1, ib >= Nb or ramp outside 0..L-1 is painted as background and has the range NaN, NaN.
+ *   Two launches: one workgroup per tile for the ranges (minimum and maximum are exact: any order), then one thread per four pixels of
+ *   the sheet taken as one flat array, three whole 4-byte stores each; no workspace.  Refused before the launch, in this order: a null a,
+ *   tiles, luts, ranges or sheet; what pk_plane_sheet_size refuses; Na < 1, Nb < 0, Nb > 0 with b NULL, L < 1; a background value outside
+ *   0..255; a, b, tiles, ranges or the sheet not 4-byte aligned.
+ * pk_heatmap_quality: pred, gt (M,h,w) fp32; records (M,PK_QUALITY_COLS) float64, every element written.  One 256-thread workgroup per
+ *   map (workgroups stride over the maps when M exceeds the grid).  An element takes part iff p and g are both finite; the others are
+ *   counted in column 15 and nowhere else; n = the elements that take part.  All arithmetic on the values widened to float64, without FMA.
+ *   Every sum: thread r adds its elements r, r + 256, ... in ascending order to 0.0; then the xor butterfly 32, 16, ..., 1 inside each
+ *   wave, then wave 0 + wave 1 + wave 2 + wave 3 (pk_heatmap_summary's order).  Columns: 0, 1 sum p, sum g; 2 sum (p - g)^2; 3 max |p - g|
+ *   (0 when n = 0); 4, 5, 6 max p, its x, its y by pk_heatmap_summary's rule (replaced iff v > best in fp32, the smallest flat index among
+ *   equal maxima, -0 = +0; -inf at (0, 0) without a value above -inf); 7, 8, 9 the same for g; 10, 11, 12 sum (p - mp)(g - mg),
+ *   sum (p - mp)^2, sum (g - mg)^2 with mp = column 0 / n, mg = column 1 / n, taken in a second pass over the map; 13, 14 the number of
+ *   elements with p >= 0.5f max p AND g >= 0.5f max g, and with either (products and comparisons in fp32), both 0 unless both peaks are
+ *   > 0; 15 the elements left out.  Refused before the launch, in this order: a null pointer; M, h or w < 1 or h w > PK_PANEL_MAX_PLANE;
+ *   pred or gt not 4-byte or records not 8-byte aligned.                                                                              */
+#define PK_PANEL_MAX_TILES 4096
+#define PK_PANEL_MAX_SIDE 8192
+#define PK_PANEL_MAX_PLANE 16777216
+#define PK_PANEL_MAX_ZOOM 64
+#define PK_PANEL_MAX_PAD 64
+#define PK_QUALITY_COLS 16
+int pk_gather_planes(const void* x /* (B,H,W,C) bf16 */, int B, int H, int W, int C, int b, const int32_t* channels /* (n) */, int n, int c_used,
+                     float* out /* (n,H,W) */, void* stream);
+int pk_plane_sheet_size(int T, int h, int w, int cols, int zoom, int pad, int* SH, int* SW);
+int pk_plane_sheet(const float* a /* (Na,h,w) */, int Na, const float* b /* (Nb,h,w) or NULL */, int Nb, const int32_t* tiles /* (T,3) */, int T,
+                   const void* luts_u8 /* (L,256,3) */, int L, float* ranges /* (T,2) */, void* sheet_u8 /* (SH,SW,3) */, int h, int w, int cols,
+                   int zoom, int pad, int bg0, int bg1, int bg2, void* stream);
+int pk_heatmap_quality(const float* pred, const float* gt /* (M,h,w) */, double* records /* (M,16) */, int64_t M, int h, int w, void* stream);
+
 
 /* ======================= network contractions (bf16 MFMA, fp32 accumulate; NHWC activations) =======================
  * These replace the groups of ATen calls inside the reference's modules; weights are bf16 "compute copies" packed by

@@ -2,6 +2,7 @@
 and `torch.autograd.Function`s for the differentiable ops.  Every function here launches HIP kernels from
 libposekernels.so on the current torch stream; none has a PyTorch fallback.
 """
+import ctypes
 import math
 
 import numpy as np
@@ -1418,3 +1419,91 @@ def activation_bin_edges():
     edges[np.isnan(edges) & (np.arange(ACT_HIST_BINS + 1) < ACT_HIST_BINS // 2)] = -np.inf
     edges[np.isnan(edges)] = np.inf
     return edges
+
+
+# ------------------------------------------------------------------------------------------------ feature sheets, heat-map quality
+# pk_gather_planes / pk_plane_sheet / pk_heatmap_quality: channel planes of a tapped map, a finished uint8 sheet of colour-mapped tiles and
+# one float64 record per pair of maps, on the current stream; nothing is read back.
+PANEL_MAX_TILES = _lib.CONSTANTS["PK_PANEL_MAX_TILES"]
+PANEL_MAX_SIDE = _lib.CONSTANTS["PK_PANEL_MAX_SIDE"]
+QUALITY_COLS = _lib.CONSTANTS["PK_QUALITY_COLS"]
+
+
+def gather_planes(x, channels, sample=0, c_used=None):
+    """Channels of one sample of an NHWC map as planes (pk_gather_planes; one launch, no synchronisation).  x (B,H,W,C) bf16, C a multiple
+    of 8; channels (n,) int32 on the device -> (n,H,W) fp32, plane i = x[sample, :, :, channels[i]] widened.  A channel outside
+    [0, c_used) gives a plane of NaN (the kernel reads nothing for it); callers check their list on the host before they upload it."""
+    x, channels = _chk(x, BF16, "x"), _chk(channels, I32, "channels")
+    if x.dim() != 4 or x.shape[-1] % 8 or x.numel() == 0:
+        raise _lib.PoseKernelError(f"gather_planes: x {tuple(x.shape)} is not a non-empty (B, H, W, C) map with C a multiple of 8")
+    B, H, W, C = (int(s) for s in x.shape)
+    c_used = C if c_used is None else int(c_used)
+    n = int(channels.numel())
+    if channels.dim() != 1 or not 1 <= n <= PANEL_MAX_TILES:
+        raise _lib.PoseKernelError(f"gather_planes: channels {tuple(channels.shape)} is not a list of 1 to {PANEL_MAX_TILES} entries")
+    if not 0 <= int(sample) < B or not 1 <= c_used <= C:
+        raise _lib.PoseKernelError(f"gather_planes: sample={sample} of {B}, c_used={c_used} of {C}")
+    out = torch.empty(n, H, W, dtype=F32, device=x.device)
+    call("pk_gather_planes", x, B, H, W, C, int(sample), channels, n, c_used, out, stream_ptr())
+    return out
+
+
+def plane_sheet_size(T, h, w, cols, zoom, pad):
+    """(SH, SW) of a sheet of T tiles of h x w elements (pk_plane_sheet_size: host only); raises for what the library refuses."""
+    SH, SW = ctypes.c_int(0), ctypes.c_int(0)
+    rc = _lib.lib.pk_plane_sheet_size(int(T), int(h), int(w), int(cols), int(zoom), int(pad), ctypes.addressof(SH), ctypes.addressof(SW))
+    if rc != 0:
+        raise _lib.PoseKernelError(f"pk_plane_sheet_size failed (code {rc}): {_lib.lib.pk_last_error_string().decode()}")
+    return SH.value, SW.value
+
+
+def plane_sheet(a, tiles, luts, b=None, cols=4, zoom=1, pad=2, background=(255, 255, 255)):
+    """T colour-mapped tiles on one sheet (pk_plane_sheet; two launches, no synchronisation).  a (Na,h,w) fp32; b (Nb,h,w) fp32 or None;
+    tiles (T,3) int32 on the device = {ia, ib or -1, ramp}: the tile shows a[ia], or |a[ia] - b[ib]|, scaled to its own range of finite
+    values and looked up in luts[ramp]; luts (L,256,3) or (256,3) uint8 in the sheet's channel order.  Tile t sits at row t // cols,
+    column t % cols, every element zoom x zoom pixels, pad pixels of `background` around each tile.  A tile that names a plane or a ramp
+    that does not exist is background.  -> (sheet (SH,SW,3) uint8, ranges (T,2) fp32: lo, hi of each tile; +inf, -inf without a finite
+    value, NaN for a refused tile)."""
+    a, tiles, luts = _chk(a, name="a"), _chk(tiles, I32, "tiles"), _chk(luts, U8, "luts")
+    if luts.dim() == 2:
+        luts = luts[None]
+    if a.dim() != 3 or a.numel() == 0 or tiles.dim() != 2 or tiles.shape[1] != 3 or luts.dim() != 3 or tuple(luts.shape[1:]) != (256, 3) \
+            or luts.shape[0] < 1:
+        raise _lib.PoseKernelError(f"plane_sheet: a (Na,h,w), tiles (T,3) and luts (L,256,3), got {tuple(a.shape)}, {tuple(tiles.shape)}, "
+                                   f"{tuple(luts.shape)}")
+    Na, h, w = (int(s) for s in a.shape)
+    Nb = 0
+    if b is not None:
+        b = _chk(b, name="b")
+        if b.dim() != 3 or tuple(b.shape[1:]) != (h, w) or b.shape[0] < 1:
+            raise _lib.PoseKernelError(f"plane_sheet: b {tuple(b.shape)} is not (Nb, {h}, {w})")
+        Nb = int(b.shape[0])
+    T, L = int(tiles.shape[0]), int(luts.shape[0])
+    SH, SW = plane_sheet_size(T, h, w, cols, zoom, pad)
+    bg = [int(c) for c in background]
+    if len(bg) != 3 or not all(0 <= c <= 255 for c in bg):
+        raise _lib.PoseKernelError(f"plane_sheet: background {background} is not three bytes")
+    sheet = torch.empty(SH, SW, 3, dtype=U8, device=a.device)
+    ranges = torch.empty(T, 2, dtype=F32, device=a.device)
+    call("pk_plane_sheet", a, Na, b, Nb, tiles, T, luts, L, ranges, sheet, h, w, int(cols), int(zoom), int(pad), bg[0], bg[1], bg[2], stream_ptr())
+    return sheet, ranges
+
+
+def heatmap_quality(pred, gt, out=None):
+    """(..., h, w) predicted and target maps -> (..., 16) float64 records (pk_heatmap_quality; one launch, no synchronisation).  Columns:
+    0, 1 sum p, sum g; 2 sum (p - g)^2; 3 max |p - g|; 4-6 max p, its x, its y (the first of equal maxima); 7-9 the same for g; 10-12
+    sum (p - mean p)(g - mean g), sum (p - mean p)^2, sum (g - mean g)^2; 13, 14 the elements above half of both peaks, and of either;
+    15 the elements left out because p or g is not finite.  Every sum in float64 in a fixed order.  `out`: a contiguous float64 device
+    tensor of that shape to write into (a slice of a larger table)."""
+    p, g = _chk(pred, name="pred"), _chk(gt, name="gt")
+    if p.dim() < 2 or tuple(p.shape) != tuple(g.shape):
+        raise _lib.PoseKernelError(f"heatmap_quality: pred {tuple(p.shape)} and gt {tuple(g.shape)} must both be (..., h, w)")
+    lead, h, w = tuple(p.shape[:-2]), int(p.shape[-2]), int(p.shape[-1])
+    M = int(np.prod(lead, dtype=np.int64)) if lead else 1
+    if out is None:
+        out = torch.empty(*lead, QUALITY_COLS, dtype=F64, device=p.device)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == F64 and out.is_contiguous()
+              and tuple(out.shape) == lead + (QUALITY_COLS,)):
+        raise _lib.PoseKernelError(f"heatmap_quality: out must be a contiguous float64 device tensor {lead + (QUALITY_COLS,)}")
+    _call_if(M * h * w, "pk_heatmap_quality", p, g, out, M, h, w, stream_ptr())
+    return out

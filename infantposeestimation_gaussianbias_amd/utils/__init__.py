@@ -4,6 +4,9 @@ from .metrics import (AverageMeter, COCOEvaluator, KeypointErrorAnalyzer, Metric
                       movement_spectrum)
 from . import activations
 from .activations import ActivationAnalyzer, ActivationCollector, activation_report
+from . import feature_maps
+from .feature_maps import (FeatureCollector, FeatureVisualizer, HeatmapQualityAccumulator, feature_sheet, heatmap_quality,
+                           heatmap_quality_sheet)
 from . import postprocess
 from .postprocess import oks_nms, soft_oks_nms
 from . import sensitivity
@@ -23,4 +26,5 @@ __all__ = ['AverageMeter', 'COCOEvaluator', 'MetricLogger', 'postprocess', 'visu
            'gradient_statistics', 'gradient_flow', 'weight_statistics', 'KeypointErrorAnalyzer',
            'keypoint_error_report', 'sensitivity', 'SensitivityAnalyzer', 'occlusion_sensitivity_maps', 'activations',
            'ActivationAnalyzer', 'ActivationCollector', 'activation_report', 'uncertainty', 'UncertaintyAnalyzer', 'mc_uncertainty',
-           'attribution_maps', 'GradCAMVisualizer', 'GradientCollector']
+           'attribution_maps', 'GradCAMVisualizer', 'GradientCollector', 'feature_maps', 'FeatureCollector', 'FeatureVisualizer',
+           'HeatmapQualityAccumulator', 'feature_sheet', 'heatmap_quality', 'heatmap_quality_sheet']

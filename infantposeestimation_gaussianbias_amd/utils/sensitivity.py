@@ -21,8 +21,9 @@ from .activations import ActivationCollector
 __all__ = ['GradCAMVisualizer', 'GradientCollector', 'SensitivityAnalyzer', 'attribution_maps', 'occlusion_sensitivity_maps']
 
 
-def _packed_image(image, who="occlusion_sensitivity_maps", what="sweep"):
-    """(1,3,H,W) or (3,H,W) fp32 normalised, or the packed (1,H,W,8) / (H,W,8) bf16 -> (1,H,W,8) bf16, packed once."""
+def _packed_image(image, who="occlusion_sensitivity_maps", what="sweep", single=True):
+    """(1,3,H,W) or (3,H,W) fp32 normalised, or the packed (1,H,W,8) / (H,W,8) bf16 -> (1,H,W,8) bf16, packed once.  `single` False
+    (utils/feature_maps.py): a batch of either is taken as well."""
     if not (isinstance(image, torch.Tensor) and image.is_cuda):
         raise TypeError(f"{who}: image must be a device tensor (the {what} has no CPU implementation)")
     if image.dtype == torch.bfloat16 and image.shape[-1] == 8 and image.dim() in (3, 4):
@@ -31,7 +32,7 @@ def _packed_image(image, who="occlusion_sensitivity_maps", what="sweep"):
         image = image[None] if image.dim() == 3 else image
     else:
         raise ValueError(f"{who}: image {tuple(image.shape)} is neither (1,3,H,W) / (3,H,W) nor the packed (1,H,W,8) bf16")
-    if image.shape[0] != 1:
+    if single and image.shape[0] != 1:
         raise ValueError(f"{who}: one image at a time, got a batch of {image.shape[0]}")
     return nnops.to_features(image)
 

@@ -52,6 +52,31 @@ def heatmap_lut() -> np.ndarray:
     return np.stack([chan(1.0), chan(2.0), chan(3.0)], axis=1)
 
 
+_RAMP_ANCHORS = {
+    # RGB colours at evenly spaced t in [0, 1], joined by straight lines
+    'sequential': ((68, 1, 84), (59, 82, 139), (33, 145, 140), (94, 201, 98), (253, 231, 37)),
+    'diverging': ((59, 76, 192), (221, 221, 221), (180, 4, 38)),
+}
+
+
+def colour_ramp(name: str) -> np.ndarray:
+    """(256, 3) uint8 BGR colour ramp of the feature sheets, entry i at t = i / 255, interpolated in float64 and rounded with rint.
+    'hot': r = clip(t / 0.365079), g = clip((t - 0.365079) / 0.380953), b = clip((t - 0.746032) / 0.253968) (black, red, yellow, white);
+    'sequential': dark violet to yellow through (68,1,84), (59,82,139), (33,145,140), (94,201,98), (253,231,37) at t = 0, 1/4, 1/2, 3/4, 1;
+    'diverging': blue to red through (59,76,192), (221,221,221), (180,4,38) at t = 0, 1/2, 1; 'jet': `heatmap_lut()`."""
+    t = np.arange(256, dtype=np.float64) / 255.0
+    if name == 'jet':
+        return heatmap_lut()
+    if name == 'hot':
+        rgb = 255.0 * np.clip(np.stack([t / 0.365079, (t - 0.365079) / 0.380953, (t - 0.746032) / 0.253968], axis=1), 0.0, 1.0)
+    elif name in _RAMP_ANCHORS:
+        anchors = np.asarray(_RAMP_ANCHORS[name], np.float64)
+        rgb = np.stack([np.interp(t, np.linspace(0.0, 1.0, len(anchors)), anchors[:, c]) for c in range(3)], axis=1)
+    else:
+        raise ValueError(f"colour_ramp: no ramp named {name!r}; the ramps are 'hot', 'sequential', 'diverging', 'jet'")
+    return np.ascontiguousarray(np.rint(rgb).astype(np.uint8)[:, ::-1])
+
+
 _TABLES = {}
 
 

@@ -24,6 +24,8 @@ members and the spread of the peak, and the std maps are drawn where the crop li
 `attribution` / `--saliency_map JOINT` / `--grad_cam JOINT` answer what in the crop made the network put a joint there, by gradients: the
 input saliency and the Grad-CAM of every joint from one batched forward and one batched backward (utils/sensitivity.py), drawn where the
 crop lies.
+`feature_maps` / `--feature_maps LAYER` show what a layer computes for the person: the first channels of the tapped map (or a list of them)
+as one sheet of colour-mapped tiles, each scaled to its own range, painted on the device (utils/feature_maps.py).
 """
 import argparse
 import os
@@ -41,6 +43,7 @@ from infantposeestimation_gaussianbias_amd.configs.config import check_decode, c
 from infantposeestimation_gaussianbias_amd.engine import checkpoint_weights  # noqa: E402
 from infantposeestimation_gaussianbias_amd.datasets.transforms import DeviceCropper, get_affine_matrix, multiscale_matrices  # noqa: E402
 from infantposeestimation_gaussianbias_amd.models import build_model  # noqa: E402
+from infantposeestimation_gaussianbias_amd.utils.feature_maps import feature_sheet  # noqa: E402
 from infantposeestimation_gaussianbias_amd.utils.metrics import movement_heatmap, movement_report  # noqa: E402
 from infantposeestimation_gaussianbias_amd.utils.postprocess import heatmap_to_image_coords, temporal_smoothing  # noqa: E402
 from infantposeestimation_gaussianbias_amd.utils.sensitivity import attribution_maps, occlusion_sensitivity_maps  # noqa: E402
@@ -227,6 +230,13 @@ class PoseInference:
         out['center'], out['scale'] = center, scale
         return out
 
+    def feature_maps(self, img: np.ndarray, bbox: Optional[np.ndarray] = None, layer: Optional[str] = None, **kw):
+        """What a layer computes for this person: the sheet of its channels (utils.feature_maps.feature_sheet; `kw`: channels, cols, zoom,
+        pad, ramp) on the crop `predict` takes for this image and box, un-flipped.  -> (sheet (SH,SW,3) uint8 BGR and ranges (n,2) on the
+        device, the channel list)."""
+        x, _, _ = self.preprocess(img, bbox)
+        return feature_sheet(self.model, x, layer, **kw)
+
     def uncertainty(self, img: np.ndarray, bbox: Optional[np.ndarray] = None, samples: int = 30, rate: Optional[float] = None, seed: int = 0,
                     **kw):
         """Which joints to distrust: `samples` stochastic-depth members (utils.uncertainty.mc_uncertainty; `kw`: batch_size, radius,
@@ -397,6 +407,19 @@ def main_attribution(args, pose, img, bbox):
     return res
 
 
+def main_feature_maps(args, pose, img, bbox):
+    """--feature_maps LAYER: the sheet of that layer's channels for the person's crop; one line per channel with its range."""
+    chans = args.feature_channels
+    chans = 16 if not chans else (int(chans[0]) if len(chans) == 1 else [int(c) for c in chans])
+    sheet, ranges, shown = pose.feature_maps(img, bbox, args.feature_maps, channels=chans, zoom=args.feature_zoom)
+    print(f'Feature maps of {args.feature_maps}: {len(shown)} channels on a {int(sheet.shape[0])} x {int(sheet.shape[1])} sheet')
+    for c, (lo, hi) in zip(shown, ranges.cpu().tolist()):          # the one read-back, after everything ran
+        print(f'  channel {c:4d}: {lo:.6g} .. {hi:.6g}')
+    write_image(sheet, args.output)
+    print(f'Result saved to: {args.output}')
+    return sheet, ranges, shown
+
+
 def main_uncertainty(args, pose, img, bbox):
     """--uncertainty S: S stochastic-depth members on the person's crop; one line per joint, the same as JSON with --report, the std maps
     drawn where the crop lies with --output."""
@@ -442,6 +465,8 @@ def main(args):
         return main_occlusion(args, pose, img, bboxes[0])
     if getattr(args, "uncertainty", None) is not None:
         return main_uncertainty(args, pose, img, bboxes[0])
+    if getattr(args, "feature_maps", None) is not None:
+        return main_feature_maps(args, pose, img, bboxes[0])
     if getattr(args, "saliency_map", None) is not None or getattr(args, "grad_cam", None) is not None:
         return main_attribution(args, pose, img, bboxes[0])
     whole = len(bboxes) == 1 and np.array_equal(np.asarray(bboxes[0], np.float64), [0, 0, img.shape[1], img.shape[0]])
@@ -465,8 +490,8 @@ def main(args):
 
 
 class _Parser(argparse.ArgumentParser):
-    """--uncertainty excludes --occlusion_map and --sequence, and --saliency_map and --grad_cam exclude each other and all three: refused
-    while parsing, like any other bad combination of switches."""
+    """--uncertainty excludes --occlusion_map and --sequence, and --saliency_map and --grad_cam exclude each other and all three;
+    --feature_maps excludes all of them: refused while parsing, like any other bad combination of switches."""
 
     def parse_args(self, args=None, namespace=None):
         ns = super().parse_args(args, namespace)
@@ -484,6 +509,15 @@ class _Parser(argparse.ArgumentParser):
                 self.error(f"{flag} cannot be combined with --occlusion_map, --uncertainty or --sequence")
             if not ns.output:
                 self.error(f"{flag} draws a picture and needs --output")
+        if ns.feature_maps is not None:
+            if any(v is not None for v in (ns.occlusion_map, ns.uncertainty, ns.saliency_map, ns.grad_cam)) or ns.sequence:
+                self.error("--feature_maps cannot be combined with --occlusion_map, --uncertainty, --saliency_map, --grad_cam or --sequence")
+            if not ns.output:
+                self.error("--feature_maps draws a picture and needs --output")
+            if ns.feature_zoom is not None and not 1 <= ns.feature_zoom <= 64:
+                self.error("--feature_zoom takes 1 to 64 pixels per element")
+        elif ns.feature_channels is not None or ns.feature_zoom is not None:
+            self.error("--feature_channels and --feature_zoom belong to --feature_maps")
         if ns.grad_cam_layer is not None and ns.grad_cam is None:
             self.error("--grad_cam_layer names the layer of --grad_cam")
         return ns
@@ -556,6 +590,16 @@ def build_parser():
     p.add_argument('--grad_cam_layer', type=str, default=None, metavar='NAME',
                    help='--grad_cam: the tapped layer (a qualified module name as the activation report lists them; default: the '
                         'backbone\'s output, output 0 of the last exchange unit)')
+    p.add_argument('--feature_maps', type=str, default=None, metavar='LAYER',
+                   help='the feature maps of this tapped layer for the person in --bbox instead of the pose overlay (needs --output): its '
+                        'channels as one sheet of colour-mapped tiles, four per row, each scaled to its own range, painted on the device; '
+                        'prints every channel\'s range.  LAYER is a qualified module name as the activation report lists them; an unknown '
+                        'name lists them.  Not with --occlusion_map, --uncertainty, --saliency_map, --grad_cam or --sequence')
+    p.add_argument('--feature_channels', type=int, nargs='+', default=None, metavar='N',
+                   help='--feature_maps: one number = the first N channels (default 16, capped at the layer\'s channel count); several = '
+                        'exactly those channels')
+    p.add_argument('--feature_zoom', type=int, default=None, metavar='Z',
+                   help='--feature_maps: pixels per element, 1 to 64 (default: the largest that keeps the sheet within 2048 px per side)')
     p.add_argument('--uncertainty_rate', type=float, default=None, metavar='R',
                    help='--uncertainty: the stochastic-depth rate of the members (default: the model\'s drop_path_rate)')
     p.add_argument('--uncertainty_seed', type=int, default=0, metavar='N', help='--uncertainty: seed of the device generator that draws the members')

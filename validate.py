@@ -9,7 +9,9 @@ the quarter-pixel shift (the default) or the unbiased, distribution-aware step o
 averaged weights of a checkpoint written by `train.py --ema`; plus --error_report PATH / --error_px T for the localisation error
 analysis: per joint the quantiles of the error in image pixels, the calibration of the confidence and precision / recall of "within T
 pixels" over a confidence threshold, gathered on the device and written as JSON; plus --activation_report PATH / --activation_batches N for
-the activation statistics and dead channels of every tapped layer, likewise).
+the activation statistics and dead channels of every tapped layer, likewise; plus --heatmap_quality PATH / --heatmap_quality_sheet PNG for
+the quality of the predicted heat maps as maps against the loader's targets: per joint the mean peak distance, correlation and half-maximum
+overlap, gathered on the device and written as JSON, and the target / prediction / difference panels of the first sample as one image).
 
 Flip-test inference + decode run entirely on the GPU (`PoseEstimator.inference`: two forwards, one flip-merge kernel, one
 decode kernel); the heat-px -> image transform of validate.py:100-117 is one kernel (`heatmap_to_image_coords`) instead of a
@@ -37,7 +39,8 @@ from infantposeestimation_gaussianbias_amd.utils.postprocess import heatmap_to_i
 
 @torch.no_grad()
 def validate(model, loader, device, cfg, logger, flip_test=True, scales=None, pck_thresholds=None, evaluator=None, decode=None,
-             modulate_kernel=None, error_analysis=None, error_report=None):
+             modulate_kernel=None, error_analysis=None, error_report=None, heatmap_quality=None, heatmap_quality_report=None,
+             heatmap_quality_sheet=None):
     """train.py:231-325 == validate.py:39-140 of the reference: loss + decode + image-space transform + COCOEvaluator.update per batch,
     then AP.  Decode, flip merge, the heat-px -> image transform and the evaluator's record arrays are kernels (no B x K Python loops, one
     device->host copy per batch).  AP / AR come from COCOKeypointEval when the loader's dataset has an annotation file; otherwise AP is the
@@ -55,7 +58,12 @@ def validate(model, loader, device, cfg, logger, flip_test=True, scales=None, pc
     `error_analysis`: None (nothing added: no metric key, no launch), or a `KeypointErrorAnalyzer` to fill in image space with the
     predictions, ground truth and visibility that PCK gets and the per-joint scores that the evaluator gets, in pixels (no normaliser).
     After the last batch its report goes to the log (median and 95th percentile per joint when it holds those quantiles, pooled ECE and AP)
-    and, with `error_report` (a path), to that file as JSON.  Like PCK it raises on a loader of detector boxes.  The metrics are unchanged."""
+    and, with `error_report` (a path), to that file as JSON.  Like PCK it raises on a loader of detector boxes.  The metrics are unchanged.
+    `heatmap_quality`: None (nothing added: no launch), or a `HeatmapQualityAccumulator` to fill with the loss forward's `out["heatmaps"]`
+    against `batch["target"]`, weighted by `batch["target_weight"]`.  After the last batch its report goes to the log (one line per joint)
+    and, with `heatmap_quality_report` (a path), to that file as JSON; with `heatmap_quality_sheet` (a path) the panels of the first sample
+    are written as an image.  It raises when the model's heat maps and the loader's target differ in shape, and on a loader of detector
+    boxes, whose targets are placeholders.  The metrics are unchanged."""
     from infantposeestimation_gaussianbias_amd.utils import COCOEvaluator
     from infantposeestimation_gaussianbias_amd.utils import metrics as metrics_mod
     pck = metrics_mod.PCKAccumulator(cfg.data.num_keypoints, pck_thresholds) if pck_thresholds is not None else None
@@ -70,6 +78,7 @@ def validate(model, loader, device, cfg, logger, flip_test=True, scales=None, pc
     flip_pairs = cfg.data.flip_pairs if flip_test else None
     gts = []
     no_gt = False
+    first_maps = None
     for i, batch in enumerate(loader):
         imgs = batch["img"].to(device)
         if scales is None:
@@ -88,11 +97,16 @@ def validate(model, loader, device, cfg, logger, flip_test=True, scales=None, pc
                 raise RuntimeError("validate: PCK needs ground-truth keypoints; a loader of detector boxes (bbox_file) carries none")
             if error_analysis is not None:
                 raise RuntimeError("validate: the error analysis needs ground-truth keypoints; a loader of detector boxes (bbox_file) carries none")
+            if heatmap_quality is not None:
+                raise RuntimeError("validate: the heat-map quality needs ground-truth targets; a loader of detector boxes (bbox_file) carries "
+                                   "placeholders")
             no_gt, gt_kp = True, None
         else:
             gt_kp = batch["keypoints"].to(device) if batch.get("keypoints") is not None else None
             out = model(imgs, batch["target"].to(device), batch["target_weight"].to(device), gt_keypoints=gt_kp, input_size=cfg.data.input_size)
             loss_meter.update(float(out["loss"]), imgs.size(0))
+            if heatmap_quality is not None:
+                first_maps = _update_heatmap_quality(heatmap_quality, out, batch, device, first_maps)
         center, scale = meta["center"].to(device).float(), meta["scale"].to(device).float()
         img_kp = heatmap_to_image_coords(kp, center, scale, cfg.data.input_size, cfg.data.heatmap_size)
         if box_scores is not None:
@@ -132,7 +146,42 @@ def validate(model, loader, device, cfg, logger, flip_test=True, scales=None, pc
                 + ("" if ann else "  (reference OKS matching against the loader's ground truth: the loader has no annotation file)"))
     if error_analysis is not None:
         log_error_report(error_analysis, logger, error_report)
+    if heatmap_quality is not None:
+        log_heatmap_quality(heatmap_quality, logger, heatmap_quality_report, heatmap_quality_sheet, first_maps)
     return metrics, evaluator.predictions
+
+
+def _update_heatmap_quality(accumulator, out, batch, device, first_maps):
+    """One batch into the accumulator; -> the (prediction, target) maps of the very first sample, kept on the device for the sheet."""
+    hm = out.get("heatmaps") if isinstance(out, dict) else None
+    target = batch["target"].to(device)
+    if hm is None or tuple(hm.shape) != tuple(target.shape):
+        raise RuntimeError(f"validate: the heat-map quality compares the model's heat maps with the loader's target, map by map; the model gives "
+                           f"{None if hm is None else tuple(hm.shape)} and the loader {tuple(target.shape)}")
+    accumulator.update(hm, target, batch["target_weight"].to(device))
+    return (hm[0].detach().float().clone(), target[0].float().clone()) if first_maps is None else first_maps
+
+
+def log_heatmap_quality(accumulator, logger, path=None, sheet_path=None, first_maps=None):
+    """The report of a filled `HeatmapQualityAccumulator`: one log line per joint and the pooled line, the whole of it as JSON to `path`, and
+    the target / prediction / difference panels of `first_maps` = (pred (K,h,w), target (K,h,w)) as an image to `sheet_path`."""
+    import json
+    from infantposeestimation_gaussianbias_amd.utils.feature_maps import heatmap_quality_sheet, quality_report_json
+    from infantposeestimation_gaussianbias_amd.utils.visualization import write_image
+    report = accumulator.compute()
+    line = lambda r: f"n {r['n']}  peak distance {r['peak_distance']:.3f} px  correlation {r['correlation']:.4f}  IoU {r['iou_half_max']:.4f}"  # noqa: E731
+    for joint in report["joints"]:
+        logger.info(f"  joint {joint['joint']}: {line(joint)}")
+    logger.info(f"Heat-map quality over {report['n_samples']} samples: {line(report['pooled'])}  MSE {report['pooled']['mse']:.3e}")
+    if path:
+        with open(path, "w") as f:
+            json.dump(quality_report_json(report), f)
+        logger.info(f"Heat-map quality written to {path}")
+    if sheet_path and first_maps is not None:
+        sheet, _ = heatmap_quality_sheet(*first_maps)
+        write_image(sheet, sheet_path)
+        logger.info(f"Heat-map quality sheet of the first sample written to {sheet_path}")
+    return report
 
 
 def log_error_report(analyzer, logger, path=None):
@@ -183,8 +232,14 @@ def main(args):
     if getattr(args, "error_report", None):
         from infantposeestimation_gaussianbias_amd.utils import KeypointErrorAnalyzer
         error_analysis = KeypointErrorAnalyzer(cfg.data.num_keypoints, pixel_threshold=getattr(args, "error_px", 10.0))
+    quality = None
+    if getattr(args, "heatmap_quality", None):
+        from infantposeestimation_gaussianbias_amd.utils import HeatmapQualityAccumulator
+        quality = HeatmapQualityAccumulator(cfg.data.num_keypoints)
     metrics, _ = validate(model, loader, device, cfg, logger, flip_test=not args.no_flip, scales=cfg.test_scales, pck_thresholds=pck_thresholds,
-                          error_analysis=error_analysis, error_report=getattr(args, "error_report", None))
+                          error_analysis=error_analysis, error_report=getattr(args, "error_report", None), heatmap_quality=quality,
+                          heatmap_quality_report=getattr(args, "heatmap_quality", None),
+                          heatmap_quality_sheet=getattr(args, "heatmap_quality_sheet", None))
     logger.info(f"Loss: {metrics['loss']:.4f}")
     if getattr(args, "activation_report", None):
         log_activation_report(model, loader, device, logger, args.activation_report, getattr(args, "activation_batches", 1))
@@ -211,6 +266,16 @@ def log_activation_report(model, loader, device, logger, path=None, max_batches=
     return report
 
 
+class _Parser(argparse.ArgumentParser):
+    """--heatmap_quality_sheet only means something next to --heatmap_quality: refused while parsing, like any other bad combination."""
+
+    def parse_args(self, args=None, namespace=None):
+        ns = super().parse_args(args, namespace)
+        if ns.heatmap_quality_sheet and not ns.heatmap_quality:
+            self.error("--heatmap_quality_sheet needs --heatmap_quality PATH: the sheet is written by the heat-map quality pass")
+        return ns
+
+
 def apply_detector_box_args(cfg, args):
     """--bbox_file / --det_score_thr / --oks_nms / --soft_nms / --in_vis_thr onto the config (a flag that is not given leaves the yaml's value)."""
     if getattr(args, "bbox_file", None):
@@ -229,7 +294,7 @@ def apply_detector_box_args(cfg, args):
 
 
 def build_parser():
-    p = argparse.ArgumentParser(description="Validate Pose Estimation Model")
+    p = _Parser(description="Validate Pose Estimation Model")
     p.add_argument("--checkpoint", type=str, required=True)
     p.add_argument("--data_root", type=str, default=None)
     p.add_argument("--batch_size", type=int, default=32)
@@ -251,6 +316,12 @@ def build_parser():
                         "JSON: mean, std, min, max, quantiles, zero / negative fractions and the dead channels per layer (default: nothing)")
     p.add_argument("--activation_batches", type=int, default=1, metavar="N",
                    help="--activation_report: how many batches of the loader to run (default 1, as the reference's dead-neuron analysis)")
+    p.add_argument("--heatmap_quality", type=str, default=None, metavar="PATH",
+                   help="also measure the predicted heat maps against the loader's targets on the device and write the report to PATH as JSON: "
+                        "per joint and pooled the mean squared error, peak distance, correlation, half-maximum IoU and mass ratio over the "
+                        "samples whose target weight is > 0 (default: nothing)")
+    p.add_argument("--heatmap_quality_sheet", type=str, default=None, metavar="PNG",
+                   help="--heatmap_quality: also write the first sample's target / prediction / |difference| panels, one row per joint, as an image")
     p.add_argument("--bbox_file", type=str, default=None,
                    help="validate on detector boxes: a COCO-style person-detection file [{image_id, category_id, bbox, score}], relative to "
                         "data_root (default: the config's bbox_file; none: crops from the ground-truth boxes)")
