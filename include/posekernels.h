@@ -166,6 +166,33 @@ int pk_affine_crop_jitter_ws_bytes(int n_samples, int out_w, int out_h);
 int pk_affine_crop_jitter_normalize(const void* src_u8, const void* desc_table, const void* jitter_table, int n_samples, int out_w, int out_h,
                                     float* out_nchw_f32, void* out_nhwc8_bf16, const float* mean3, const float* std3, void* ws,
                                     int64_t ws_bytes, void* stream);
+/* The same crop with this project's occlusion, blur and noise augmentation (DESIGN.md "Occlusion, blur and noise on the device") on the
+ * warped bytes, per sample in this order: colour jitter (exactly the arithmetic above, m from the byte sum of the warped crop), Gaussian
+ * blur, additive sensor noise, rectangle erasing, then the normalisation.  Every stage has an off state in which it does nothing: a row
+ * with only the jitter on gives pk_affine_crop_jitter_normalize's bits, a row of zeros pk_affine_crop_normalize's.  Blur, noise and erasing
+ * are integer arithmetic, with pix = y out_w + x and uint32 arithmetic mod 2^32 in
+ *   hash(seed, pix, stream):  x = seed + pix 0x9E3779B9 + stream 0x85EBCA6B;  x ^= x >> 16;  x *= 0x7FEB352D;  x ^= x >> 15;  x *= 0x846CA68B;  x ^= x >> 16
+ *   blur (radius R = 1 .. PK_AUG_MAX_RADIUS, 0 = off; weights q[0] + 2 sum_{k>=1} q[k] = 256; clamp-to-edge), per channel:
+ *     t(x, y) = (sum_{k=-R..R} q[|k|] u(clamp(x + k), y) + 128) >> 8;   v(x, y) = (sum_k q[|k|] t(x, clamp(y + k)) + 128) >> 8
+ *   noise (amp = 1 .. 255, 0 = off), channel c:  h = hash(noise_seed, pix, 0x100 + c);  s = sum of the four bytes of h - 510;
+ *     v' = clamp(v + ((amp s + 256) >> 9), 0, 255), the shift arithmetic (floor)
+ *   erasing (n_rects = 0 .. PK_AUG_MAX_RECTS): rectangle r covers x0 <= x < x1, y0 <= y < y1 (clipped to the crop by that test; may be
+ *     empty), a later one overwrites an earlier one; mode 0 writes its RGB bytes, mode 1 bytes 0, 1, 2 of hash(erase_seed, pix, 1 + r).
+ * aug_table rows (PK_AUG_ROW_BYTES = 176 bytes, 16-byte aligned), one per sample, little-endian, in this order:
+ *   int32 jitter_enable; float b, c, s;  int32 radius;  int32 q[8] (q[0] centre; entries beyond radius unread);  int32 amp;  uint32 noise_seed;
+ *   int32 n_rects;  uint32 erase_seed;  4 x { int32 x0, y0, x1, y1;  int32 mode;  uint32 rgb = r | g << 8 | b << 16 };  12 bytes of padding.
+ * The table is device memory, so the entry cannot check the rows: the caller does (DeviceCropper raises before anything is staged).  The
+ * kernel clamps radius to 0 .. 7, amp to 0 .. 255 and n_rects to 0 .. 4, treats every mode but 0 as 1, and writes nothing out of bounds
+ * whatever a row holds.  Two launches on `stream` (the warp into the workspace, then one 32 x 32 output tile per workgroup); ws:
+ * pk_affine_crop_augment_ws_bytes(n_samples, out_w, out_h) bytes -- the jitter entry's formula and its 2^32 refusal -- 4-byte aligned.
+ * PK_ERR_INVALID before any launch: a null pointer, a bad shape, a short workspace, a misaligned workspace, NHWC output or table.        */
+#define PK_AUG_MAX_RADIUS 7
+#define PK_AUG_MAX_RECTS 4
+#define PK_AUG_ROW_BYTES 176
+int pk_affine_crop_augment_ws_bytes(int n_samples, int out_w, int out_h);
+int pk_affine_crop_augment_normalize(const void* src_u8, const void* desc_table, const void* aug_table, int n_samples, int out_w, int out_h,
+                                     float* out_nchw_f32, void* out_nhwc8_bf16, const float* mean3, const float* std3, void* ws,
+                                     int64_t ws_bytes, void* stream);
 
 /* ---- D4: flip-test merge (models/pose_estimator.py:303-319): out = (a + swapLR(flipW(b)))/2 ------------- */
 int pk_flip_merge(const float* a, const float* b_flipped, const int32_t* partner, float* out,

@@ -6,7 +6,9 @@ identically.  Extension over the reference: `get_config(path_or_name)` also acce
   * a legacy-format yaml (reference configs/*.yaml, written by root config.py:135-224): `MODEL.NUM_JOINTS`,
     `MODEL.IMAGE_SIZE`, `MODEL.HEATMAP_SIZE`, `MODEL.SIGMA`, `TRAIN.*` are mapped onto the dataclass fields, and
     `DATA.COLOR_JITTER.{BRIGHTNESS,CONTRAST,SATURATION}` onto `cfg.train.color_jitter` (a yaml that names it trains with it; a
-    missing sub-key reads as 0, and a block that is empty or all zero leaves jitter off), and `ADVANCED.MULTI_SCALE_TEST` /
+    missing sub-key reads as 0, and a block that is empty or all zero leaves jitter off), this project's own `DATA.BLUR {PROB, SIGMA}` /
+    `DATA.NOISE {PROB, SIGMA}` / `DATA.OCCLUSION {PROB, MAX_RECTS, AREA, ASPECT, FILL}` onto `cfg.train.blur` / `sensor_noise` /
+    `occlusion` (`check_augment`; an empty block or `PROB: 0` leaves the stage off), and `ADVANCED.MULTI_SCALE_TEST` /
     `ADVANCED.SCALE_LIST` onto `cfg.test_scales` (multi-scale test; off unless MULTI_SCALE_TEST is true), `EVAL.{METRICS, PCK_THRESHOLD,
     MIN_KEYPOINT_VISIBILITY}` onto `cfg.eval_metrics` / `pck_threshold` / `min_keypoint_visibility`, `TEMPORAL.*` onto `cfg.temporal` and
     `CLINICAL.*` onto `cfg.clinical` (movement analysis: utils/metrics.py, `validate.py --pck`, `inference.py --sequence`), and
@@ -99,6 +101,12 @@ class TrainConfig:
     # Weight EMA (`train.py --ema DECAY`): None (off) or the decay of the average the optimiser kernel keeps.  A plain class attribute too;
     # no yaml key (the reference's configs have none).
     ema_decay = None
+    # Occlusion, blur and sensor noise of the training crops (this project's own legacy-yaml keys DATA.BLUR / DATA.NOISE / DATA.OCCLUSION,
+    # `train.py --blur / --noise / --occlusion`), plain class attributes as well: None (off) or what `check_augment` returns --
+    # {'prob', 'sigma': (lo, hi)} for blur and sensor_noise, {'prob', 'max_rects', 'area': (lo, hi), 'aspect': (lo, hi), 'fill'} for occlusion.
+    blur = None
+    sensor_noise = None
+    occlusion = None
 
 
 @dataclass
@@ -220,6 +228,87 @@ def check_ohkm(topk, weight=1.0, num_keypoints=None, allow_off=True, what=("ohkm
     return k, w
 
 
+AUGMENT_DEFAULTS = {
+    'blur': {'prob': 0.3, 'sigma': (0.3, 2.0)},
+    'noise': {'prob': 0.3, 'sigma': (2.0, 10.0)},
+    'occlusion': {'prob': 0.5, 'max_rects': 2, 'area': (0.02, 0.2), 'aspect': (0.3, 3.3), 'fill': 'random'},
+}
+_AUGMENT_SIGMA_MAX = {'blur': 2.5, 'noise': 73.0}      # blur: radius 7 holds 3 sigma up to 2.33 and the table no more; noise: amp <= 255
+
+
+def _check_range(value, what, hi=None):
+    """(lo, hi) with 0 < lo <= hi (<= `hi`), as floats."""
+    try:
+        lo, up = value
+        ok = not isinstance(lo, (bool, str)) and not isinstance(up, (bool, str))
+        lo, up = float(lo), float(up)
+        ok = ok and math.isfinite(lo) and math.isfinite(up) and 0 < lo <= up and (hi is None or up <= hi)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"{what} must be [lo, hi] with 0 < lo <= hi" + (f" <= {hi:g}" if hi is not None else "") + f", got {value!r}")
+    return lo, up
+
+
+def _check_prob(value, what):
+    try:
+        p = float(value)
+        ok = not isinstance(value, (bool, str)) and 0 <= p <= 1
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"{what} must be a probability in [0, 1], got {value!r}")
+    return p
+
+
+def check_fill(fill, what="fill"):
+    """The fill of the erased rectangles: 'random', 'mean' or an (r, g, b) triple of bytes (returned as a tuple of ints)."""
+    if isinstance(fill, str):
+        if fill in ("random", "mean"):
+            return fill
+        raise ValueError(f"{what} must be 'random', 'mean' or three bytes R,G,B, got {fill!r}")
+    try:
+        rgb = tuple(fill)
+        ok = len(rgb) == 3 and all(not isinstance(v, (bool, str)) and int(v) == v and 0 <= int(v) <= 255 for v in rgb)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"{what} must be 'random', 'mean' or three bytes R,G,B, got {fill!r}")
+    return tuple(int(v) for v in rgb)
+
+
+def check_augment(kind, setting, what=None):
+    """One of the three augmentation settings ('blur', 'noise', 'occlusion') as the dict `get_train_transforms` takes, or None when it is
+    off (`setting` None or empty, or prob 0); missing entries take AUGMENT_DEFAULTS.  ValueError naming `what` (the yaml block or flag the
+    value came from) and the entry: prob outside [0, 1]; a sigma range that is not 0 < lo <= hi <= 2.5 (blur: the table holds radius 7)
+    or <= 73 (noise: the amplitude 2 sqrt(3) sigma must stay <= 255); max_rects outside 1 .. 4; an area range outside 0 < lo <= hi <= 1;
+    an aspect range that is not 0 < lo <= hi; an unknown fill."""
+    what = what or kind
+    if kind not in AUGMENT_DEFAULTS:
+        raise ValueError(f"unknown augmentation {kind!r}")
+    if not setting:
+        return None
+    if not isinstance(setting, dict) or set(setting) - set(AUGMENT_DEFAULTS[kind]):
+        raise ValueError(f"{what} must be a mapping with keys from {sorted(AUGMENT_DEFAULTS[kind])}, got {setting!r}")
+    s = {**AUGMENT_DEFAULTS[kind], **setting}
+    out = {'prob': _check_prob(s['prob'], f"{what}.prob")}
+    if kind in ('blur', 'noise'):
+        out['sigma'] = _check_range(s['sigma'], f"{what}.sigma", _AUGMENT_SIGMA_MAX[kind])
+    else:
+        try:
+            n = int(s['max_rects'])
+            ok = not isinstance(s['max_rects'], bool) and n == s['max_rects'] and 1 <= n <= 4
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f"{what}.max_rects must be an integer from 1 to 4, got {s['max_rects']!r}")
+        out['max_rects'] = n
+        out['area'] = _check_range(s['area'], f"{what}.area", 1.0)
+        out['aspect'] = _check_range(s['aspect'], f"{what}.aspect")
+        out['fill'] = check_fill(s['fill'], f"{what}.fill")
+    return out if out['prob'] > 0 else None
+
+
 def _apply_preset(cfg: Config, name: str) -> Config:
     bb, head, ch, insz, hmsz, K, sigma = _PRESETS[name]
     cfg.model.backbone, cfg.model.head_type = bb, head
@@ -270,6 +359,13 @@ def _apply_legacy_yaml(cfg: Config, path: str) -> Config:
         # not the identity (u / 255 * 255 truncates)
         rng = tuple(float((cj or {}).get(k, 0) or 0) for k in ('BRIGHTNESS', 'CONTRAST', 'SATURATION'))
         cfg.train.color_jitter = rng if any(rng) else None
+    # DATA.BLUR / DATA.NOISE / DATA.OCCLUSION are this project's own keys (the reference's yamls have none); an empty block or PROB: 0 is off
+    for key, kind, attr in (('BLUR', 'blur', 'blur'), ('NOISE', 'noise', 'sensor_noise'), ('OCCLUSION', 'occlusion', 'occlusion')):
+        blk = (y.get('DATA', {}) or {}).get(key)
+        if blk is not None:
+            if not isinstance(blk, dict):
+                raise ValueError(f"DATA.{key} must be a mapping, got {blk!r}")
+            setattr(cfg.train, attr, check_augment(kind, {str(k).lower(): v for k, v in blk.items()}, f"DATA.{key}"))
     # LOSS.USE_OHKM / LOSS.TOPK are HRNet's own keys (TOPK defaults to its 8); LOSS.OHKM_WEIGHT weighs the term in the fusion loss.  A yaml
     # without USE_OHKM: true keeps mining off whatever else the block holds
     ls = y.get('LOSS', {}) or {}

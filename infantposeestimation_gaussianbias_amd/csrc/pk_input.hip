@@ -178,3 +178,173 @@ extern "C" int pk_affine_crop_jitter_normalize(const void* src_u8, const void* d
                        std3[0], std3[1], std3[2]);
     return pk_launch_status("pk_affine_crop_jitter_normalize");
 }
+
+// ------------------------------------------------------------------------------------------------ f2 + occlusion, blur, noise
+// This project's own augmentation of the warped bytes (DESIGN.md "Occlusion, blur and noise on the device"; the contract is in
+// posekernels.h): colour jitter, separable integer Gaussian blur, hashed sensor noise and rectangle erasing between the 8-bit warp and the
+// normalisation.  Launch 1 is k_crop_u8 as above; k_augment_normalize then takes one 32 x 32 output tile of one sample per workgroup.
+// With the blur on it loads the tile and an R-pixel halo (clamped coordinates, jittered on the way in), runs the horizontal pass from one
+// LDS image into a second and the vertical pass into registers; with the blur off it touches no LDS beyond the reduction of S.
+struct AugRect {
+    int32_t x0, y0, x1, y1;
+    int32_t mode;            // 0: the constant `rgb`, otherwise hashed bytes
+    uint32_t rgb;            // r | g << 8 | b << 16
+};
+struct AugDesc {
+    JitterDesc jit;
+    int32_t radius;
+    int32_t q[PK_AUG_MAX_RADIUS + 1];
+    int32_t amp;
+    uint32_t noise_seed;
+    int32_t n_rects;
+    uint32_t erase_seed;
+    AugRect rect[PK_AUG_MAX_RECTS];
+    int32_t pad[3];
+};
+static_assert(sizeof(AugDesc) == PK_AUG_ROW_BYTES && PK_AUG_ROW_BYTES % 16 == 0, "aug_table row layout");
+// The jitter arithmetic of k_jitter_normalize on one pixel's bytes, m given.
+__device__ __forceinline__ void jitter_pixel_u8(int u[3], float b, float c, float s, float m) {
+    float x[3];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        x[ch] = __fmul_rn(__fdiv_rn((float)u[ch], 255.0f), b);
+        x[ch] = __fadd_rn(__fmul_rn(__fsub_rn(x[ch], m), c), m);
+    }
+    const float g = __fdiv_rn(__fadd_rn(__fadd_rn(x[0], x[1]), x[2]), 3.0f);
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        const float v = fminf(fmaxf(__fadd_rn(g, __fmul_rn(__fsub_rn(x[ch], g), s)), 0.f), 1.f);
+        u[ch] = (int)__fmul_rn(v, 255.0f);
+    }
+}
+__device__ __forceinline__ uint32_t aug_hash(uint32_t seed, uint32_t pix, uint32_t stream) {
+    uint32_t x = seed + pix * 0x9E3779B9u + stream * 0x85EBCA6Bu;
+    x ^= x >> 16;
+    x *= 0x7FEB352Du;
+    x ^= x >> 15;
+    x *= 0x846CA68Bu;
+    x ^= x >> 16;
+    return x;
+}
+// One blur tap on a packed pixel: red and blue share a register as two 16-bit fields.  A field's sum is at most 255 * 256 + 128 = 65408,
+// so it never carries into its neighbour.
+__device__ __forceinline__ void blur_tap(uint32_t p, uint32_t q, uint32_t& rb, uint32_t& g) {
+    rb += (p & 0x00FF00FFu) * q;
+    g += ((p >> 8) & 0xFFu) * q;
+}
+__device__ __forceinline__ uint32_t blur_round(uint32_t rb, uint32_t g) {
+    return (((rb + 0x00800080u) >> 8) & 0x00FF00FFu) | (((g + 128u) >> 8) << 8);
+}
+constexpr int kAugTile = 32, kAugSpan = kAugTile + 2 * PK_AUG_MAX_RADIUS;
+__global__ void __launch_bounds__(256) k_augment_normalize(const uint32_t* __restrict__ crop, const uint32_t* __restrict__ partial,
+                                                           const AugDesc* __restrict__ aug, int out_w, int out_h, float* __restrict__ out_nchw,
+                                                           uint16_t* __restrict__ out_nhwc8, float m0, float m1, float m2, float s0, float s1,
+                                                           float s2) {
+    // A half-wave is 32 consecutive columns of one row in every pass, so each 4-byte LDS access of a 32-lane group covers 32 consecutive
+    // dwords = 32 different banks, whatever the row stride: neither the horizontal nor the vertical pass serialises.
+    __shared__ uint32_t red[4];
+    __shared__ uint32_t ta[kAugSpan * kAugSpan];         // jittered tile + halo
+    __shared__ uint32_t tb[kAugSpan * kAugTile];         // after the horizontal pass
+    __shared__ uint32_t qs[2 * PK_AUG_MAX_RADIUS + 1];   // the taps, -R .. R
+    const AugDesc* __restrict__ a = aug + blockIdx.y;    // per-sample fields are uniform over the workgroup
+    const int tid = threadIdx.x, plane = out_w * out_h, tiles_x = (out_w + kAugTile - 1) / kAugTile;
+    const int ty0 = (int)blockIdx.x / tiles_x, x0 = ((int)blockIdx.x - ty0 * tiles_x) * kAugTile, y0 = ty0 * kAugTile;
+    const uint32_t* __restrict__ cs = crop + (size_t)blockIdx.y * plane;
+    const int jit_on = a->jit.enable;
+    const float jb = a->jit.b, jc = a->jit.c, js = a->jit.s;
+    float m = 0.f;
+    if (jit_on) {                        // as k_jitter_normalize: the exact S from the partial sums of k_crop_u8
+        const int nblk = (plane + 255) / 256;
+        uint32_t S = 0;
+        for (int i = tid; i < nblk; i += 256) S += partial[(size_t)blockIdx.y * nblk + i];
+        S = block_reduce<4>(S, red, SumOp());
+        m = (float)__dmul_rn(__ddiv_rn((double)S, __dmul_rn(255.0, (double)plane * 3.0)), (double)jb);
+    }
+    auto load = [&](int x, int y) -> uint32_t {          // one warped pixel, jittered
+        const uint32_t p = cs[y * out_w + x];
+        if (!jit_on) return p;
+        int u[3] = {(int)(p & 255u), (int)((p >> 8) & 255u), (int)(p >> 16)};
+        jitter_pixel_u8(u, jb, jc, js, m);
+        return (uint32_t)u[0] | ((uint32_t)u[1] << 8) | ((uint32_t)u[2] << 16);
+    };
+    const int R = min(max(a->radius, 0), PK_AUG_MAX_RADIUS);
+    if (R > 0) {
+        const int span = kAugTile + 2 * R;
+        if (tid <= 2 * R) qs[tid] = (uint32_t)a->q[abs(tid - R)];
+        for (int i = tid; i < span * span; i += 256) {
+            const int ly = i / span, lx = i - ly * span;
+            ta[ly * kAugSpan + lx] = load(min(max(x0 + lx - R, 0), out_w - 1), min(max(y0 + ly - R, 0), out_h - 1));
+        }
+        __syncthreads();
+        for (int i = tid; i < span * kAugTile; i += 256) {
+            const int ly = i / kAugTile, lx = i - ly * kAugTile;
+            uint32_t rb = 0, g = 0;
+            for (int k = 0; k <= 2 * R; ++k) blur_tap(ta[ly * kAugSpan + lx + k], qs[k], rb, g);
+            tb[i] = blur_round(rb, g);
+        }
+        __syncthreads();
+    }
+    const int amp = min(max(a->amp, 0), 255), n_rects = min(max(a->n_rects, 0), PK_AUG_MAX_RECTS);
+    const uint32_t noise_seed = a->noise_seed, erase_seed = a->erase_seed;
+    const float mean[3] = {m0, m1, m2}, sd[3] = {s0, s1, s2};
+    const int lx = tid & (kAugTile - 1), x = x0 + lx;
+    if (x >= out_w) return;
+    for (int ly = tid / kAugTile; ly < kAugTile; ly += 256 / kAugTile) {
+        const int y = y0 + ly;
+        if (y >= out_h) break;
+        uint32_t p;
+        if (R > 0) {
+            uint32_t rb = 0, g = 0;
+            for (int k = 0; k <= 2 * R; ++k) blur_tap(tb[(ly + k) * kAugTile + lx], qs[k], rb, g);
+            p = blur_round(rb, g);
+        } else {
+            p = load(x, y);
+        }
+        const uint32_t pix = (uint32_t)(y * out_w + x);
+        int u[3] = {(int)(p & 255u), (int)((p >> 8) & 255u), (int)(p >> 16)};
+        if (amp > 0) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const uint32_t h = aug_hash(noise_seed, pix, 0x100u + c);
+                const int s = (int)((h & 255u) + ((h >> 8) & 255u) + ((h >> 16) & 255u) + (h >> 24)) - 510;
+                u[c] = min(max(u[c] + ((amp * s + 256) >> 9), 0), 255);
+            }
+        }
+        for (int r = 0; r < n_rects; ++r) {
+            const AugRect& k = a->rect[r];
+            if (x < k.x0 || x >= k.x1 || y < k.y0 || y >= k.y1) continue;
+            const uint32_t f = k.mode == 0 ? k.rgb : aug_hash(erase_seed, pix, 1u + r);
+            u[0] = (int)(f & 255u), u[1] = (int)((f >> 8) & 255u), u[2] = (int)((f >> 16) & 255u);
+        }
+        crop_normalize_store(u, blockIdx.y, (int)pix, (size_t)plane, out_nchw, out_nhwc8, mean, sd);
+    }
+}
+extern "C" int pk_affine_crop_augment_ws_bytes(int n_samples, int out_w, int out_h) {
+    PK_REQUIRE(n_samples > 0 && out_w > 0 && out_h > 0 && (int64_t)out_w * out_h * 765 < (int64_t)1 << 32,
+               "pk_affine_crop_augment_ws_bytes: bad shape n=%d w=%d h=%d (the byte sum of a crop must stay below 2^32)", n_samples, out_w, out_h);
+    const int64_t nblk = ((int64_t)out_w * out_h + 255) / 256, bytes = 4 * (jitter_partial_offset(n_samples, out_w, out_h) + n_samples * nblk);
+    PK_REQUIRE(bytes <= 0x7fffffff, "pk_affine_crop_augment_ws_bytes: %lld-byte workspace for n=%d w=%d h=%d exceeds 2^31", (long long)bytes,
+               n_samples, out_w, out_h);
+    return (int)bytes;
+}
+extern "C" int pk_affine_crop_augment_normalize(const void* src_u8, const void* desc_table, const void* aug_table, int n_samples, int out_w,
+                                                int out_h, float* out_nchw_f32, void* out_nhwc8_bf16, const float* mean3, const float* std3,
+                                                void* ws, int64_t ws_bytes, void* stream) {
+    PK_REQUIRE(crop_pointers_ok(src_u8, desc_table, out_nchw_f32, out_nhwc8_bf16, mean3, std3) && aug_table && ws,
+               "pk_affine_crop_augment_normalize: null pointer");
+    const int need = pk_affine_crop_augment_ws_bytes(n_samples, out_w, out_h);      // the shape checks live there
+    if (need < 0) return need;
+    PK_REQUIRE(ws_bytes >= need, "pk_affine_crop_augment_normalize: workspace of %lld bytes, %d needed", (long long)ws_bytes, need);
+    PK_REQUIRE((((uintptr_t)ws) & 3) == 0 && nhwc8_aligned(out_nhwc8_bf16) && (((uintptr_t)aug_table) & 15) == 0,
+               "pk_affine_crop_augment_normalize: alignment (workspace 4 bytes, NHWC output 16 bytes, augmentation table 16 bytes)");
+    const int nblk = (out_w * out_h + 255) / 256;
+    const int tiles = ((out_w + kAugTile - 1) / kAugTile) * ((out_h + kAugTile - 1) / kAugTile);
+    uint32_t* crop = (uint32_t*)ws;
+    uint32_t* partial = crop + jitter_partial_offset(n_samples, out_w, out_h);
+    hipLaunchKernelGGL(k_crop_u8, dim3(nblk, n_samples), dim3(256), 0, (hipStream_t)stream, (const unsigned char*)src_u8, (const CropDesc*)desc_table,
+                       out_w, out_h, crop, partial);
+    hipLaunchKernelGGL(k_augment_normalize, dim3(tiles, n_samples), dim3(256), 0, (hipStream_t)stream, (const uint32_t*)crop,
+                       (const uint32_t*)partial, (const AugDesc*)aug_table, out_w, out_h, out_nchw_f32, (uint16_t*)out_nhwc8_bf16, mean3[0],
+                       mean3[1], mean3[2], std3[0], std3[1], std3[2]);
+    return pk_launch_status("pk_affine_crop_augment_normalize");
+}

@@ -172,8 +172,11 @@ class DeviceBatcher:
         d = self.cfg.data
         img_scales = None
         if self.test_scales is None:
+            # blur / noise / occlusion decisions of the records (RandomBlur, SensorNoise, RandomOcclusion); none: the call of before
+            aug = [{k: s[k] for k in ("blur", "noise", "occlusion") if s.get(k) is not None} or None for s in samples]
+            extra = {"augment": aug} if any(a is not None for a in aug) else {}
             img32, img16 = self.cropper([s["img"] for s in samples], [s["matrix"] for s in samples], [s.get("flip", False) for s in samples],
-                                        jitter=[s.get("jitter") for s in samples])
+                                        jitter=[s.get("jitter") for s in samples], **extra)
         else:
             S, B = len(self.test_scales), len(samples)
             per = [multiscale_matrices(s["center"], s["scale"], self.test_scales, d.input_size) for s in samples]
@@ -229,7 +232,8 @@ def build_coco_dataloader(cfg, is_train: bool = True, device="cuda"):
     """coco_dataset.py:253-306 with the image work moved to the device."""
     d, t = cfg.data, cfg.train
     tf = (get_train_transforms(d.input_size, t.flip_prob, t.rotation_factor, t.scale_factor, color_jitter=t.color_jitter,
-                               color_jitter_prob=t.color_jitter_prob) if is_train else get_val_transforms(d.input_size))
+                               color_jitter_prob=t.color_jitter_prob, blur=t.blur, noise=t.sensor_noise, occlusion=t.occlusion)
+          if is_train else get_val_transforms(d.input_size))
     ds = COCOPoseDataset(d.data_root, d.train_ann if is_train else d.val_ann, d.train_img_prefix if is_train else d.val_img_prefix, d.input_size,
                          d.heatmap_size, d.sigma, d.num_keypoints, tf, is_train, d.flip_pairs,
                          bbox_file=None if is_train else getattr(cfg, "bbox_file", None), det_score_thr=getattr(cfg, "det_score_thr", 0.0))

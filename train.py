@@ -8,7 +8,8 @@ Differences from the reference loop (train.py:131-228): no per-step `loss.item()
 log interval), bf16 instead of fp16+GradScaler, fused AdamW over a flat parameter buffer, optional hipGraph replay
 (`--graph`), GradScaler's "drop the step when a gradient is inf/NaN" and gradient-norm clipping as an opt-in device-side guard
 (`--skip_nonfinite`, `--clip_grad_norm X`), colour jitter on the device (`--color_jitter B C S`, or DATA.COLOR_JITTER of a legacy
-yaml), and an exponential moving average of the weights kept by the optimiser kernel (`--ema DECAY`): validation inside the loop then
+yaml), blur, sensor noise and rectangle erasing of the crops on the device (`--blur`, `--noise`, `--occlusion`, or DATA.BLUR / NOISE /
+OCCLUSION of a legacy yaml; labels stay), and an exponential moving average of the weights kept by the optimiser kernel (`--ema DECAY`): validation inside the loop then
 scores the averaged weights, and checkpoints carry them as "ema_state_dict" (validate.py / inference.py `--ema` load them), and online
 hard keypoint mining (`--ohkm TOPK [--ohkm_weight W]`, or LOSS.USE_OHKM / TOPK of a legacy yaml): per sample only the TOPK worst-fitted
 joints count in the heatmap loss, selected on the device inside the step; every validation interval logs which joints were selected, and
@@ -123,6 +124,39 @@ def selection_report(model, names):
     return ", ".join(f"{names[i]} {100 * share[i]:.1f}%" for i in np.argsort(-share, kind="stable"))
 
 
+def parse_fill(text):
+    """--occlusion_fill: 'random', 'mean' or 'R,G,B'."""
+    if text in ("random", "mean"):
+        return text
+    try:
+        return tuple(int(v) for v in text.split(","))
+    except ValueError:
+        return text          # check_augment refuses it and names the flag
+
+
+def apply_augment_flags(cfg, args):
+    """--blur / --noise / --occlusion (+ --occlusion_area, --occlusion_fill) onto cfg.train.blur / sensor_noise / occlusion, over what a
+    yaml set.  A flag gives the probability and the upper end of the range; the lower end is the default's, or the upper end where that is
+    smaller.  PROB 0 turns the stage off.  ValueError (naming the flag) for a value `check_augment` refuses."""
+    from infantposeestimation_gaussianbias_amd.configs.config import AUGMENT_DEFAULTS, check_augment
+    for flag, kind, attr in (("blur", "blur", "blur"), ("noise", "noise", "sensor_noise")):
+        v = getattr(args, flag)
+        if v is not None:
+            lo = min(AUGMENT_DEFAULTS[kind]["sigma"][0], v[1])
+            setattr(cfg.train, attr, check_augment(kind, {"prob": v[0], "sigma": (lo, v[1])}, f"--{flag}"))
+    if args.occlusion is not None:
+        n = args.occlusion[1]
+        cfg.train.occlusion = check_augment("occlusion", {**(cfg.train.occlusion or {}), "prob": args.occlusion[0],
+                                                          "max_rects": int(n) if float(n).is_integer() else n}, "--occlusion")
+    for flag, key, value in (("occlusion_area", "area", args.occlusion_area),
+                             ("occlusion_fill", "fill", parse_fill(args.occlusion_fill) if args.occlusion_fill is not None else None)):
+        if value is not None:
+            if cfg.train.occlusion is None:
+                raise ValueError(f"--{flag} needs --occlusion PROB MAX_RECTS (or a DATA.OCCLUSION block) with PROB > 0")
+            cfg.train.occlusion = check_augment("occlusion", {**cfg.train.occlusion, key: tuple(value) if key == "area" else value},
+                                                f"--{flag}")
+
+
 def main(args):
     cfg = get_config(args.config) if args.config else get_config()
     if args.data_root:
@@ -137,6 +171,7 @@ def main(args):
         cfg.train.color_jitter = tuple(args.color_jitter)
     if args.color_jitter_prob is not None:
         cfg.train.color_jitter_prob = args.color_jitter_prob
+    apply_augment_flags(cfg, args)
     if args.ema is not None:
         cfg.train.ema_decay = args.ema
     if args.ohkm is not None:
@@ -220,6 +255,16 @@ def build_parser():
     p.add_argument("--color_jitter", type=float, nargs=3, default=None, metavar=("B", "C", "S"),
                    help="brightness / contrast / saturation ranges of the colour jitter applied to training crops on the device")
     p.add_argument("--color_jitter_prob", type=float, default=None, help="share of the samples that are jittered (default 0.5)")
+    p.add_argument("--blur", type=float, nargs=2, default=None, metavar=("PROB", "SIGMA_MAX"),
+                   help="Gaussian blur of a share PROB of the training crops on the device, sigma up to SIGMA_MAX <= 2.5 pixels")
+    p.add_argument("--noise", type=float, nargs=2, default=None, metavar=("PROB", "SIGMA_MAX"),
+                   help="additive sensor noise on a share PROB of the training crops, standard deviation up to SIGMA_MAX <= 73 grey levels")
+    p.add_argument("--occlusion", type=float, nargs=2, default=None, metavar=("PROB", "MAX_RECTS"),
+                   help="erase 1 to MAX_RECTS <= 4 random rectangles in a share PROB of the training crops (labels stay)")
+    p.add_argument("--occlusion_area", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                   help="area of one erased rectangle as a fraction of the crop (default 0.02 0.2)")
+    p.add_argument("--occlusion_fill", type=str, default=None, metavar="random|mean|R,G,B",
+                   help="what the erased rectangles hold: random bytes (default), the ImageNet mean, or one colour")
     p.add_argument("--clip_grad_norm", type=float, default=0.0, metavar="X",
                    help="clip the global gradient norm to X on the device (torch.nn.utils.clip_grad_norm_; 0 = off); implies --skip_nonfinite")
     p.add_argument("--skip_nonfinite", action="store_true",
