@@ -784,6 +784,22 @@ int pk_conv1x1_bn_bwd_apply(const void* dy, const void* x, const void* w, const 
 int pk_conv1x1_bn_bwd(const void* dy, const void* x, const void* w, const float* save_mean, const float* save_rstd, const float* gamma,
                       float* partial, float* sums, float* dgamma, float* dbeta, void* draw, void* dresidual, int64_t rows, int Cin, int Cout,
                       int relu, const uint8_t* relu_mask, void* stream);
+/* ---- BatchNorm (train) + ReLU + 1x1 output conv of a fusion-head branch; the output conv's data gradient dt is never stored and the
+ * activated tensor t is written but not read back in forward (pk_bn_out1x1.hip).  raw, t: [rows][C] bf16, C = 128 or 256; N <= 48
+ * outputs; rows = B * hw.
+ * pk_bn_out1x1_supported: 1 for those shapes at rows >= 32 768.  Per-call environment switches: PK_BN_OUT1X1=0 (route off),
+ *   PK_BN_OUT1X1_MIN_ROWS (row threshold), PK_BN_OUT1X1_MAX_GRID (at most this many workgroups per launch).
+ * pk_bn_out1x1_fwd: t = bf16(relu(raw * scale + shift)), the ReLU bit mask and out [B][N][hw] fp32 = conv1x1(t) + bias (softplus): bit for
+ *   bit pk_bn_act followed by pk_conv2d_nhwc (out_mode 2).  w_fwd: the packed forward weight [N][1][C].
+ * pk_bn_out1x1_bwd: g = the maps' gradient as [rows][up8(N)] bf16 (pk_nchw_f32_to_nhwc_bf16, channels >= N zero); w_dgrad: the packed
+ *   data-gradient weight [C][1][up8(N)].  dt = bf16(g w_dgrad^T) is recomputed in both passes: partial [pk_bn_bwd_blocks(rows)][2][C],
+ *   sums [2][C], dgamma, dbeta and draw are pk_bn_bwd's on a stored dt bit for bit (either of its forms).                              */
+int pk_bn_out1x1_supported(int64_t rows, int C, int N);
+int pk_bn_out1x1_fwd(const void* raw, const float* scale, const float* shift, const void* w_fwd, const float* bias, void* t, float* out,
+                     uint8_t* relu_mask, int64_t rows, int C, int N, int hw, int softplus, void* stream);
+int pk_bn_out1x1_bwd(const void* g, const void* raw, const uint8_t* relu_mask, const void* w_dgrad, const float* save_mean,
+                     const float* save_rstd, const float* gamma, float* partial, float* sums, float* dgamma, float* dbeta, void* draw,
+                     int64_t rows, int C, int N, void* stream);
 /* nn.LayerNorm(C, eps 1e-5) over the channel dim of NHWC rows (hrformer.py:240,252,273,288).  C = row width (multiple of 8,
  * <= 1024); C_real (0 = C) = number of real channels when the rows carry zero padding: statistics over the real channels,
  * padded outputs / input gradients are zero.  gamma/beta (and dgamma/dbeta) have C entries, 16-byte aligned; the padded

@@ -8,7 +8,8 @@
 
 // The library reads nothing from the environment except the documented routing switches of the specialised convolution kernels
 // (PK_CONV8P, PK_CONV8P_MIN_TILES, PK_CONV3H, PK_CONV3H_MIN_TILES; PK_CONV1X1_BN, PK_CONV1X1_BN_MIN_ROWS, PK_CONV1X1_BN_MAX_GRID of
-// pk_conv1x1_bn.hip: the parity tests lower the thresholds to push small and ragged shapes through them).  Every other threshold is a
+// pk_conv1x1_bn.hip, PK_BN_OUT1X1, PK_BN_OUT1X1_MIN_ROWS, PK_BN_OUT1X1_MAX_GRID of pk_bn_out1x1.hip: the parity tests lower the thresholds to
+// push small and ragged shapes through them).  Every other threshold is a
 // constant next to the routing code that uses it, with the measurement behind it.
 
 #define PK_WAVE 64

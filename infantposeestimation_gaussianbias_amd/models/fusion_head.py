@@ -102,8 +102,8 @@ class HeatmapRegressionHead(nn.Module):
 
         def make(br, softplus=False):
             def run(ins):
-                t = nnops.conv_bn_act(ins[0], br["0"], br["1"], True, None, tr)
-                return nnops.head_out(t, br["3"], softplus)
+                # (training at full size: BatchNorm + ReLU + output conv in one forward pass, the output conv's data gradient never stored)
+                return nnops.conv_bn_act_out(ins[0], br["0"], br["1"], br["3"], softplus, tr)
             return run
 
         # the three branches are independent: on concurrent streams their small BatchNorm kernels (finalize, partial sums: a

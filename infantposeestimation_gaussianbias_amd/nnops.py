@@ -5,6 +5,7 @@ forward and backward are explicit sequences of C-ABI calls; torch only allocates
 
   conv_bn_act   A5/A6/H1  conv3x3|1x1 (MFMA implicit GEMM, BN statistics in the epilogue) -> BN finalize -> scale/shift(+res)(+ReLU)
   head_out      H1/H2     1x1 conv + bias (+softplus) -> fp32 NCHW maps
+  conv_bn_act_out  H1     a head branch: conv3x3 -> BN -> ReLU -> head_out; BN + ReLU + output conv fused, its data gradient never stored (training)
   attn_half     A1-A3     LN1 -> qkv GEMM (window gather) -> window attention -> proj GEMM (+residual, DropPath, window scatter)
   mlp_half      A3        LN2 -> fc1 GEMM + GELU -> fc2 GEMM (+residual, DropPath)
   fuse_sum      A4        sum of branches with fused bilinear up-sampling (+ReLU)
@@ -829,6 +830,83 @@ class _HeadOut(torch.autograd.Function):
 
 def head_out(x, conv, softplus=False):
     return _HeadOut.apply(x, conv.weight, conv.bias, softplus)
+
+
+# ================================================================================================ head branch: conv + BN + ReLU + output conv
+class _ConvBnActOut(torch.autograd.Function):
+    """conv_bn_act (train, ReLU, no residual) followed by head_out (pk_bn_out1x1.hip): forward writes the activated tensor t and the maps
+    from one read of raw (the output conv does not read t back), backward never stores the output conv's data gradient: both BatchNorm
+    passes recompute it.  The output conv's weight gradient is head_out's own launch on the saved t: the same sums, bit for bit."""
+
+    @staticmethod
+    def forward(ctx, x, weight, gamma, beta, out_weight, out_bias, bn, softplus):
+        ctx.params = (weight, gamma, beta, out_weight, out_bias)
+        wc = _wc()
+        wf, wd = wc.fwd[id(weight)], wc.dgrad[id(weight)]
+        owf, owd = wc.fwd[id(out_weight)], wc.dgrad[id(out_weight)]
+        Cout, ksize, N = weight.shape[0], weight.shape[2], out_weight.shape[0]
+        x = x.contiguous()
+        B, Hs, Ws, Cin, Ho, Wo = _conv_geometry(x, ksize, 1)
+        M, dev = B * Ho * Wo, x.device
+        wc.bn_eval.pop(id(bn), None)           # pk_bn_finalize rewrites the running statistics in place (no version bump)
+        raw, part = _conv_raw(x, wf, Cout, ksize, 1, True)
+        scale, shift, mean, rstd = (_e((Cout,), F32, dev) for _ in range(4))
+        call("pk_bn_finalize", part, part.shape[0], Cout, M, gamma, beta, bn.running_mean, bn.running_var, bn.num_batches_tracked, 0.1, 1e-5,
+             scale, shift, mean, rstd, stream_ptr())
+        mask = _e((M * Cout // 8,), torch.uint8, dev)
+        t = _e((B, Ho, Wo, Cout), BF16, dev)
+        out = _e((B, N, Ho, Wo), F32, dev)
+        call("pk_bn_out1x1_fwd", raw, scale, shift, owf, out_bias, t, out, mask, M, Cout, N, Ho * Wo, 1 if softplus else 0, stream_ptr())
+        ctx.save_for_backward(x, raw, t, mask, mean, rstd, gamma, wd, owd, out if softplus else x.new_empty(0))
+        ctx.meta = (softplus, N, ksize, (B, Hs, Ws, Ho, Wo), Cout)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, raw, t, mask, mean, rstd, gamma, wd, owd, y = ctx.saved_tensors
+        softplus, N, ksize, (B, Hs, Ws, Ho, Wo), Cout = ctx.meta
+        w_p, g_p, b_p, ow_p, ob_p = ctx.params
+        Cin, M, dev = x.shape[-1], B * Ho * Wo, x.device
+        # the maps' gradient as bf16 rows and the output conv's weight / bias gradient, as _HeadOut.backward launches them
+        Np = _up8(N)
+        g = _e((B, Ho, Wo, Np), BF16, dev)
+        call("pk_nchw_f32_to_nhwc_bf16", dout.contiguous(), y if softplus else None, g, B, N, Ho, Wo, Np, stream_ptr())
+        ow, ob = _Dest(ow_p), _Dest(ob_p)
+        geom = (B, Ho, Wo, Ho, Wo)
+        if _deferrable(ow, ob):
+            _wgrad(t, g, Np, Cout, 1, 1, geom, out=ow.t, dbias=ob.t, deferred=True, n_real=N)
+            dow = dob = None
+        else:
+            dob = _e((N,), F32, dev)
+            dow = _wgrad(t, g, Np, Cout, 1, 1, geom, dbias=dob)[:N]
+            if ow.direct and ob.direct:
+                ow.t.copy_(dow)
+                ob.t.copy_(dob)
+                dow = dob = None
+            else:
+                dow, dob = dow.contiguous(), dob.contiguous()
+        # BatchNorm backward of the output conv's data gradient, which is recomputed from g in both passes instead of stored
+        part, sums = _e((_lib.lib.pk_bn_bwd_blocks(M), 2, Cout), F32, dev), _e((2 * Cout,), F32, dev)
+        dgamma, dbeta = _Dest(g_p), _Dest(b_p)
+        draw = _e((B, Ho, Wo, Cout), BF16, dev)
+        call("pk_bn_out1x1_bwd", g, raw, mask, owd, mean, rstd, gamma, part, sums, dgamma.t, dbeta.t, draw, M, Cout, N, stream_ptr())
+        # the 3x3 conv's gradients, as _ConvBnAct.backward launches them
+        dx = _conv_dgrad(draw, wd, Cin, ksize, 1, (Hs, Ws)) if ctx.needs_input_grad[0] else None
+        w = _Dest(w_p)
+        _wgrad(x, draw, Cout, Cin, ksize, 1, (B, Hs, Ws, Ho, Wo), out=w.t, deferred=_deferrable(w))
+        return dx, w.grad(), dgamma.grad(), dbeta.grad(), dow, dob, None, None
+
+
+def conv_bn_act_out(x, conv, bn, out_conv, softplus=False, training=False):
+    """head_out(conv_bn_act(x, conv, bn, relu=True), out_conv, softplus).  In training, with autograd recording, no activation collector
+    installed (its taps need the activated tensor) and where the library says so (full-width tensors of 32 768 rows and more; switches
+    PK_BN_OUT1X1*), BatchNorm + ReLU + the output conv run as one pass forward and the output conv's data gradient is recomputed inside
+    BatchNorm backward; everything else takes the two ops."""
+    Cin = conv.weight.shape[1]
+    if (training and torch.is_grad_enabled() and _OBSERVER[0] is None and conv.stride[0] == 1 and out_conv.bias is not None and
+            x.shape[-1] == Cin and _lib.lib.pk_bn_out1x1_supported(x.shape[0] * x.shape[1] * x.shape[2], conv.weight.shape[0], out_conv.weight.shape[0])):
+        return _ConvBnActOut.apply(x, conv.weight, bn.weight, bn.bias, out_conv.weight, out_conv.bias, bn, softplus)
+    return head_out(conv_bn_act(x, conv, bn, True, None, training), out_conv, softplus)
 
 
 # ================================================================================================ HRFormer block halves
