@@ -136,7 +136,7 @@ class _Unit(torch.autograd.Function):
                     means[k], rstds[k] = nnops._e((Cout,), F32, dev), nnops._e((Cout,), F32, dev)
                     d.update(out=_p(raws[k]), stats=_p(part))
                     if l.relu and want_grad:       # the chain step's own ReLU as a bit mask for its BatchNorm backward
-                        masks[k] = nnops._e((M * Cout // 8,), torch.uint8, dev)
+                        masks[k] = nnops._relu_mask(M, Cout, dev)
                     bn = l.bn
                     wc.bn_eval.pop(id(bn), None)        # the kernel rewrites the running statistics in place (no version bump)
                     bns.append(dict(raw=_p(raws[k]), stats_partial=_p(part), gamma=_p(bn.weight), beta=_p(bn.bias), running_mean=_p(bn.running_mean),

@@ -15,6 +15,7 @@ Channel counts must be multiples of 8 (16-byte bf16 chunks) and head_dim a multi
 (models/padded.py).  There is no PyTorch / CPU fallback and nothing here touches oracle/.
 """
 import os
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -413,6 +414,17 @@ def _conv_geometry(x, ksize, stride):
     return B, Hs, Ws, Cin, (Hs + 2 * pad - ksize) // stride + 1, (Ws + 2 * pad - ksize) // stride + 1
 
 
+# One convolution as its Functions carry it from forward to backward: Cin is the width of x's pixels (the stem's 8, not its weight's 3),
+# M the number of output rows, maps the (B, Hs, Ws, Ho, Wo) that _wgrad takes, out the output's shape.
+_ConvShape = namedtuple("_ConvShape", "B Hs Ws Cin Ho Wo Cout ksize stride M maps out")
+
+
+def _conv_shape(x, weight, stride):
+    Cout, ksize = weight.shape[0], weight.shape[2]
+    B, Hs, Ws, Cin, Ho, Wo = _conv_geometry(x, ksize, stride)
+    return _ConvShape(B, Hs, Ws, Cin, Ho, Wo, Cout, ksize, stride, B * Ho * Wo, (B, Hs, Ws, Ho, Wo), (B, Ho, Wo, Cout))
+
+
 def _conv_raw(x, wf, Cout, ksize, stride, stats):
     B, Hs, Ws, Cin, Ho, Wo = _conv_geometry(x, ksize, stride)
     raw = _e((B, Ho, Wo, Cout), BF16, x.device)
@@ -490,6 +502,16 @@ def _linear_wgrad(w_param, b_param, x, g, N, Cin, **kw):
     return dw.grad(), db.grad()
 
 
+def _conv_grads(x, g, q, wd, w_param, need_dx, addend=None):
+    """The tail of every conv backward: from the output gradient `g` of the convolution `q` of `x`, the data gradient (when asked for, or
+    when there is an `addend` to carry) and the weight gradient into its destination (a fresh tensor when no parameter owns the weight).
+    -> (dx or None, what autograd gets for the weight)"""
+    dx = _conv_dgrad(g, wd, q.Cin, q.ksize, q.stride, (q.Hs, q.Ws), addend) if (need_dx or addend is not None) else None
+    w = _Dest(w_param, (q.Cout, q.Cin, q.ksize, q.ksize), x.device)
+    _wgrad(x, g, q.Cout, q.Cin, q.ksize, q.stride, q.maps, out=w.t, deferred=_deferrable(w))
+    return dx, w.grad()
+
+
 def _colsum(g, rows, N, rowmap=None, row_scale=None, rps=0, out=None):
     nb = _lib.lib.pk_ln_bwd_blocks(rows)
     part = _e((nb, N), F32, g.device)
@@ -525,6 +547,30 @@ def _bn_eval_affine(wc, bn, gamma, beta):
     return ent[1:]
 
 
+def _bn_batch_vectors(bn, C, dev):
+    """-> fresh (scale, shift, mean, rstd) for a training-mode BatchNorm kernel, which rewrites the running statistics in place (no
+    version bump): the module's eval-mode constants leave the weight cache."""
+    _wc().bn_eval.pop(id(bn), None)
+    return tuple(_e((C,), F32, dev) for _ in range(4))
+
+
+def _bn_finalize(part, M, gamma, beta, bn):
+    """Batch statistics of M rows from the partial sums `part` [rows][2][C] (pk_bn_finalize; the running statistics are updated).
+    -> (scale, shift, mean, rstd)"""
+    C = part.shape[-1]
+    scale, shift, mean, rstd = _bn_batch_vectors(bn, C, part.device)
+    call("pk_bn_finalize", part, part.shape[0], C, M, gamma, beta, bn.running_mean, bn.running_var, bn.num_batches_tracked, 0.1, 1e-5,
+         scale, shift, mean, rstd, stream_ptr())
+    return scale, shift, mean, rstd
+
+
+def _relu_mask(M, C, dev):
+    """A ReLU as one bit per element (a byte per 16-byte chunk): BatchNorm backward reads it in place of y, 1/16 of the bytes.  It exists
+    where there is a ReLU and a backward can come: on conv_bn_act's stored route with ReLU unless grad mode is off, on its recomputing
+    route with ReLU, on the output route always (ReLU is part of it); likewise in the exchange units.  The deconv stack keeps y."""
+    return _e((M * C // 8,), torch.uint8, dev)
+
+
 def _bn_forward(raw, part, gamma, beta, bn, res, relu, training, mask):
     """BatchNorm (+residual) (+ReLU, its bit mask into `mask`) of a raw conv output: on the batch statistics finalized from the partial
     sums `part` [rows][2][C] in training mode, on the running statistics otherwise.  -> (y, mean, rstd)"""
@@ -532,8 +578,7 @@ def _bn_forward(raw, part, gamma, beta, bn, res, relu, training, mask):
     M, dev = raw.numel() // C, raw.device
     y = _e(tuple(raw.shape), BF16, dev)
     if training:
-        _wc().bn_eval.pop(id(bn), None)        # the kernel below rewrites the running statistics in place (no version bump)
-        scale, shift, mean, rstd = (_e((C,), F32, dev) for _ in range(4))
+        scale, shift, mean, rstd = _bn_batch_vectors(bn, C, dev)
         # finalize + apply: one fused launch for small tensors, two kernels otherwise (the library decides)
         call("pk_bn_train_fwd", raw, part, part.shape[0], C, M, gamma, beta, bn.running_mean, bn.running_var, bn.num_batches_tracked,
              0.1, 1e-5, res, y, mean, rstd, scale, shift, 1 if relu else 0, mask, stream_ptr())
@@ -543,36 +588,37 @@ def _bn_forward(raw, part, gamma, beta, bn, res, relu, training, mask):
     return y, mean, rstd
 
 
+def _bn_backward_frame(rows, shape, dev, g_param, b_param, has_res, launch):
+    """What every BatchNorm backward owns: `rows` partial rows (the route's own size query) and the sums, the destinations of dgamma
+    and dbeta, draw and, with a residual, dres, both of the output's `shape`.  `launch(part, sums, dgamma, dbeta, draw, dres)` is the
+    route's one call.  -> (draw, dres or None, dgamma and dbeta as autograd gets them)"""
+    C = shape[-1]
+    part, sums = _e((rows, 2, C), F32, dev), _e((2 * C,), F32, dev)
+    dgamma, dbeta = _Dest(g_param), _Dest(b_param)
+    draw = _e(shape, BF16, dev)
+    dres = _e(shape, BF16, dev) if has_res else None
+    launch(part, sums, dgamma.t, dbeta.t, draw, dres)
+    return draw, dres, dgamma.grad(), dbeta.grad()
+
+
 def _bn_backward(dy, y, mask, raw, mean, rstd, gamma, g_param, b_param, relu, training, has_res):
-    """BatchNorm backward; the ReLU is masked by the forward's output `y` or its bit mask `mask`.
-    -> (draw, dres or None, dgamma and dbeta as autograd gets them)"""
+    """BatchNorm backward from the stored `raw`; the ReLU is masked by the forward's output `y` or its bit mask `mask`."""
     C = raw.shape[-1]
-    M, dev = raw.numel() // C, raw.device
-    nb = _lib.lib.pk_bn_bwd_blocks(M)
-    part, sums = _e((nb, 2, C), F32, dev), _e((2 * C,), F32, dev)
-    dgamma, dbeta = _Dest(g_param), _Dest(b_param)
-    draw = _e(tuple(raw.shape), BF16, dev)
-    dres = _e(tuple(raw.shape), BF16, dev) if has_res else None
+    M = raw.numel() // C
     # (eval mode, bit 1: the running statistics are constants, the input gradient is gamma * rstd * g without the batch-mean terms)
-    call("pk_bn_bwd", dy, y, raw, mean, rstd, gamma, part, sums, dgamma.t, dbeta.t, draw, dres, M, C,
-         (1 if relu else 0) | (0 if training else 2), mask, stream_ptr())
-    return draw, dres, dgamma.grad(), dbeta.grad()
+    flags = (1 if relu else 0) | (0 if training else 2)
+    return _bn_backward_frame(_lib.lib.pk_bn_bwd_blocks(M), tuple(raw.shape), raw.device, g_param, b_param, has_res, lambda *bufs: call(
+        "pk_bn_bwd", dy, y, raw, mean, rstd, gamma, *bufs, M, C, flags, mask, stream_ptr()))
 
 
-def _conv1x1_bn_backward(dy, x, wf, mask, mean, rstd, gamma, g_param, b_param, relu, has_res, out_shape):
-    """_bn_backward (training mode) of the recomputing route: the pre-normalisation tensor comes from (x, wf) again instead of memory."""
-    C = out_shape[-1]
-    M, dev = x.numel() // x.shape[-1], x.device
-    nb = _lib.lib.pk_conv1x1_bn_bwd_rows(M)
-    part, sums = _e((nb, 2, C), F32, dev), _e((2 * C,), F32, dev)
-    dgamma, dbeta = _Dest(g_param), _Dest(b_param)
-    draw = _e(out_shape, BF16, dev)
-    dres = _e(out_shape, BF16, dev) if has_res else None
-    call("pk_conv1x1_bn_bwd", dy, x, wf, mean, rstd, gamma, part, sums, dgamma.t, dbeta.t, draw, dres, M, x.shape[-1], C, 1 if relu else 0, mask,
-         stream_ptr())
-    return draw, dres, dgamma.grad(), dbeta.grad()
-
-
+# _ConvBnAct takes one of three routes, decided in forward and kept by name in ctx.route:
+#   affine     grad mode off, eval mode: the running statistics make BatchNorm a per-channel affine map, applied (with the residual and the
+#              ReLU) in the conv's epilogue: ONE launch, the pre-normalisation tensor never exists (pk_conv2d_affine_nhwc); nothing is saved
+#   recompute  training, a shallow 1x1 conv into a wide tensor (layer1's 64 -> 256 at >= 32 768 rows; the library is asked directly, as for
+#              pk_wgrad_slices): raw is never stored, every BatchNorm pass recomputes its tile from (x, wf) (pk_conv1x1_bn.hip); saved: the
+#              common set, so no tensor of the output's size but the bit mask
+#   stored     everything else: the conv stores raw, BatchNorm reads it; saved: the common set, raw and, without a mask, y
+# Common set: x, the forward weight pack, the ReLU bit mask (empty without one), the data-gradient pack, gamma, mean, rstd.
 class _ConvBnAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, gamma, beta, residual, bn, stride, relu, training, skip_out=None, skip_in=None, infer=False):
@@ -580,57 +626,46 @@ class _ConvBnAct(torch.autograd.Function):
         ctx.skip_out, ctx.skip_in = skip_out, skip_in      # skip_out: store d(residual) there; skip_in: add what was stored to dx
         wc = _wc()
         wf, wd = wc.fwd[id(weight)], wc.dgrad[id(weight)]
-        Cout, Cin_real, ksize = weight.shape[0], weight.shape[1], weight.shape[2]
         x = x.contiguous()
-        B, Hs, Ws, Cin, Ho, Wo = _conv_geometry(x, ksize, stride)
-        M = B * Ho * Wo
-        dev = x.device
+        q = _conv_shape(x, weight, stride)
+        dev, rflag = x.device, 1 if relu else 0
         res = None if residual is None else residual.contiguous()
         if infer and not training and os.environ.get("POSE_FUSED_EVAL_BN", "1") != "0":
-            # inference: the running statistics make BatchNorm a per-channel affine map -> applied (with the residual and the ReLU) in the
-            # conv's epilogue: ONE launch, the pre-normalisation tensor never exists (pk_conv2d_affine_nhwc)
+            ctx.route = "affine"
             scale, shift = _bn_eval_affine(wc, bn, gamma, beta)[:2]
-            y = _e((B, Ho, Wo, Cout), BF16, dev)
-            call("pk_conv2d_affine_nhwc", x, wf, y, scale, shift, res, 1 if relu else 0, B, Hs, Ws, Cin, Cout, ksize, stride, Ho, Wo, stream_ptr())
+            y = _e(q.out, BF16, dev)
+            call("pk_conv2d_affine_nhwc", x, wf, y, scale, shift, res, rflag, q.B, q.Hs, q.Ws, q.Cin, q.Cout, q.ksize, stride, q.Ho, q.Wo, stream_ptr())
             return y
-        # shallow 1x1 conv into a wide tensor (layer1's 64 -> 256 at >= 32 768 rows; the library is asked directly, as for pk_wgrad_slices):
-        # the pre-normalisation tensor is never stored, every BatchNorm pass recomputes its tile from x (pk_conv1x1_bn.hip)
-        ctx.recompute = bool(training and not infer and ksize == 1 and stride == 1 and _lib.lib.pk_conv1x1_bn_supported(M, Cin, Cout))
-        if ctx.recompute:
-            # statistics pass, finalize, apply pass; backward likewise from (x, wf).  Saved: no tensor of the output's size but the bit mask.
-            wc.bn_eval.pop(id(bn), None)
-            part = _e((_lib.lib.pk_conv1x1_stats_rows(M), 2, Cout), F32, dev)
-            call("pk_conv1x1_stats", x, wf, part, M, Cin, Cout, stream_ptr())
-            mask = _e((M * Cout // 8,), torch.uint8, dev) if relu else None
-            y = _e((B, Ho, Wo, Cout), BF16, dev)
-            scale, shift, mean, rstd = (_e((Cout,), F32, dev) for _ in range(4))
-            call("pk_bn_finalize", part, part.shape[0], Cout, M, gamma, beta, bn.running_mean, bn.running_var, bn.num_batches_tracked, 0.1, 1e-5,
-                 scale, shift, mean, rstd, stream_ptr())
-            call("pk_conv1x1_bn_act", x, wf, scale, shift, res, y, 1 if relu else 0, mask, M, Cin, Cout, stream_ptr())
-            ctx.save_for_backward(x, wf, x.new_empty(0) if mask is None else mask, mean, rstd, gamma, wd)
+        ctx.q, ctx.relu, ctx.training, ctx.has_res = q, relu, training, res is not None
+        mask = _relu_mask(q.M, q.Cout, dev) if (relu and not infer) else None
+        common = (x, wf, _stash(mask, x), wd, gamma)          # (the mask at index 2: tests/test_gpu_bn_out1x1.py reads it there)
+        if training and not infer and q.ksize == 1 and stride == 1 and _lib.lib.pk_conv1x1_bn_supported(q.M, q.Cin, q.Cout):
+            ctx.route = "recompute"                          # statistics pass, finalize, apply pass; backward likewise from (x, wf)
+            part = _e((_lib.lib.pk_conv1x1_stats_rows(q.M), 2, q.Cout), F32, dev)
+            call("pk_conv1x1_stats", x, wf, part, q.M, q.Cin, q.Cout, stream_ptr())
+            scale, shift, mean, rstd = _bn_finalize(part, q.M, gamma, beta, bn)
+            y = _e(q.out, BF16, dev)
+            call("pk_conv1x1_bn_act", x, wf, scale, shift, res, y, rflag, mask, q.M, q.Cin, q.Cout, stream_ptr())
+            ctx.save_for_backward(*common, mean, rstd)
         else:
-            raw, part = _conv_raw(x, wf, Cout, ksize, stride, training)
-            # ReLU mask as one bit per element (a byte per 16-byte chunk): BatchNorm backward reads it instead of y (1/16 of the bytes)
-            mask = _e((M * Cout // 8,), torch.uint8, dev) if (relu and not infer) else None
+            ctx.route = "stored"
+            raw, part = _conv_raw(x, wf, q.Cout, q.ksize, stride, training)
             y, mean, rstd = _bn_forward(raw, part, gamma, beta, bn, res, relu, training, mask)
-            # (the stem keeps its FORWARD pack: its data gradient is pk_stem_dgrad, and its data-gradient pack has only the real input rows)
-            ctx.save_for_backward(x, raw, y if mask is None else mask, mean, rstd, gamma, wf if Cin != Cin_real else wd)
-        ctx.has_mask = mask is not None
-        ctx.meta = (stride, relu, training, residual is not None, Cin_real, ksize, (B, Hs, Ws, Ho, Wo), Cout)
+            ctx.save_for_backward(*common, mean, rstd, raw, _stash(y if mask is None else None, x))
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, raw, y, mean, rstd, gamma, wd = ctx.saved_tensors
-        stride, relu, training, has_res, Cin_real, ksize, (B, Hs, Ws, Ho, Wo), Cout = ctx.meta
-        Cin = x.shape[-1]
+        x, wf, mask, wd, gamma, mean, rstd, *stored = ctx.saved_tensors
+        q, mask, dy = ctx.q, _unstash(mask), dy.contiguous()
         w_p, g_p, b_p = ctx.params
-        if ctx.recompute:
-            draw, dres, dgamma, dbeta = _conv1x1_bn_backward(dy.contiguous(), x, raw, y if ctx.has_mask else None, mean, rstd, gamma, g_p, b_p,
-                                                             relu, has_res, (B, Ho, Wo, Cout))
+        if ctx.route == "recompute":
+            draw, dres, dgamma, dbeta = _bn_backward_frame(
+                _lib.lib.pk_conv1x1_bn_bwd_rows(q.M), q.out, x.device, g_p, b_p, ctx.has_res, lambda *bufs: call(
+                    "pk_conv1x1_bn_bwd", dy, x, wf, mean, rstd, gamma, *bufs, q.M, q.Cin, q.Cout, 1 if ctx.relu else 0, mask, stream_ptr()))
         else:
-            draw, dres, dgamma, dbeta = _bn_backward(dy.contiguous(), None if ctx.has_mask else y, y if ctx.has_mask else None, raw, mean, rstd,
-                                                     gamma, g_p, b_p, relu, training, has_res)
+            raw, y = stored
+            draw, dres, dgamma, dbeta = _bn_backward(dy, _unstash(y), mask, raw, mean, rstd, gamma, g_p, b_p, ctx.relu, ctx.training, ctx.has_res)
         addend = None
         if ctx.skip_in is not None:
             addend, ctx.skip_in.g = ctx.skip_in.g, None
@@ -638,20 +673,18 @@ class _ConvBnAct(torch.autograd.Function):
                 raise _lib.PoseKernelError("residual block backward out of order: the skip gradient has not been produced yet")
         if ctx.skip_out is not None:
             ctx.skip_out.g, dres = dres, None                # handed to the block's first conv instead of to autograd
-        if Cin != Cin_real:                # stem: 3 real input channels inside 8-channel pixels
+        c_real = w_p.shape[1]
+        if q.Cin != c_real:                # stem: 3 real input channels inside 8-channel pixels
             # its data gradient (input attribution only: in training the packed input never requires grad) is NOT the implicit GEMM with
-            # Cin = 8: the data-gradient pack holds the Cin_real real rows only, a launch over 8 would read the next weight's bytes
-            dx = _stem_dgrad(draw, wd, Cin_real, ksize, stride, (Hs, Ws), ctx.recompute, addend) if ctx.needs_input_grad[0] else None
-            dw = _wgrad(x, draw, Cout, Cin, ksize, stride, (B, Hs, Ws, Ho, Wo))[:, :Cin_real].contiguous()
-            dst = grad_sink_of(w_p)
-            if dst is not None:
-                dst.copy_(dw)
-                dw = None
-        else:
-            dx = _conv_dgrad(draw, wd, Cin, ksize, stride, (Hs, Ws), addend) if (ctx.needs_input_grad[0] or addend is not None) else None
+            # Cin = 8: the data-gradient pack holds the c_real real rows only, a launch over 8 would read the next weight's bytes, so
+            # pk_stem_dgrad takes the FORWARD pack.  The weight gradient is computed 8 wide; its real channels go to the destination.
+            dx = _stem_dgrad(draw, wf, c_real, q.ksize, q.stride, (q.Hs, q.Ws), ctx.route == "recompute", addend) if ctx.needs_input_grad[0] else None
+            # (not out=w.t: the kernel writes all 8 input channels, the destination has the weight's c_real)
             w = _Dest(w_p)
-            _wgrad(x, draw, Cout, Cin, ksize, stride, (B, Hs, Ws, Ho, Wo), out=w.t, deferred=_deferrable(w))
+            w.t.copy_(_wgrad(x, draw, q.Cout, q.Cin, q.ksize, q.stride, q.maps)[:, :c_real])
             dw = w.grad()
+        else:
+            dx, dw = _conv_grads(x, draw, q, wd, w_p, ctx.needs_input_grad[0], addend)
         return dx, dw, dgamma, dbeta, dres, None, None, None, None, None, None, None
 
 
@@ -731,19 +764,14 @@ class _ConvW(torch.autograd.Function):
         x = x.contiguous()
         raw, part = _conv_raw(x, wf, N, k, 1, True)
         ctx.save_for_backward(x, wd)
-        ctx.meta = (N, Cin, k)
+        ctx.q = _conv_shape(x, w, 1)
         ctx.mark_non_differentiable(part)
         return raw, part
 
     @staticmethod
     def backward(ctx, g, _gpart):
         x, wd = ctx.saved_tensors
-        N, Cin, k = ctx.meta
-        B, H, W, _ = x.shape
-        g = g.contiguous()
-        dx = _conv_dgrad(g, wd, Cin, k, 1, (H, W)) if ctx.needs_input_grad[0] else None
-        dw = _wgrad(x, g, N, Cin, k, 1, (B, H, W, H, W))
-        return dx, dw
+        return _conv_grads(x, g.contiguous(), ctx.q, wd, None, ctx.needs_input_grad[0])
 
 
 class _BnActOnly(torch.autograd.Function):
@@ -787,6 +815,37 @@ def deconv_bn_relu(x, deconv, bn, training):
 
 
 # ================================================================================================ head output conv
+# Backward of a 1x1 output conv into fp32 NCHW maps, in two steps because its users launch other work in between (_HeadOut: the data
+# gradient; _ConvBnActOut: nothing, and BatchNorm backward after both).
+def _out_grad_rows(dout, maps):
+    """The maps' gradient (B,N,H,W) fp32 -> bf16 rows (B,H,W,up8(N)), pad channels 0; through softplus' derivative where the forward's
+    `maps` are given."""
+    B, N, H, W = dout.shape
+    g = _e((B, H, W, _up8(N)), BF16, dout.device)
+    call("pk_nchw_f32_to_nhwc_bf16", dout.contiguous(), maps, g, B, N, H, W, g.shape[-1], stream_ptr())
+    return g
+
+
+def _out_conv_wgrad(x, g, N, w_param, b_param):
+    """Weight and bias gradient of the output conv with N real outputs from its input `x` and the 8-aligned rows `g`.
+    -> what autograd gets for the two"""
+    B, H, W, Cin = x.shape
+    Np, geom = g.shape[-1], (B, H, W, H, W)
+    w, b = _Dest(w_param), _Dest(b_param)
+    if _deferrable(w, b):
+        # slabs only; the step's one pk_reduce_many sums the first N of the Np rows straight into the sinks (was: a reduce launch + two
+        # copies per head output, at the very start of backward)
+        _wgrad(x, g, Np, Cin, 1, 1, geom, out=w.t, dbias=b.t, deferred=True, n_real=N)
+        return None, None
+    db = _e((N,), F32, x.device)
+    dw = _wgrad(x, g, Np, Cin, 1, 1, geom, dbias=db)[:N]
+    if w.direct and b.direct:
+        w.t.copy_(dw)
+        b.t.copy_(db)
+        return None, None
+    return dw.contiguous(), db.contiguous()
+
+
 class _HeadOut(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, softplus):
@@ -798,34 +857,15 @@ class _HeadOut(torch.autograd.Function):
         N = weight.shape[0]
         out = _e((B, N, H, W), F32, x.device)
         call("pk_conv2d_nhwc", x, wf, out, None, bias, B, H, W, Cin, N, 1, 1, 0, H, W, 2 if softplus else 0, 2, None, stream_ptr())
-        ctx.save_for_backward(x, out if softplus else x.new_empty(0), wd)
-        ctx.meta = (softplus, N)
+        ctx.save_for_backward(x, _stash(out if softplus else None, x), wd)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        x, y, wd = ctx.saved_tensors
-        softplus, N = ctx.meta
-        B, H, W, Cin = x.shape
-        Np = _up8(N)
-        g = _e((B, H, W, Np), BF16, x.device)
-        call("pk_nchw_f32_to_nhwc_bf16", dout.contiguous(), y if softplus else None, g, B, N, H, W, Np, stream_ptr())
-        dx = _e((B, H, W, Cin), BF16, x.device)
-        call("pk_conv2d_nhwc", g, wd, dx, None, None, B, H, W, Np, Cin, 1, 1, 0, H, W, 0, 0, None, stream_ptr())
-        w, b = (_Dest(p) for p in ctx.params)
-        geom = (B, H, W, H, W)
-        if _deferrable(w, b):
-            # slabs only; the step's one pk_reduce_many sums the first N of the Np (8-aligned) rows straight into the sinks (was: a reduce
-            # launch + two copies per head output, at the very start of backward)
-            _wgrad(x, g, Np, Cin, 1, 1, geom, out=w.t, dbias=b.t, deferred=True, n_real=N)
-            return dx, None, None, None
-        db = _e((N,), F32, x.device)
-        dw = _wgrad(x, g, Np, Cin, 1, 1, geom, dbias=db)[:N]
-        if w.direct and b.direct:
-            w.t.copy_(dw)
-            b.t.copy_(db)
-            return dx, None, None, None
-        return dx, dw.contiguous(), db.contiguous(), None
+        x, maps, wd = ctx.saved_tensors
+        g = _out_grad_rows(dout, _unstash(maps))
+        dx = _conv_dgrad(g, wd, x.shape[-1], 1, 1, x.shape[1:3])
+        return (dx, *_out_conv_wgrad(x, g, dout.shape[1], *ctx.params), None)
 
 
 def head_out(x, conv, softplus=False):
@@ -844,57 +884,31 @@ class _ConvBnActOut(torch.autograd.Function):
         wc = _wc()
         wf, wd = wc.fwd[id(weight)], wc.dgrad[id(weight)]
         owf, owd = wc.fwd[id(out_weight)], wc.dgrad[id(out_weight)]
-        Cout, ksize, N = weight.shape[0], weight.shape[2], out_weight.shape[0]
+        N = out_weight.shape[0]
         x = x.contiguous()
-        B, Hs, Ws, Cin, Ho, Wo = _conv_geometry(x, ksize, 1)
-        M, dev = B * Ho * Wo, x.device
-        wc.bn_eval.pop(id(bn), None)           # pk_bn_finalize rewrites the running statistics in place (no version bump)
-        raw, part = _conv_raw(x, wf, Cout, ksize, 1, True)
-        scale, shift, mean, rstd = (_e((Cout,), F32, dev) for _ in range(4))
-        call("pk_bn_finalize", part, part.shape[0], Cout, M, gamma, beta, bn.running_mean, bn.running_var, bn.num_batches_tracked, 0.1, 1e-5,
-             scale, shift, mean, rstd, stream_ptr())
-        mask = _e((M * Cout // 8,), torch.uint8, dev)
-        t = _e((B, Ho, Wo, Cout), BF16, dev)
-        out = _e((B, N, Ho, Wo), F32, dev)
-        call("pk_bn_out1x1_fwd", raw, scale, shift, owf, out_bias, t, out, mask, M, Cout, N, Ho * Wo, 1 if softplus else 0, stream_ptr())
-        ctx.save_for_backward(x, raw, t, mask, mean, rstd, gamma, wd, owd, out if softplus else x.new_empty(0))
-        ctx.meta = (softplus, N, ksize, (B, Hs, Ws, Ho, Wo), Cout)
+        q = ctx.q = _conv_shape(x, weight, 1)
+        dev = x.device
+        raw, part = _conv_raw(x, wf, q.Cout, q.ksize, 1, True)
+        scale, shift, mean, rstd = _bn_finalize(part, q.M, gamma, beta, bn)
+        mask = _relu_mask(q.M, q.Cout, dev)
+        t = _e(q.out, BF16, dev)
+        out = _e((q.B, N, q.Ho, q.Wo), F32, dev)
+        call("pk_bn_out1x1_fwd", raw, scale, shift, owf, out_bias, t, out, mask, q.M, q.Cout, N, q.Ho * q.Wo, 1 if softplus else 0, stream_ptr())
+        ctx.save_for_backward(x, raw, t, mask, mean, rstd, gamma, wd, owd, _stash(out if softplus else None, x))
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        x, raw, t, mask, mean, rstd, gamma, wd, owd, y = ctx.saved_tensors
-        softplus, N, ksize, (B, Hs, Ws, Ho, Wo), Cout = ctx.meta
+        x, raw, t, mask, mean, rstd, gamma, wd, owd, maps = ctx.saved_tensors
         w_p, g_p, b_p, ow_p, ob_p = ctx.params
-        Cin, M, dev = x.shape[-1], B * Ho * Wo, x.device
-        # the maps' gradient as bf16 rows and the output conv's weight / bias gradient, as _HeadOut.backward launches them
-        Np = _up8(N)
-        g = _e((B, Ho, Wo, Np), BF16, dev)
-        call("pk_nchw_f32_to_nhwc_bf16", dout.contiguous(), y if softplus else None, g, B, N, Ho, Wo, Np, stream_ptr())
-        ow, ob = _Dest(ow_p), _Dest(ob_p)
-        geom = (B, Ho, Wo, Ho, Wo)
-        if _deferrable(ow, ob):
-            _wgrad(t, g, Np, Cout, 1, 1, geom, out=ow.t, dbias=ob.t, deferred=True, n_real=N)
-            dow = dob = None
-        else:
-            dob = _e((N,), F32, dev)
-            dow = _wgrad(t, g, Np, Cout, 1, 1, geom, dbias=dob)[:N]
-            if ow.direct and ob.direct:
-                ow.t.copy_(dow)
-                ob.t.copy_(dob)
-                dow = dob = None
-            else:
-                dow, dob = dow.contiguous(), dob.contiguous()
+        q, N = ctx.q, dout.shape[1]
+        g = _out_grad_rows(dout, _unstash(maps))
+        dow, dob = _out_conv_wgrad(t, g, N, ow_p, ob_p)
         # BatchNorm backward of the output conv's data gradient, which is recomputed from g in both passes instead of stored
-        part, sums = _e((_lib.lib.pk_bn_bwd_blocks(M), 2, Cout), F32, dev), _e((2 * Cout,), F32, dev)
-        dgamma, dbeta = _Dest(g_p), _Dest(b_p)
-        draw = _e((B, Ho, Wo, Cout), BF16, dev)
-        call("pk_bn_out1x1_bwd", g, raw, mask, owd, mean, rstd, gamma, part, sums, dgamma.t, dbeta.t, draw, M, Cout, N, stream_ptr())
-        # the 3x3 conv's gradients, as _ConvBnAct.backward launches them
-        dx = _conv_dgrad(draw, wd, Cin, ksize, 1, (Hs, Ws)) if ctx.needs_input_grad[0] else None
-        w = _Dest(w_p)
-        _wgrad(x, draw, Cout, Cin, ksize, 1, (B, Hs, Ws, Ho, Wo), out=w.t, deferred=_deferrable(w))
-        return dx, w.grad(), dgamma.grad(), dbeta.grad(), dow, dob, None, None
+        draw, _, dgamma, dbeta = _bn_backward_frame(_lib.lib.pk_bn_bwd_blocks(q.M), tuple(raw.shape), x.device, g_p, b_p, False, lambda *bufs: call(
+            "pk_bn_out1x1_bwd", g, raw, mask, owd, mean, rstd, gamma, *bufs[:5], q.M, q.Cout, N, stream_ptr()))
+        dx, dw = _conv_grads(x, draw, q, wd, w_p, ctx.needs_input_grad[0])
+        return dx, dw, dgamma, dbeta, dow, dob, None, None
 
 
 def conv_bn_act_out(x, conv, bn, out_conv, softplus=False, training=False):
