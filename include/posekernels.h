@@ -262,6 +262,49 @@ int pk_position_histogram(const float* coords, const float* conf, const double* 
 int pk_motion_spectrum(const float* coords, const float* conf, double* power, double* summary, int S, int T, int K, float min_conf,
                        int N, int j0, int F, int window, void* stream);
 
+/* ---- limb kinematics of pose sequences (this project's own specification: DESIGN.md "Limb kinematics") ------------------------------
+ * coords (S,T,K,2) f32 image pixels, conf (S,T,K) f32 or NULL, frames valid as for pk_motion_stats.  A SERIES is a float64 array (S,T,Q) whose
+ * element is valid iff it is finite: the first two entries write NaN for "no value".  No float atomics, no global atomics; float64 on
+ * exactly widened inputs, one rounding per operation, every floating-point sum in the fixed order of pk_motion_stats: two launches give
+ * identical bits.
+ * pk_joint_angles: triples (A,3) int32 on the device, joints (a, b, c) in [0, K) with a != b and b != c, 1 <= A <= PK_KIN_MAX_ANGLES; angles
+ *   (S,T,A), every element written.  u = p_a - p_b, v = p_c - p_b, cr = u.x v.y - u.y v.x, dt = u.x v.x + u.y v.y, theta = atan2(|cr|, dt) in
+ *   [0, pi]: the unsigned interior angle at b.  NaN when one of the three joints is invalid or a ray has no length (not u.u > 0 or not
+ *   v.v > 0), and for a triple that breaks the rule above (the caller checks its host copy; the kernel never reads out of range).
+ * pk_joint_speeds: speeds (S,T,K): sqrt(dx dx + dy dy) of p[t+1] - p[t] when frames t and t + 1 are valid, else NaN; the last frame is NaN.
+ * pk_series_stats: stats (S,Q,PK_KIN_STATS_COLS).  Columns: 0 n valid; 1 minimum, 2 maximum (0 without a valid element); 3 mean = sum x / n
+ *   (0 when n = 0); 4 population sd = sqrt(sum (x - mean)^2 / n) with the mean as stored in column 3 (0 when n = 0); 5 sum |x[t+1] - x[t]|
+ *   over the steps whose two ends are valid; 6 the number of such steps; 7 the largest such step.
+ * pk_series_xcorr: pairs (P,2) int32 on the device, series (i, j) in [0, Q); 0 <= max_lag = L <= PK_KIN_MAX_LAG; min_count >= 2.  corr (S,P,2L+1)
+ *   float64 and count (S,P,2L+1) int32: lag index l' is the lag l = l' - L; over V = {t : 0 <= t, t + l < T, x_i[t] and x_j[t + l] valid},
+ *   n = |V|: mx = sum x / n, my = sum y / n, sxx = sum (x - mx)^2, syy = sum (y - my)^2, sxy = sum (x - mx)(y - my), r = sxy / sqrt(sxx syy);
+ *   r = 0 when n < 2 or not sxx syy > 0.  The pairs of a lag are summed in the order of the EARLIER of their two frames, so a lag's bits
+ *   depend on T and the two series alone (not on S, P, L or the other lags) and (i, j) at l equals (j, i) at -l bit for bit.  summary (S,P,4)
+ *   from the stored r and counts over the lags with count >= min_count: 0 r at lag 0 (0 if that lag does not qualify); 1 the lag l of the
+ *   largest r (the lowest l' among equal maxima); 2 that r; 3 that lag's count; 1-3 are 0 without a qualifying lag.  Two launches.
+ * pk_sample_entropy: tol (S,Q) float64, the absolute tolerance of each series; 1 <= m <= PK_KIN_MAX_M; T <= PK_KIN_MAX_T, else
+ *   PK_ERR_UNSUPPORTED.  counts (S,Q,3) int64: 0 |W|, W = {i : 0 <= i <= T - m - 1, x[i .. i + m] all valid}; 1 B and 2 A, the pairs i < j of W
+ *   with max_{k<m} |x[i+k] - x[j+k]| <= tol and max_{k<=m} ... <= tol: fabs(a - b) <= tol in float64, equality is a match.  A tolerance that
+ *   is not finite or is negative gives (|W|, 0, 0).  SampEn = -ln(A / B) is the caller's.  workspace: S Q pk_sample_entropy_tiles(T, m) rows of
+ *   2 int64 (never NULL: one row for a query of 0), every row written: the template starts are cut into blocks of PK_KIN_ENTROPY_TILE and one
+ *   workgroup counts one pair of blocks; a second launch adds the rows.  pk_sample_entropy_tiles: nb (nb + 1) / 2 with
+ *   nb = ceil((T - m) / PK_KIN_ENTROPY_TILE); 0 for T <= m, T > PK_KIN_MAX_T or an m out of range.                                       */
+#define PK_KIN_MAX_ANGLES 64
+#define PK_KIN_MAX_LAG 4096
+#define PK_KIN_MAX_M 4
+#define PK_KIN_MAX_T 262144
+#define PK_KIN_STATS_COLS 8
+#define PK_KIN_ENTROPY_TILE 256
+int pk_joint_angles(const float* coords, const float* conf, const int32_t* triples, double* angles, int S, int T, int K, int A,
+                    float min_conf, void* stream);
+int pk_joint_speeds(const float* coords, const float* conf, double* speeds, int S, int T, int K, float min_conf, void* stream);
+int pk_series_stats(const double* series, double* stats, int S, int T, int Q, void* stream);
+int pk_series_xcorr(const double* series, const int32_t* pairs, double* corr, int32_t* count, double* summary, int S, int T, int Q, int P,
+                    int max_lag, int min_count, void* stream);
+int pk_sample_entropy_tiles(int T, int m);
+int pk_sample_entropy(const double* series, const double* tol, int64_t* workspace, int64_t* counts, int S, int T, int Q, int m,
+                      void* stream);
+
 /* ---- localisation error analysis (this project's own specification, DESIGN.md "Localisation error analysis": the numbers behind the
  * reference's PerformanceAnalyzer, analysis/nn_quantitative_viz.py:105-252).  One launch each; no float atomics, no global atomics; every
  * output is an integer count, an order statistic or a fixed-order sum, so the same input gives the same bits.

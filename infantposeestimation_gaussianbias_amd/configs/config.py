@@ -18,6 +18,8 @@ identically.  Extension over the reference: `get_config(path_or_name)` also acce
     heatmap-head models; a bad value raises and names the key).  `TEST.POST_PROCESS` and `TEST.SHIFT_HEATMAP` are deliberately NOT mapped:
     both shipped yamls set them true, and mapping them would change what those configurations do today.  `CLINICAL.FREQUENCY_BAND:
     [lo, hi]` (Hz; this project's own key) maps onto `cfg.frequency_band`, the band of the movement spectrum; a bad value names the key.
+    `CLINICAL.JOINT_ANGLES: {name: [a, b, c]}` and `CLINICAL.KINEMATICS: {MAX_LAG, ENTROPY_M, ENTROPY_R}` (this project's own keys) map onto
+    `cfg.joint_angles` / `cfg.kinematics`, the angle table and settings of the limb kinematics; `cfg.clinical` keeps its four entries.
     `LOSS.USE_OHKM` / `LOSS.TOPK` (HRNet's keys; TOPK defaults to 8) / `LOSS.OHKM_WEIGHT` map onto `cfg.model.ohkm_topk` /
     `cfg.model.ohkm_weight` (online hard keypoint mining; off unless USE_OHKM is true).
 """
@@ -145,6 +147,12 @@ class Config:
     # Movement spectrum (this project's own legacy-yaml key CLINICAL.FREQUENCY_BAND, `inference.py --freq_band`), a plain class attribute as
     # well.  frequency_band: None or (f_min, f_max) in Hz, the band whose dominant frequency and power `movement_report` adds per joint.
     frequency_band = None
+    # Limb kinematics (this project's own legacy-yaml keys CLINICAL.JOINT_ANGLES and CLINICAL.KINEMATICS, `inference.py --kinematics`), plain
+    # class attributes as well.  joint_angles: None (COCO_ANGLES of utils/kinematics.py for 17 joints) or {name: (a, b, c)}, the angle at joint
+    # b between the rays to a and c; kinematics: None or {'max_lag': frames or None, 'entropy': (m, r)}, the lags searched by the
+    # cross-correlation and the template length and tolerance of the sample entropy.
+    joint_angles = None
+    kinematics = None
 
 
 _PRESETS = {
@@ -204,6 +212,60 @@ def check_frequency_band(band, what="frequency_band") -> Tuple[float, float]:
     if not ok:
         raise ValueError(f"{what} must be [f_min, f_max] in Hz with 0 <= f_min < f_max, got {band!r}")
     return lo, hi
+
+
+def check_joint_angles(table, what="joint_angles", num_joints=None):
+    """A table of joint angles as an ordered {name: (a, b, c)}: a non-empty mapping (at most 64 entries) of names onto three integer joints,
+    a != b and b != c, each in 0 .. num_joints - 1 where the layout is known.  ValueError naming `what` (the key or argument the value
+    came from) otherwise."""
+    if not isinstance(table, dict) or not 1 <= len(table) <= 64:
+        raise ValueError(f"{what} must map 1 to 64 names onto joints [a, b, c], got {table!r}")
+    out = {}
+    for name, triple in table.items():
+        try:
+            ok = len(triple) == 3 and all(not isinstance(v, bool) and int(v) == v for v in triple)
+            a, b, c = (int(v) for v in triple) if ok else (0, 0, 0)
+            ok = ok and min(a, b, c) >= 0 and a != b and b != c and (num_joints is None or max(a, b, c) < num_joints)
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            top = "" if num_joints is None else f" of 0 to {int(num_joints) - 1}"
+            raise ValueError(f"{what}[{name!r}] must be three joints [a, b, c]{top} with a != b and b != c, got {triple!r}")
+        out[str(name)] = (a, b, c)
+    return out
+
+
+def check_kinematics(max_lag=None, entropy=None, what=("max_lag", "entropy m", "entropy r")):
+    """The settings of the limb kinematics as {'max_lag': None or an integer from 0 to 4096 (frames), 'entropy': None or (m, r) with m an
+    integer from 1 to 4 and r finite and >= 0}.  ValueError naming the entry of `what` (key, flag or argument) the bad value came from."""
+    out = {"max_lag": None, "entropy": None}
+    if max_lag is not None:
+        try:
+            ok = not isinstance(max_lag, bool) and int(max_lag) == max_lag and 0 <= int(max_lag) <= 4096
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f"{what[0]} must be an integer from 0 to 4096 frames, got {max_lag!r}")
+        out["max_lag"] = int(max_lag)
+    if entropy is not None:
+        try:
+            m, r = entropy
+        except (TypeError, ValueError):
+            raise ValueError(f"{what[1]} and {what[2]}: expected (m, r), got {entropy!r}") from None
+        try:
+            ok = not isinstance(m, bool) and int(m) == m and 1 <= int(m) <= 4
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f"{what[1]} must be an integer from 1 to 4, got {m!r}")
+        try:
+            ok = not isinstance(r, (bool, str)) and math.isfinite(float(r)) and float(r) >= 0
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f"{what[2]} must be a finite number >= 0 (a share of the standard deviation), got {r!r}")
+        out["entropy"] = (int(m), float(r))
+    return out
 
 
 def check_ohkm(topk, weight=1.0, num_keypoints=None, allow_off=True, what=("ohkm_topk", "ohkm_weight")):
@@ -413,6 +475,16 @@ def _apply_legacy_yaml(cfg: Config, path: str) -> Config:
     # CLINICAL.FREQUENCY_BAND: [lo, hi] in Hz is this project's own key (the reference's yamls have none): the band of the movement spectrum
     if cl.get('FREQUENCY_BAND') is not None:
         cfg.frequency_band = check_frequency_band(cl['FREQUENCY_BAND'], 'CLINICAL.FREQUENCY_BAND')
+    # CLINICAL.JOINT_ANGLES: {name: [a, b, c]} and CLINICAL.KINEMATICS: {MAX_LAG, ENTROPY_M, ENTROPY_R} are this project's own keys as well:
+    # the angle table and the settings of `kinematics_report`.  They land on attributes of their own; `cfg.clinical` keeps its four entries.
+    if cl.get('JOINT_ANGLES') is not None:
+        cfg.joint_angles = check_joint_angles(cl['JOINT_ANGLES'], 'CLINICAL.JOINT_ANGLES')
+    if cl.get('KINEMATICS') is not None:
+        kin = cl['KINEMATICS']
+        if not isinstance(kin, dict) or set(kin) - {'MAX_LAG', 'ENTROPY_M', 'ENTROPY_R'}:
+            raise ValueError(f"CLINICAL.KINEMATICS must be a mapping with the keys MAX_LAG, ENTROPY_M, ENTROPY_R, got {kin!r}")
+        cfg.kinematics = check_kinematics(kin.get('MAX_LAG'), (kin.get('ENTROPY_M', 2), kin.get('ENTROPY_R', 0.2)),
+                                          ('CLINICAL.KINEMATICS.MAX_LAG', 'CLINICAL.KINEMATICS.ENTROPY_M', 'CLINICAL.KINEMATICS.ENTROPY_R'))
     cfg.exp_name = os.path.splitext(os.path.basename(path))[0]
     return cfg
 

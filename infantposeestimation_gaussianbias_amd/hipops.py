@@ -703,6 +703,119 @@ def motion_spectrum(coords, conf=None, min_conf=0.3, n_fft=None, j0=1, n_bins=No
     return power, summary
 
 
+# ------------------------------------------------------------------------------------------------ limb kinematics
+KIN_MAX_ANGLES = _lib.CONSTANTS["PK_KIN_MAX_ANGLES"]
+KIN_MAX_LAG = _lib.CONSTANTS["PK_KIN_MAX_LAG"]
+KIN_MAX_M = _lib.CONSTANTS["PK_KIN_MAX_M"]
+KIN_MAX_T = _lib.CONSTANTS["PK_KIN_MAX_T"]
+KIN_STATS_COLS = _lib.CONSTANTS["PK_KIN_STATS_COLS"]
+
+
+def _index_table(table, width, limit, name, what, distinct_neighbours=False):
+    """A host list / array (or tensor) of index rows -> (n, width) int32 numpy array, every entry in [0, limit): ValueError naming the row."""
+    rows = np.asarray(table.cpu() if isinstance(table, torch.Tensor) else table)
+    if rows.ndim != 2 or rows.shape[1] != width or rows.shape[0] < 1 or rows.dtype.kind not in "iu":
+        raise ValueError(f"{name}: expected at least one row of {width} integer {what}, got {rows.dtype} {tuple(rows.shape)}")
+    rows = rows.astype(np.int64)
+    for i, row in enumerate(rows):
+        if (row < 0).any() or (row >= limit).any():
+            raise ValueError(f"{name}[{i}] = {tuple(int(v) for v in row)}: {what} lie in 0 to {limit - 1}")
+        if distinct_neighbours and (row[0] == row[1] or row[1] == row[2]):
+            raise ValueError(f"{name}[{i}] = {tuple(int(v) for v in row)}: the middle joint must differ from both ends")
+    return np.ascontiguousarray(rows, np.int32)
+
+
+def _series(series, name="series"):
+    """series (S,T,Q) float64: shape (ValueError) -> S, T, Q."""
+    if series.dim() != 3:
+        raise ValueError(f"{name}: expected (S, T, Q), got {tuple(series.shape)}")
+    return tuple(int(v) for v in series.shape)
+
+
+def joint_angles(coords, conf, min_conf, triples):
+    """(S,T,K,2) image-pixel trajectories (+ (S,T,K) confidences or None) and `triples`, a host list of joints (a, b, c) -> (S,T,A) float64:
+    the unsigned interior angle at b in radians, NaN where one of the three joints is invalid or coincides with b (pk_joint_angles)."""
+    if coords.dim() != 4 or coords.shape[-1] != 2:
+        raise ValueError(f"coords: expected (S, T, K, 2), got {tuple(coords.shape)}")
+    tri = _index_table(triples, 3, int(coords.shape[2]), "triples", "joints", distinct_neighbours=True) if coords.shape[2] > 0 else None
+    if tri is None or not 1 <= tri.shape[0] <= KIN_MAX_ANGLES:
+        raise ValueError(f"triples: expected 1 to {KIN_MAX_ANGLES} angles over at least one joint")
+    coords, conf, S, T, K = _sequences(coords, conf)
+    A = int(tri.shape[0])
+    angles = torch.full((S, T, A), float("nan"), dtype=F64, device=coords.device)
+    if S * T > 0:
+        call("pk_joint_angles", coords, conf, torch.from_numpy(tri).to(coords.device), angles, S, T, K, A, float(min_conf), stream_ptr())
+    return angles
+
+
+def joint_speeds(coords, conf=None, min_conf=0.3):
+    """(S,T,K,2) trajectories -> (S,T,K) float64: |p[t+1] - p[t]| in pixels per frame where both frames are valid, else NaN (pk_joint_speeds)."""
+    coords, conf, S, T, K = _sequences(coords, conf)
+    speeds = torch.full((S, T, K), float("nan"), dtype=F64, device=coords.device)
+    _call_if(S * T * K, "pk_joint_speeds", coords, conf, speeds, S, T, K, float(min_conf), stream_ptr())
+    return speeds
+
+
+def series_stats(series):
+    """(S,T,Q) float64 series (NaN = no value) -> (S,Q,8) float64 (pk_series_stats: n, min, max, mean, population sd, sum of |steps|, number
+    of steps, largest step)."""
+    S, T, Q = _series(series)
+    series = _chk(series, F64, "series")
+    stats = torch.zeros(S, Q, KIN_STATS_COLS, dtype=F64, device=series.device)
+    _call_if(S * T * Q, "pk_series_stats", series, stats, S, T, Q, stream_ptr())
+    return stats
+
+
+def series_xcorr(series, pairs, max_lag, min_count=2):
+    """(S,T,Q) float64 series and `pairs`, a host list of series (i, j) -> corr (S,P,2L+1) float64, count (S,P,2L+1) int32 and summary (S,P,4)
+    float64 (pk_series_xcorr): Pearson's r of x_i[t] against x_j[t + l] over the co-valid frames of each lag l = -L .. L, and per pair r at
+    lag 0, the lag of the largest r, that r and its pair count over the lags with at least `min_count` pairs."""
+    S, T, Q = _series(series)
+    L, min_count = int(max_lag), int(min_count)
+    if not 0 <= L <= KIN_MAX_LAG:
+        raise ValueError(f"max_lag: expected 0 to {KIN_MAX_LAG}, got {max_lag}")
+    if min_count < 2:
+        raise ValueError(f"min_count: expected at least 2 (one pair has no correlation), got {min_count}")
+    if Q < 1:
+        raise ValueError(f"series: expected at least one series, got {tuple(series.shape)}")
+    pr = _index_table(pairs, 2, Q, "pairs", "series")
+    series = _chk(series, F64, "series")
+    P = int(pr.shape[0])
+    corr = torch.zeros(S, P, 2 * L + 1, dtype=F64, device=series.device)
+    count = torch.zeros(S, P, 2 * L + 1, dtype=I32, device=series.device)
+    summary = torch.zeros(S, P, 4, dtype=F64, device=series.device)
+    if S * T > 0:
+        call("pk_series_xcorr", series, torch.from_numpy(pr).to(series.device), corr, count, summary, S, T, Q, P, L, min_count, stream_ptr())
+    return corr, count, summary
+
+
+def sample_entropy_tiles(T, m):
+    """Partial-count rows per series of `sample_entropy_counts` (pk_sample_entropy_tiles)."""
+    return int(_lib.lib.pk_sample_entropy_tiles(int(T), int(m)))
+
+
+def sample_entropy_counts(series, tol, m=2, workspace=None):
+    """(S,T,Q) float64 series and their absolute tolerances (S,Q) float64 -> (S,Q,3) int64: the number of valid templates of length m + 1, and
+    the pairs of them that match within `tol` over m and over m + 1 elements, B and A of SampEn = -ln(A / B) (pk_sample_entropy).
+    workspace: None, or an int64 tensor of at least S Q sample_entropy_tiles(T, m) rows of 2 to use instead of a fresh one."""
+    S, T, Q = _series(series)
+    if tuple(tol.shape) != (S, Q):
+        raise ValueError(f"tol: expected {(S, Q)}, got {tuple(tol.shape)}")
+    m = int(m)
+    if not 1 <= m <= KIN_MAX_M:
+        raise ValueError(f"m: expected 1 to {KIN_MAX_M}, got {m}")
+    if T > KIN_MAX_T:
+        raise ValueError(f"series: {T} frames exceed the {KIN_MAX_T} of one call; analyse it in windows")
+    rows = S * Q * sample_entropy_tiles(T, m)
+    if workspace is not None and workspace.numel() < 2 * max(rows, 1):
+        raise ValueError(f"workspace: expected at least {2 * max(rows, 1)} int64, got {workspace.numel()}")
+    series, tol = _chk(series, F64, "series"), _chk(tol, F64, "tol")
+    workspace = torch.empty(max(rows, 1), 2, dtype=I64, device=series.device) if workspace is None else _chk(workspace, I64, "workspace")
+    counts = torch.zeros(S, Q, 3, dtype=I64, device=series.device)
+    _call_if(S * T * Q, "pk_sample_entropy", series, tol, workspace, counts, S, T, Q, m, stream_ptr())
+    return counts
+
+
 # ------------------------------------------------------------------------------------------------ localisation error analysis
 ERR_MAX_BINS = _lib.CONSTANTS["PK_ERR_MAX_BINS"]
 ERR_MAX_CONF_THRESHOLDS = _lib.CONSTANTS["PK_ERR_MAX_CONF_THR"]

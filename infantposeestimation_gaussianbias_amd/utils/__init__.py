@@ -2,6 +2,8 @@
 from .metrics import (AverageMeter, COCOEvaluator, KeypointErrorAnalyzer, MetricLogger, PCKAccumulator, calculate_movement_amplitude,
                       calculate_pck, calculate_temporal_consistency, keypoint_error_report, movement_heatmap, movement_report,
                       movement_spectrum)
+from . import kinematics
+from .kinematics import COCO_ANGLES, joint_angle_series, kinematics_report, limb_coordination, sample_entropy
 from . import activations
 from .activations import ActivationAnalyzer, ActivationCollector, activation_report
 from . import feature_maps
@@ -27,4 +29,5 @@ __all__ = ['AverageMeter', 'COCOEvaluator', 'MetricLogger', 'postprocess', 'visu
            'keypoint_error_report', 'sensitivity', 'SensitivityAnalyzer', 'occlusion_sensitivity_maps', 'activations',
            'ActivationAnalyzer', 'ActivationCollector', 'activation_report', 'uncertainty', 'UncertaintyAnalyzer', 'mc_uncertainty',
            'attribution_maps', 'GradCAMVisualizer', 'GradientCollector', 'feature_maps', 'FeatureCollector', 'FeatureVisualizer',
-           'HeatmapQualityAccumulator', 'feature_sheet', 'heatmap_quality', 'heatmap_quality_sheet']
+           'HeatmapQualityAccumulator', 'feature_sheet', 'heatmap_quality', 'heatmap_quality_sheet', 'kinematics', 'COCO_ANGLES',
+           'joint_angle_series', 'kinematics_report', 'limb_coordination', 'sample_entropy']

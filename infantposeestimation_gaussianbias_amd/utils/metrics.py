@@ -248,7 +248,7 @@ def calculate_temporal_consistency(keypoints_sequence, confidence=None, min_conf
 
 
 def movement_report(keypoints_sequence, confidence=None, flip_pairs=(), min_confidence: float = 0.3, min_movement: float = 5.0,
-                    max_movement: float = 200.0, asymmetry_threshold: float = 0.2, fps: Optional[float] = None, spectrum=None) -> Dict:
+                    max_movement: float = 200.0, asymmetry_threshold: float = 0.2, fps: Optional[float] = None, spectrum=None, kinematics=None) -> Dict:
     """JSON-serialisable movement summary of one (T,K,2) trajectory, built from ONE (K,11) device->host copy.  Per joint: amplitude, path
     length, mean and largest speed (px / frame, or px / s with `fps`), share of valid frames, and the flag 'low' (amplitude below
     `min_movement`), 'high' (above `max_movement`) or None.  Per (left, right) pair of `flip_pairs`: ratio = |a_L - a_R| / max(a_L, a_R)
@@ -256,7 +256,12 @@ def movement_report(keypoints_sequence, confidence=None, flip_pairs=(), min_conf
     its yaml's CLINICAL thresholds).
     spectrum=(f_min, f_max) in Hz (needs `fps`): the Hann-windowed movement spectrum of that band (`movement_spectrum`) adds, from one more
     (K,6) copy, `dominant_frequency` (Hz; None for a joint without power in the band), `peak_amplitude` (px) and `band_power` to each
-    joint, `frequency_difference` (Hz, or None) to each pair and `frequency_band` to the report.  Without it the report is unchanged."""
+    joint, `frequency_difference` (Hz, or None) to each pair and `frequency_band` to the report.  Without it the report is unchanged.
+    kinematics: a dict of `kinematics_report`'s keyword arguments `angles`, `max_lag`, `entropy` (an empty one: its defaults) adds
+    `report["kinematics"]`, that function's result for this trajectory, confidence, `flip_pairs`, `min_confidence` and `fps` (joint angles,
+    inter-limb coordination, sample entropy: utils/kinematics.py).  Without it the report is unchanged."""
+    if kinematics is not None and (not isinstance(kinematics, dict) or set(kinematics) - {"angles", "max_lag", "entropy"}):
+        raise ValueError(f"movement_report: kinematics takes a dict with the keys angles, max_lag, entropy, got {kinematics!r}")
     band = None
     if spectrum is not None:
         if fps is None:
@@ -273,6 +278,10 @@ def movement_report(keypoints_sequence, confidence=None, flip_pairs=(), min_conf
     if band is not None:
         _, summary = hipops.motion_spectrum(coords, conf, min_confidence, T, j0, F, 1)
         _add_spectrum_to_report(report, summary[0].cpu().numpy(), band, T, float(fps))
+    if kinematics is not None:
+        from .kinematics import kinematics_report
+        report["kinematics"] = kinematics_report(keypoints_sequence, confidence, flip_pairs=flip_pairs, min_confidence=min_confidence, fps=fps,
+                                                 **kinematics)
     return report
 
 

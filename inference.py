@@ -12,7 +12,8 @@ With `decode='unbiased'` (`--decode unbiased [--modulate_kernel K]`, or the conf
 unbiased, distribution-aware step (pk_unbiased_decode) instead of the quarter-pixel shift -- single images, `--scales` and `--sequence` alike.
 `predict_sequence` / `--sequence` take the frames of a video (a directory of images) for one person and keep the trajectory on the device
 for the movement analysis of utils/metrics.py (temporal smoothing, `movement_report`, `movement_heatmap`); `--freq_band LO HI` with `--fps`
-adds the movement spectrum of that band (pk_motion_spectrum) to the report.
+adds the movement spectrum of that band (pk_motion_spectrum) to the report, `--kinematics` the joint angles, the inter-limb coordination
+and the sample entropy (csrc/pk_kinematics.hip).
 Visualisation is on the device too: `visualize` / `visualize_batch` draw through utils/visualization.py (pk_draw_shapes,
 pk_heatmap_overlay, pk_heatmap_overlay_patches: this project's own integer rasterisation rule, not OpenCV's pixels) and files are written
 with Pillow.
@@ -307,12 +308,27 @@ def detect_persons(img: np.ndarray) -> List[np.ndarray]:
 _FRAME_SUFFIXES = (".png", ".jpg", ".jpeg", ".bmp")
 
 
+def _kinematics_settings(cfg, kinematics):
+    """`sequence_report`'s `kinematics` -> None or the dict `movement_report` takes: the caller's entries over the config's."""
+    if kinematics is None or kinematics is False:
+        return None
+    settings = {}
+    if getattr(cfg, "joint_angles", None):
+        settings["angles"] = dict(cfg.joint_angles)
+    settings.update({k: v for k, v in (getattr(cfg, "kinematics", None) or {}).items() if v is not None})
+    if kinematics is not True:
+        settings.update({k: v for k, v in dict(kinematics).items() if v is not None})
+    return settings
+
+
 def sequence_report(pose: PoseInference, frames, bbox=None, smooth: Optional[int] = None, fps: Optional[float] = None, batch_size: int = 16,
-                    freq_band=None):
+                    freq_band=None, kinematics=None):
     """Movement analysis of one person over `frames` (BGR arrays of one size): `predict_sequence`, temporal smoothing when `smooth` (an odd
     window, 'gaussian') or the config's `temporal` asks for it, then `movement_report` with the config's visibility and CLINICAL
     thresholds.  `freq_band` (f_min, f_max) in Hz, or the config's `frequency_band` when `fps` is known, adds the movement spectrum's
-    entries (dominant frequency, peak amplitude, band power); `freq_band` without `fps` is a ValueError.
+    entries (dominant frequency, peak amplitude, band power); `freq_band` without `fps` is a ValueError.  `kinematics` (True, or a dict with
+    any of `angles`, `max_lag`, `entropy`) adds `report["kinematics"]` (joint angles, inter-limb coordination, sample entropy:
+    `kinematics_report`); what the dict leaves out comes from the config's `joint_angles` / `kinematics`, then from the defaults.
     -> (report dict, keypoints (T,K,2) and scores (T,K) on the device, the keypoints as analysed)."""
     cfg = pose.cfg
     kp, sc = pose.predict_sequence(frames, bbox, batch_size=batch_size)
@@ -323,7 +339,7 @@ def sequence_report(pose: PoseInference, frames, bbox=None, smooth: Optional[int
     band = freq_band if freq_band is not None else (getattr(cfg, "frequency_band", None) if fps is not None else None)
     report = movement_report(kp, sc, flip_pairs=cfg.data.flip_pairs, min_confidence=cfg.min_keypoint_visibility,
                              min_movement=clinical.get("min_movement", 5.0), max_movement=clinical.get("max_movement", 200.0), fps=fps,
-                             spectrum=None if band is None else tuple(band))
+                             spectrum=None if band is None else tuple(band), kinematics=_kinematics_settings(cfg, kinematics))
     report["smoothing"] = list(temporal) if temporal else None
     return report, kp, sc
 
@@ -339,7 +355,12 @@ def main_sequence(args, pose):
     if len({f.shape for f in frames}) != 1:
         raise SystemExit("--sequence: the frames differ in size")
     bbox = np.array(args.bbox) if args.bbox else None
-    report, kp, sc = sequence_report(pose, frames, bbox, smooth=args.smooth, fps=args.fps, freq_band=getattr(args, "freq_band", None))
+    kinematics = None
+    if getattr(args, "kinematics", False):
+        entropy = getattr(args, "entropy", None)
+        kinematics = {"max_lag": getattr(args, "max_lag", None), "entropy": None if entropy is None else (int(entropy[0]), entropy[1])}
+    report, kp, sc = sequence_report(pose, frames, bbox, smooth=args.smooth, fps=args.fps, freq_band=getattr(args, "freq_band", None),
+                                     kinematics=kinematics)
     report["frames"] = names
     text = json.dumps(report, indent=2)
     if args.report:
@@ -491,7 +512,8 @@ def main(args):
 
 class _Parser(argparse.ArgumentParser):
     """--uncertainty excludes --occlusion_map and --sequence, and --saliency_map and --grad_cam exclude each other and all three;
-    --feature_maps excludes all of them: refused while parsing, like any other bad combination of switches."""
+    --feature_maps excludes all of them; --kinematics needs --sequence, and --max_lag / --entropy belong to it: refused while parsing, like
+    any other bad combination of switches."""
 
     def parse_args(self, args=None, namespace=None):
         ns = super().parse_args(args, namespace)
@@ -518,6 +540,14 @@ class _Parser(argparse.ArgumentParser):
                 self.error("--feature_zoom takes 1 to 64 pixels per element")
         elif ns.feature_channels is not None or ns.feature_zoom is not None:
             self.error("--feature_channels and --feature_zoom belong to --feature_maps")
+        if ns.kinematics and not ns.sequence:
+            self.error("--kinematics analyses a trajectory and needs --sequence")
+        if (ns.max_lag is not None or ns.entropy is not None) and not ns.kinematics:
+            self.error("--max_lag and --entropy belong to --kinematics")
+        if ns.max_lag is not None and not 0 <= ns.max_lag <= 4096:
+            self.error("--max_lag takes 0 to 4096 frames")
+        if ns.entropy is not None and not (ns.entropy[0] in (1.0, 2.0, 3.0, 4.0) and 0 <= ns.entropy[1] < float("inf")):
+            self.error("--entropy takes a template length M from 1 to 4 and a tolerance R >= 0")
         if ns.grad_cam_layer is not None and ns.grad_cam is None:
             self.error("--grad_cam_layer names the layer of --grad_cam")
         return ns
@@ -551,6 +581,15 @@ def build_parser():
                    help='--sequence with --fps: add the movement spectrum of the band LO to HI Hz to the report (per joint the dominant '
                         'frequency, its amplitude and the band power; per left/right pair the frequency difference); default: the '
                         'config\'s frequency_band')
+    p.add_argument('--kinematics', action='store_true',
+                   help='--sequence: add the limb kinematics to the report: per joint angle (elbows, shoulders, hips, knees of the 17-joint '
+                        'layout, or the config\'s joint_angles) its range, mean, angular speed and sample entropy, and per left/right pair '
+                        'the cross-correlation at lag 0, its peak and the lag of the peak')
+    p.add_argument('--max_lag', type=int, default=None, metavar='N',
+                   help='--kinematics: lags searched on both sides, in frames (default: the config\'s, else one second with --fps, else 30)')
+    p.add_argument('--entropy', type=float, nargs=2, default=None, metavar=('M', 'R'),
+                   help='--kinematics: template length M (1 to 4) and tolerance R as a share of each series\' standard deviation '
+                        '(default: the config\'s, else 2 0.2)')
     p.add_argument('--report', type=str, default=None, help='--sequence: write the movement report (JSON) here instead of printing it; --uncertainty: write the per-joint numbers '
                                                                '(JSON) here as well')
     p.add_argument('--decode', type=str, choices=('shift', 'unbiased'), default=None,
